@@ -72,6 +72,8 @@ def parse():
     ap.add_argument('--force-device', type=int, default=None, help='rehearsal only: put every rank on this device')
     ap.add_argument('--force-dist', action='store_true', help='rehearsal only: create the process group even for one rank, so that '
                                                                'the RCCL calls of the N > 1 path run on a one-GPU box')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write every shard's (U, V) tables they left as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -315,6 +317,32 @@ def train_leg(D, workload, n_shards, d, batch, steps, warmup, split, roofline_st
         out['job'] = None
         out['shards'] = None
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, leg, rank, world):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- (U, V) of every shard this rank trains -- as
+    DIR/[rank<r>_]U<s>.npy and V<s>.npy, float32.  Over the byte budget (64 MB, shared by the ranks) every table is cut to the same
+    fixed, seeded sample of its rows (sorted row ids), so that two builds given the same arguments write comparable files."""
+    job, spec = leg['job'], leg['spec']
+    if job is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    n_user, n_item, n_tab = spec['n_user'], spec['n_item'], len(leg['mine'])
+    budget = DUMP_MAX_BYTES // world - 2 * n_tab * 128            # (128: the header of a .npy file)
+    frac = min(1.0, budget / (n_tab * (n_user + n_item) * job.k * 4))
+    pick = {}
+    for name, n, seed in (('U', n_user, 0), ('V', n_item, 1)):
+        m = int(n * frac)
+        pick[name] = None if m == n else torch.as_tensor(np.sort(np.random.RandomState(seed).choice(n, m, replace=False)), device=job.device)
+    prefix = f'rank{rank}_' if world > 1 else ''
+    for k, s in enumerate(leg['mine']):
+        for name, t in zip(('U', 'V'), job.tables(k)):
+            if pick[name] is not None:
+                t = t.index_select(0, pick[name])
+            np.save(os.path.join(out_dir, f'{prefix}{name}{s}.npy'), t.float().cpu().numpy())
 
 
 def source_hash():
@@ -675,6 +703,8 @@ def main():
     split = bool(a.split) and D.pg is not None
     leg = train_leg(D, a.workload, a.shards, a.d, a.batch, a.steps, a.warmup, split, a.roofline_steps, keep_job=True)
     spec, job = leg['spec'], leg['job']
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, leg, rank, world)
 
     roofline = roofline_of(a, leg, a.d, a.batch) if job is not None and (rank == 0) else None
     if job is not None and rank != 0:

@@ -401,13 +401,15 @@ from ultrare_amd.read import RatingData, loadData
 rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
 n_user, n_item, k, E, sizes = eval(sys.argv[3])
 dist.init_process_group('gloo')
+def barrier():          # (dist.barrier() asks the HIP runtime for an accelerator, which opens the GPU on a GPU host: these ranks are CPU only)
+    dist.all_reduce(torch.zeros(1))
 rs = np.random.RandomState(0)
 loaders = [loadData(RatingData(np.vstack([rs.randint(0, n_user, n), rs.randint(0, n_item, n), rs.rand(n)])), 16, 1) for n in sizes]
 ids = list(range(len(sizes)))
 owner = assign_shards(sizes, world)
 prepare_owned(ids[:2], [rank, rank], rank, loaders[:2], 64, 64, 4, 1, on_device=False)      # (library, thread pools: loaded before the clock starts)
 torch.manual_seed(42)
-dist.barrier()
+barrier()
 from ultrare_amd import rng
 rng.STATS.update(normals=0, skipped_draws=0)
 t0 = time.thread_time()            # (CPU time of this thread: eight ranks and their transport threads share this host's cores)
@@ -424,7 +426,7 @@ all_s = 0.0
 if len(ids) > 4:        # the same phase with every shard owned by this rank, under the same load (the other ranks do the same now)
     state = torch.get_rng_state()
     torch.manual_seed(42)
-    dist.barrier()
+    barrier()
     t0 = time.thread_time()
     prepare_owned(ids, [rank] * len(ids), rank, loaders, n_user, n_item, k, E, on_device=False)
     all_s = time.thread_time() - t0
@@ -553,12 +555,12 @@ def test_bench_spawn_propagates_rank_failure_without_hanging():
     """`python bench.py --gpus 2` with no launcher starts two rank processes itself.  In this container
     there is no GPU, so every rank stops with the 'needs an MI355X' message: the parent must come back
     promptly with a non-zero code (and must not have touched the GPU itself)."""
+    if torch.cuda.is_available():
+        pytest.skip('a GPU is visible: covered by tests/test_gpu_multirank.py')
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=300)
-    if torch.cuda.is_available():
-        pytest.skip('a GPU is visible: covered by tests/test_gpu_multirank.py')
     assert p.returncode != 0 and time.time() - t0 < 120
     # the first failing rank decides the code; its peers get a grace period to report by themselves before they are
     # terminated, so at least one message (normally both) arrives
@@ -590,6 +592,42 @@ def test_bench_counts_interactions_exactly():
     assert tot == 3 * 70 + 3 * 25 + 3 * 100
     assert per_tick[:4].tolist() == [30 + 25 + 30, 30 + 25 + 30, 10 + 25 + 30, 30 + 0 + 10]
     assert dense[:4].tolist() == [111, 111, 111, 101] and dense[9:].tolist() == [100, 100, 100]
+
+
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """--dump-outputs: every shard's (U, V) as float32 .npy files; tables beyond 64 MB in all are cut to one seeded row sample,
+    the same from run to run."""
+    import importlib.util
+    sp = importlib.util.spec_from_file_location('bench', os.path.join(ROOT, 'bench.py'))
+    b = importlib.util.module_from_spec(sp)
+    sp.loader.exec_module(b)
+
+    class Job:
+        k, device = 4, torch.device('cpu')
+
+        def __init__(self, tables):
+            self.t = tables
+
+        def tables(self, s):
+            return self.t[s]
+    g = torch.Generator().manual_seed(1)
+    small = Job([(torch.randn(60, 4, generator=g), torch.randn(34, 4, generator=g)) for _ in range(2)])
+    b.dump_outputs(str(tmp_path / 'small'), {'job': small, 'spec': {'n_user': 60, 'n_item': 34}, 'mine': [3, 4]}, 0, 1)
+    assert sorted(os.listdir(tmp_path / 'small')) == ['U3.npy', 'U4.npy', 'V3.npy', 'V4.npy']
+    got = np.load(tmp_path / 'small' / 'V4.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, small.t[1][1].numpy())
+    n_user, n_item = 3_000_000, 1_500_000                    # 2 x 72 MB of tables; row i holds i
+    big = Job([tuple(torch.arange(n, dtype=torch.float32)[:, None].expand(n, 4) for n in (n_user, n_item))])
+    for d in ('a', 'b'):
+        b.dump_outputs(str(tmp_path / d), {'job': big, 'spec': {'n_user': n_user, 'n_item': n_item}, 'mine': [0]}, 1, 2)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['rank1_U0.npy', 'rank1_V0.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= b.DUMP_MAX_BYTES // 2
+    for f, n in zip(files, (n_user, n_item)):
+        got = np.load(tmp_path / 'a' / f)
+        assert got.dtype == np.float32 and np.array_equal(got, np.load(tmp_path / 'b' / f))
+        rows = got[:, 0]
+        assert 0 < len(rows) < n and (np.diff(rows) > 0).all() and rows[-1] < n and (got == rows[:, None]).all()
 
 
 # ---------------------------------------------------------------- generator skip-ahead (ure_host_mt_advance)
