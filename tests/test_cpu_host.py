@@ -72,7 +72,7 @@ def test_no_step_kernel_instantiation_spills(lib):
     assert all(r['vgpr_spill'] == 0 for r in isa_report.kernels(lib.LIB_PATH))
 
 
-def test_no_kernel_is_built_in_threadgroup_split_mode(lib):
+def test_no_kernel_is_built_in_tgsplit_mode(lib, monkeypatch):
     """csrc/perm_tags.hip's waves hand inv[] to each other through global memory with workgroup-scope release (s_waitcnt vmcnt(0)) and
     no acquire-side invalidate -- the LLVM AMDGPU memory model's sequence for NON-tgsplit mode only.  The TG_SPLIT bit of every kernel
     descriptor of the built library must be clear, and the build refuses the flag."""
@@ -82,8 +82,9 @@ def test_no_kernel_is_built_in_threadgroup_split_mode(lib):
     assert any(r['name'].startswith('perm_tags_kernel') for r in rows)
     assert all(r['tg_split'] == 0 for r in rows), [r['name'] for r in rows if r['tg_split'] != 0]
     from ultrare_amd import build as lib_build
-    with pytest.raises(RuntimeError):
-        lib_build.build(force=True, defines=['X', 'Y -mtgsplit'], out='/tmp/never_built.so')
+    monkeypatch.setenv('HIPCC_COMPILE_FLAGS_APPEND', '-O3 -mtgsplit')
+    with pytest.raises(RuntimeError, match='tgsplit'):
+        lib_build.build(timeline='/tmp/never_built.so')
 
 
 def test_argument_errors_are_reported_not_crashed(lib):

@@ -1,6 +1,6 @@
-"""Full MF at the 25 M shape in touch_mode 3 (csrc/mf_index.h), one library build per process: step-launch time (event pair per launch),
-epoch-start time, interactions/s.  The synthetic set is cached under /tmp so that several builds can be compared in one session.
-    URE_LIB=tools/ab/lib_x.so URE_ALLOW_STALE_LIB=1 python tools/exp_index.py [--d 128] [--epochs 2] [--batch 30000]"""
+"""Full MF at the 25 M shape in touch_mode 3 (csrc/mf_index.h): step-launch time (event pair per launch), epoch-start time,
+interactions/s.  The synthetic set is cached under /tmp so that repeated runs in one session skip making it.
+    python tools/exp_index.py [--d 128] [--epochs 2] [--batch 30000]"""
 import argparse
 import json
 import os
@@ -30,7 +30,6 @@ def main():
     ap.add_argument('--d', type=int, default=128)
     ap.add_argument('--epochs', type=int, default=2)
     ap.add_argument('--batch', type=int, default=30000)
-    ap.add_argument('--label', default=os.environ.get('URE_LIB', 'product'))
     a = ap.parse_args()
     from ultrare_amd import engine, rng
     part, spec = dataset()
@@ -50,7 +49,7 @@ def main():
     t0 = time.perf_counter()
     step_ms, n_step, prep_ms, n_prep = job.run_profiled(a.epochs * steps)
     wall = time.perf_counter() - t0
-    out = {'label': a.label, 'd': a.d, 'touch': job.touch, 'index': getattr(job, 'index', False), 'steps_per_epoch': steps,
+    out = {'d': a.d, 'touch': job.touch, 'index': getattr(job, 'index', False), 'steps_per_epoch': steps,
            'step_us': round(step_ms / n_step * 1e3, 2), 'epoch_start_ms': round(prep_ms / a.epochs, 3), 'prep_launch_groups': n_prep,
            'rows_per_step': job.touch_rows_per_step(), 'epoch_ms_device': round((step_ms + prep_ms) / a.epochs, 3),
            'minter_per_s': round(n * a.epochs / ((step_ms + prep_ms) * 1e-3) / 1e6, 1), 'wall_s_profiled': round(wall, 3)}
@@ -63,7 +62,6 @@ def main():
     torch.cuda.synchronize()
     out['epoch_ms_plain'] = round(ev0.elapsed_time(ev1) / a.epochs, 3)
     out['minter_per_s_plain'] = round(n * a.epochs / (ev0.elapsed_time(ev1) * 1e-3) / 1e6, 1)
-    out['overlap'] = os.environ.get('URE_INDEX_OVERLAP', '1')
     job.close()
     print(json.dumps(out), flush=True)
 

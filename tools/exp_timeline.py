@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Inside one step launch: when every workgroup starts and ends (diagnostic build).
 
-    python -m ultrare_amd.build --timeline tools/ab/libtimeline.so      # here (cross-compiles)
-    python tools/exp_timeline.py [--lib tools/ab/libtimeline.so]         # on the GPU box
+    python -m ultrare_amd.build --timeline ultrare_amd/libultrare_hip_timeline.so      # here (cross-compiles)
+    python tools/exp_timeline.py [--lib ultrare_amd/libultrare_hip_timeline.so]         # on the GPU box
 
 Prints, for 14 consecutive launches of the bench workload (ml-1m shape, 5 shards, d=32), the start
 / duration / end distribution of the workgroups by kind: `multi` = unit workgroups holding a row cut
@@ -13,7 +13,7 @@ import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
-ap.add_argument('--lib', default=os.path.join(ROOT, 'tools', 'ab', 'libtimeline.so'))
+ap.add_argument('--lib', default=os.path.join(ROOT, 'ultrare_amd', 'libultrare_hip_timeline.so'))
 ap.add_argument('--shards', type=int, default=5)
 a = ap.parse_args()
 from ultrare_amd import _native as nv

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('URE_LIB') or os.path.join(_PKG, 'libultrare_hip.so')      # URE_LIB: experiment builds (tools/) only
+LIB_PATH = os.path.join(_PKG, 'libultrare_hip.so')
 ABI_VERSION = 9
 MAX_MODELS_PER_CALL = 32
 
@@ -142,10 +142,10 @@ def lib():
         if L.ure_abi_version() != ABI_VERSION:
             raise NativeError(f'ABI mismatch: library {L.ure_abi_version()} != binding {ABI_VERSION}')
         # the library must be the build of THIS tree's sources (they travel together): a stale .so is an error,
-        # not something to run silently.  URE_ALLOW_STALE_LIB=1 is for experiment builds (tools/) only.
+        # not something to run silently.  (tools/exp_timeline.py points LIB_PATH at the diagnostic build, whose hash differs.)
         from . import build as _build
         have, want = L.ure_source_hash().decode().replace('URE_SRC_HASH=', ''), _build.source_hash()
-        if have != want and os.environ.get('URE_ALLOW_STALE_LIB', '0') != '1' and LIB_PATH == _build.LIB:
+        if have != want and LIB_PATH == _build.LIB:
             raise NativeError(f'{LIB_PATH} was built from other sources (hash {have}, tree {want}): run `python -m ultrare_amd.build`')
         _lib = L
     return _lib

@@ -1,6 +1,6 @@
 """Build libultrare_hip.so (HIP kernels + C ABI) in-tree for gfx950 with hipcc.
 
-    python -m ultrare_amd.build [--force] [--timeline OUT.so] [--out OUT.so -DNAME=VALUE ...]
+    python -m ultrare_amd.build [--force] [--timeline OUT.so]
 
 The library is compiled for MI355X only (--offload-arch=gfx950); hipcc
 cross-compiles without a GPU.  The built .so is git-ignored but travels with the
@@ -90,16 +90,16 @@ def _stale():
     return built_hash() != source_hash()
 
 
-def build(force=False, verbose=False, timeline=None, defines=(), out=None):
+def build(force=False, verbose=False, timeline=None):
     """timeline=PATH builds a diagnostic library there instead (per-workgroup timestamps inside the
     step kernel, -DURE_TIMELINE; see tools/exp_timeline.py) and leaves the product library alone."""
-    if not timeline and not out and not force and not _stale():
+    if not timeline and not force and not _stale():
         return LIB
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     if not os.path.exists(hipcc):
         raise RuntimeError('hipcc not found: libultrare_hip.so cannot be built')
-    out = timeline or out or LIB
-    extra = (['-DURE_TIMELINE'] if timeline else []) + ['-D' + d for d in defines]
+    out = timeline or LIB
+    extra = ['-DURE_TIMELINE'] if timeline else []
     # csrc/perm_tags.hip exchanges data between the waves of a workgroup with the workgroup-scope release / acquire of NON-tgsplit mode
     # (LLVM AMDGPU memory model); in threadgroup-split mode it would read stale lines silently
     if any('tgsplit' in f and not f.startswith('-mno') for f in FLAGS + extra + os.environ.get('HIPCC_COMPILE_FLAGS_APPEND', '').split()):
@@ -123,6 +123,4 @@ def build(force=False, verbose=False, timeline=None, defines=(), out=None):
 
 if __name__ == '__main__':
     tl = sys.argv[sys.argv.index('--timeline') + 1] if '--timeline' in sys.argv else None
-    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
-    defs = [a[2:] for a in sys.argv if a.startswith('-D')]
-    print(build(force='--force' in sys.argv, verbose=True, timeline=tl, defines=defs, out=out))
+    print(build(force='--force' in sys.argv, verbose=True, timeline=tl))

@@ -54,19 +54,6 @@ def mark(label):
         HOST_TRACE.append((label, time.perf_counter()))
 
 
-_SIDE_STREAMS = {}
-
-
-def side_streams(dev, n):
-    """n HIP streams beside the current one, kept per device (independent chains of short launches -- the test series of a
-    request's shards -- run on them side by side)."""
-    key = str(torch.device(dev))
-    have = _SIDE_STREAMS.setdefault(key, [])
-    while len(have) < n:
-        have.append(torch.cuda.Stream(dev))
-    return have[:n]
-
-
 def to_device_async(arr, dev):
     """A small host array -> device tensor without stalling the host: through a pooled pinned buffer and an asynchronous
     copy (from pageable memory `.to(device)` waits until the stream has reached and finished the copy)."""

@@ -89,7 +89,7 @@ def prepare_owned(ids, owner, rank, train_dlist, n_user, n_item, k, epochs, on_d
         specs, order = [], []
         # permutation chunks: 8 epochs each for a few shards (a 5-shard call: 8 -> 13.8 / 11.7 ms learn / unlearn, 17 -> 19.7 /
         # 14.2), larger ones when many shards make many chunk uploads (16 shards: 8 -> 21.6 / 23.2, 13 -> 20.9 / 20.1;
-        # tools/ab_host.py medians): about 64 chunks per call.
+        # ab_host.py medians, a script since removed: see git history): about 64 chunks per call.
         n_owned = sum(1 for pos in range(len(ids)) if owner[pos] == rank)
         chunk_epochs = max(8, -(-epochs * n_owned // 64))
         for pos, i in enumerate(ids):
@@ -193,14 +193,6 @@ def exchange_tables(models, ids, owner, rank, rows, n_item, k, device, dist, ful
     return out
 
 
-def untouched_scale(lr, lr_decay, epochs, steps, lam, momentum, lr_step=50):
-    """a_T of a row that only decays (no interaction in its shard) after the whole training:
-    w_T = float32(a_T) * w_0 -- the same closed form ure_job_materialize applies on the owner."""
-    lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(epochs)], dtype=np.float32)
-    a = engine.closed_form_scalars(lr_host, steps, float(np.float32(lam)), float(np.float32(momentum)))
-    return np.float32(a[-1]) if len(a) else np.float32(1.0)
-
-
 class Sisa(Scratch):
     def __init__(self, param={}, model_type='mf', n_group=5, group_index=[]):
         super(Sisa, self).__init__(param, model_type)
@@ -227,9 +219,6 @@ class Sisa(Scratch):
         self.log0 = log
 
     # ------------------------------------------------------------------ helpers
-    def _rows(self, i):
-        return torch.as_tensor(np.asarray(self.group_index[i], dtype=np.int64))
-
     def _rows_dev(self, i):
         """group_index[i] as a device int64 tensor; all groups go up together, once per (group_index object, its group sizes, device):
         the reference reads self.group_index at every merge (sisa.py:55-56), so a reassigned list or another current device must not
@@ -392,7 +381,8 @@ class Sisa(Scratch):
         if dist:
             queue_series(lambda j: padded_tables(out[j])[:2])
             engine.mark('series_queued')
-        # two copies for the whole call (a copy per shard and kind was a synchronisation each; tools/ab_host.py medians of 6:
+        # two copies for the whole call (a copy per shard and kind was a synchronisation each; medians of 6 of ab_host.py,
+        # since removed:
         # 13.5 / 12.2 -> 12.1 / 12.2 ms learn / unlearn at 5 shards, within the noise at 16)
         if mine:
             from .. import rng

@@ -52,7 +52,7 @@ def limit_torch_threads():
     50-80 ms stalls in the middle of a 15 ms Sisa.learn (cpu.stat: 28 of 285 periods throttled; profiles/r03/NOTES.md).
     The pool is capped at 4 threads (and at the CPUs this rank may really use, host_cpus()): the CPU-side torch ops of the path are
     small (fills of ~200 k normals, copies) and run on several worker threads at once, where a wide intra-op pool only adds hand-offs
-    -- medians of alternating runs (tools/ab_host.py), learn / unlearn at 5 shards: 16.4 / 14.3 ms with 16 threads, 14.6 / 13.1 with 4,
+    -- medians of alternating runs (ab_host.py, since removed: see git history), learn / unlearn at 5 shards: 16.4 / 14.3 ms with 16 threads, 14.6 / 13.1 with 4,
     15.2 / 14.0 with 1; at 16 shards 24.3 / 27.0, 27.6 / 24.8, 22.5 / 20.2.  URE_TORCH_THREADS=0 leaves torch alone, =n sets n."""
     import os
     env = os.environ.get('URE_TORCH_THREADS', '')
@@ -95,7 +95,7 @@ def perm_threads():
     import os
     env = os.environ.get('URE_PERM_THREADS')
     # (the rank's CPUs, not more: with 32 threads on a 16-CPU grant the isolated expansion is faster -- 2.3 against 3.0 ms per 250
-    # permutations -- and the whole call slower, medians of 5 alternating runs: learn 17.3 against 15.2 ms; tools/ab_host.py)
+    # permutations -- and the whole call slower, medians of 5 alternating runs: learn 17.3 against 15.2 ms; ab_host.py, since removed)
     return max(1, int(env)) if env else min(64, host_cpus())
 
 
