@@ -1040,9 +1040,10 @@ def test_work_units_of_several_passes(lib):
             assert len(units) < len(lib.build_units(sched, sh.n_active, d, 1))
 
 
-def test_host_batch_tags_are_the_inverse_permutation_in_batches():
+def test_host_batch_tags_are_the_inverse_permutation_in_batches(monkeypatch):
     """ure_host_randperm_tags (struct ure_shard: file_tags): tags[t][perm_t[b]] = b // batch for the very permutations
-    ure_host_randperm / torch.randperm give -- the numbers the device otherwise derives from perm (csrc/tag_prep.h)."""
+    ure_host_randperm / torch.randperm give -- the numbers the device otherwise derives from perm (csrc/tag_prep.h).  And when an order
+    travels as tags (rng.tags_batch_for): at most 65535 steps, below ATen's huge-n randperm, unless URE_HOST_TAGS=0."""
     from ultrare_amd import rng
     seeds = [3, 2 ** 40 + 17, 99, 12345678901]
     for n, batch in ((1, 5), (7, 3), (1000, 64), (30001, 30000), (180000, 30000), (5000, 1)):
@@ -1056,6 +1057,13 @@ def test_host_batch_tags_are_the_inverse_permutation_in_batches():
         assert np.array_equal(tags, want), (n, batch)
     with pytest.raises(Exception):
         rng.epoch_tags(seeds, 70000, 1)                 # more than 65535 steps per epoch
+    monkeypatch.delenv('URE_HOST_TAGS', raising=False)
+    huge = rng.RANDPERM_HUGE_N
+    for n, batch, want in ((1, 5, 5), (65535, 1, 1), (65536, 1, 0), (0, 64, 0), (100, 0, 0), (65535 * 3000, 3000, 3000),
+                           (65535 * 3000 + 1, 3000, 0), (huge - 1, 1 << 20, 1 << 20), (huge, 1 << 20, 0)):
+        assert rng.tags_batch_for(n, batch) == want, (n, batch)
+    monkeypatch.setenv('URE_HOST_TAGS', '0')
+    assert rng.tags_batch_for(1000, 64) == 0 and rng.tags_batch_for(1000, 64, honour_env=False) == 64
 
 
 def test_layouts_and_units_from_one_native_call():

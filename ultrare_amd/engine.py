@@ -420,7 +420,8 @@ class TrainJob:
 
     shards : list[ShardData]
     inits  : list of (U0 [n_user,k], V0 [n_item,k]) float32 numpy / CPU tensors
-    perms  : list of int32 [epochs, N_s] arrays (numpy or torch; CPU or device), or int16 batch tags (rng.epoch_tags)
+    perms  : list of int32 [epochs, N_s] arrays (numpy or torch; CPU or device), or int16 batch tags (rng.epoch_tags); a device
+             tensor may still be arriving (its rng.Arrival)
     """
 
     def __init__(self, shards, inits, perms, k, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50, lazy_rows=None, snapshots=False,
@@ -471,8 +472,10 @@ class TrainJob:
         small = [lr_host] + ([closed_form_scalars(lr_host, st_, float(np.float32(lam)), float(np.float32(momentum))) for st_ in steps_of] if self.snapshots else [])
         small = upload_many(small, dev)                  # the learning rates and every shard's closed-form scalars: one copy
         self.lr = small[0]
-        self._chunks = []        # per shard whose permutations are uploaded in chunks: [(first epoch after the chunk, event), ...]
+        self._arrivals = []      # the rng.Arrival of every order that has one: run() waits for their chunks, check_tags() reads their flags
+        self.wait_marks = None   # a list: run() adds an event pair around each wait of its stream for a chunk (bench.py)
         descs = (nv.UreShard * len(shards))()
+        from . import rng
         mark('job: start')
         cur = torch.cuda.current_stream(dev) if torch.device(dev).type == 'cuda' else None
         seen = set()
@@ -518,11 +521,12 @@ class TrainJob:
                 at += al(x)
             self._offs.append(off)
             pU, pV, pmU, pmV, psse, pU0, pV0 = (base + 4 * o for o in off)
+            arrival = rng.Arrival.of(perm)                  # (before a conversion could make another tensor)
+            if arrival is not None:
+                self._arrivals.append(arrival)
+                if arrival.whole:                           # uploaded on a side stream in one piece (rng.epoch_perms_async)
+                    arrival.wait(cur, self.epochs)
             perm = torch.as_tensor(perm)
-            if getattr(perm, '_ure_chunks', None) is not None:      # still arriving in chunks of epochs (rng.shard_draws_async)
-                self._chunks.append(list(perm._ure_chunks))
-            elif getattr(perm, '_ure_event', None) is not None:     # uploaded on a side stream (rng.epoch_perms_async)
-                cur.wait_event(perm._ure_event)
             assert perm.shape == (self.epochs, sh.N), f'perm of shard {s} must be [epochs, N]'
             # int16: not permutations but the batch tags the host made of them (rng.epoch_tags; struct ure_shard: file_tags)
             as_tags = perm.dtype == torch.int16
@@ -606,6 +610,11 @@ class TrainJob:
                           snapV=sp[at + nU:at + nU + self.epochs * sh.n_item * d].view(self.epochs, sh.n_item, d))
         return st
 
+    @property
+    def chunk_wait_s(self):
+        """Host seconds run() has waited for chunks of the orders to be queued."""
+        return sum(a.waited_s for a in self._arrivals)
+
     def steps_per_epoch(self, s):
         return self.shard_steps[s] // self.epochs
 
@@ -614,42 +623,15 @@ class TrainJob:
         t1 = self.ticks if n_ticks is None else min(self.ticks, self.done + int(n_ticks))
         while t1 > self.done:
             t_next = t1
-            if self._chunks:
-                # the launches of tick t read the permutation of the epoch AFTER the one a shard is in (the batch tags are
-                # prepared one epoch ahead): wait for the chunk that holds it, and launch only up to where the next one is needed
+            if self._arrivals:
+                # the launches of tick t read the order of the epoch AFTER the one a shard is in (the batch tags are prepared one epoch
+                # ahead): wait for the chunks up to the one that holds it, and launch only up to where the next one is needed
                 min_steps = min(self.steps_per_epoch(s) for s in range(len(self.shards)))
-                need = self.done // min_steps + (2 if self.ahead else 1)  # newest epoch any shard can read at tick self.done
+                lead = 2 if self.ahead else 1
                 st = stream if stream is not None else torch.cuda.current_stream(self.device)
-                horizon = self.epochs
-                def wait(chunk):                                        # host: until the worker queued the upload; device: until it is done
-                    if HOST_TRACE is not None and not chunk[1].is_set():
-                        import time
-                        t0 = time.perf_counter()
-                        chunk[1].wait()
-                        self.chunk_wait_s = getattr(self, 'chunk_wait_s', 0.0) + time.perf_counter() - t0
-                    chunk[1].wait()
-                    if chunk[2][0] is None:
-                        raise nv.NativeError('the permutation worker failed before this chunk was uploaded')
-                    marks = getattr(self, 'wait_marks', None)
-                    if marks is None:
-                        st.wait_event(chunk[2][0])
-                    else:           # (measurement: how long the stream stood still for the chunk -- bench.py takes it out of the launches' time)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(st)
-                        st.wait_event(chunk[2][0])
-                        e1.record(st)
-                        marks.append((e0, e1))
-                for ch in self._chunks:
-                    while ch and ch[0][0] <= need and len(ch) > 1:      # chunks that end at or before `need`, then the one holding it
-                        wait(ch.pop(0))
-                    if ch:
-                        wait(ch[0])
-                        horizon = min(horizon, ch[0][0])                # epochs < horizon have arrived (after these waits)
-                        if len(ch) == 1 and ch[0][0] >= self.epochs:
-                            ch.pop(0)
-                self._chunks = [ch for ch in self._chunks if ch]
+                horizon = min(a.wait(st, self.done // min_steps + lead, self.wait_marks) for a in self._arrivals)
                 if horizon < self.epochs:
-                    t_next = min(t_next, max(self.done + 1, (horizon - (2 if self.ahead else 1)) * min_steps))
+                    t_next = min(t_next, max(self.done + 1, (horizon - lead) * min_steps))
             nv.check(nv.lib().ure_job_train(self._job, self.done, t_next, nv.stream_handle(stream)), 'ure_job_train')
             self.done = t_next
         return self.done
@@ -786,8 +768,9 @@ class TrainJob:
         """Device-made batch tags (rng.device_tags): did a workgroup of perm_tags_kernel give up on a shuffle?  It cannot -- and its tags
         then match no batch, so nothing trained on a wrong permutation -- but a job that trained on fewer rows must not pass silently.
         Reads one small flag array (synchronises): called by close() and by callers right after they read a job's results."""
-        from . import rng
-        rng.device_tags_check(self._perms or [])
+        seen = set()
+        for a in self._arrivals:
+            a.check(seen)
 
     def close(self):
         if self._job:
@@ -798,7 +781,7 @@ class TrainJob:
             finally:
                 # the device memory goes back now: tables, snapshots, batch tags and what made them
                 self._pool = self._snap_pool = self._small = None
-                self._perms = []
+                self._perms, self._arrivals = [], []
                 if isinstance(getattr(self, 'state', None), _States):
                     self.state._got.clear()
 

@@ -15,8 +15,6 @@ and isolated, and the RNG stream is consumed in the reference's order in both):
                         end-of-epoch snapshots (`param.epoch_logs`, default on while the
                         snapshots fit URE_SNAPSHOT_LIMIT_GB).
 """
-import os
-
 import numpy as np
 import torch
 from torch import nn
@@ -97,7 +95,7 @@ def prepare_owned(ids, owner, rank, train_dlist, n_user, n_item, k, epochs, on_d
             base = dict(start_state=starts[pos], n_user=n_user, n_item=n_item, k=k, epochs=epochs, with_total_test=True, seeds=seeds[pos])
             if owner[pos] == rank:
                 specs.append(dict(base, n_rows=len(loader.dataset), shuffle=loader.shuffle, device=engine._device(),
-                                  tags_batch=loader.batch_size if os.environ.get('URE_HOST_TAGS', '1') != '0' else 0,
+                                  tags_batch=rng.tags_batch_for(len(loader.dataset), loader.batch_size),
                                   chunk_epochs=chunk_epochs))
                 order.append(i)
         tasks = rng.start_inits(specs)
@@ -299,7 +297,7 @@ class Sisa(Scratch):
             engine.mark('job_created')
             job.run()
             self._rows_dev(mine[0])             # (the merge's row lists go up while the device works through the launches)
-            engine.mark(f'launched (waited {getattr(job, "chunk_wait_s", 0.0) * 1e3:.2f} ms for permutation chunks)')
+            engine.mark(f'launched (waited {job.chunk_wait_s * 1e3:.2f} ms for permutation chunks)')
             for i in mine:
                 rng.release(prepared[i][2])                 # uploaded: host buffers go back to the pool
 

@@ -12,6 +12,7 @@ be taken up front and the permutations expanded later (or on other threads).
 """
 import ctypes
 import threading
+import time
 
 import numpy as np
 import torch
@@ -393,26 +394,115 @@ SMALL = _HostPool(1 << 14)   # small descriptors on their way to the device (eng
 STAGING = _HostPool()        # layout staging (engine.build_shards): its own pool, so that a 23 MB request never takes a 36 MB permutation buffer
 
 
-def release(perms):
-    """Hand a permutation buffer from epoch_perms(pooled=True) back (after it was uploaded)."""
-    if torch.is_tensor(perms):
-        host = getattr(perms, '_ure_host', None)
-        if host is not None:                    # uploaded by a background worker: wait for the (last) copy
-            chunks = getattr(perms, '_ure_chunks', None)
-            if chunks is not None:
-                chunks[-1][1].wait()
-                if chunks[-1][2][0] is not None:
-                    chunks[-1][2][0].synchronize()
-            else:
-                perms._ure_event.synchronize()
-            shared = getattr(perms, '_ure_shared', None)
-            if shared is not None:
-                shared.drop()                   # (a view of a block the shards of a call share)
-            else:
-                POOL.give(host)
-            perms._ure_host = None
+class Chunk:
+    """The epochs before `end` of an order on its way to the device: `queued` is set once their upload or shuffle is queued, and `event`
+    then marks its end on the producer's stream (None: the producer failed first)."""
+
+    def __init__(self, end):
+        self.end, self.queued, self.event = int(end), threading.Event(), None
+
+    def put(self, event):
+        self.event = event
+        self.queued.set()
+
+
+class Arrival:
+    """Which epochs of an order (a request's epoch permutations or batch tags, on the device) can be read yet, and what must be given back
+    afterwards: its producer (epoch_perms_async, _DrawsTask, device_tags) hangs it on the tensor as `_ure_arrival`, engine.TrainJob takes
+    it.  It never references that tensor (a request's memory goes back by reference counts).  chunks: [Chunk], the last ending at the
+    order's epoch count; host: the pinned source (a view of the _SharedBlock `shared`, or a POOL buffer); flags: device words a device
+    shuffle sets if it gives up; keep: blocks its side stream works on; whole: uploaded in one piece, waited for before anything reads it."""
+
+    def __init__(self, chunks, host=None, shared=None, flags=(), keep=(), whole=False):
+        self.chunks, self.host, self.shared, self.flags, self.keep, self.whole = list(chunks), host, shared, flags, keep, whole
+        self.error, self.waited_s, self._at = None, 0.0, 0      # (_at: the first chunk this consumer has not waited past)
+
+    @staticmethod
+    def of(order):
+        return getattr(order, '_ure_arrival', None)
+
+    def wait(self, stream, epoch, marks=None):
+        """Make `stream` wait for the chunks up to the one holding `epoch` -> the horizon: the epochs before it can be read behind these
+        waits (the holding chunk, unless it is the last, is waited for again by the next call).  marks: a list that gets an event pair
+        around each wait of the stream (how long it stood still: bench.py)."""
+        ch = self.chunks
+        while self._at < len(ch):
+            c = ch[self._at]
+            self._wait(c, stream, marks)
+            if c.end > epoch and c is not ch[-1]:
+                return c.end
+            self._at += 1
+        return ch[-1].end
+
+    def _wait(self, c, stream, marks):
+        if not c.queued.is_set():                       # (the host waits for the producer to queue the chunk: TrainJob.chunk_wait_s)
+            t0 = time.perf_counter()
+            c.queued.wait()
+            self.waited_s += time.perf_counter() - t0
+        if c.event is None:
+            from ._native import NativeError
+            raise NativeError('the permutation worker failed before this chunk was uploaded') from self.error
+        if marks is None:
+            stream.wait_event(c.event)
         else:
-            POOL.give(perms)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            stream.wait_event(c.event)
+            e1.record(stream)
+            marks.append((e0, e1))
+
+    def fail(self, exc):
+        """The producer failed: the exception is kept, no consumer is left waiting (a chunk never queued raises in wait())."""
+        self.error = exc
+        for c in self.chunks:
+            c.queued.set()
+
+    def release(self):
+        """Give the host source back once the last copy that reads it is done."""
+        if self.host is not None:
+            last = self.chunks[-1]
+            last.queued.wait()
+            if last.event is not None:
+                last.event.synchronize()
+            if self.shared is not None:
+                self.shared.drop()
+            else:
+                POOL.give(self.host)
+            self.host = self.shared = None
+
+    def check(self, seen=None):
+        """After the order's device work is done: did a workgroup of perm_tags_kernel give up, did the resolve pass of perm_chain.hip meet a
+        link it cannot follow?  Neither can happen -- and their tags match no batch, so nothing trained on them --, but tags that were not
+        made must not go unnoticed.  seen: data pointers of flag words read already (a call's orders share theirs: read once)."""
+        seen = set() if seen is None else seen
+        for f in self.flags:
+            if f.data_ptr() not in seen:
+                seen.add(f.data_ptr())
+                if bool(f.ne(0).any()):
+                    from ._native import NativeError
+                    raise NativeError('device shuffle: a permutation was given up (URE_DEVICE_TAGS=0 takes the host path)')
+
+
+def release(perms):
+    """Hand an order back after it was uploaded: its Arrival's host source, or a POOL buffer from epoch_perms(pooled=True)."""
+    a = Arrival.of(perms)
+    if a is not None:
+        a.release()
+    elif torch.is_tensor(perms):
+        POOL.give(perms)
+
+
+RANDPERM_HUGE_N = (2 ** 32 - 1) // 20     # ATen's randperm takes another algorithm from this n on: such orders are made by torch itself
+
+
+def tags_batch_for(n, batch, honour_env=True):
+    """`batch` when an order of n rows may travel as batch tags (int16 [epochs, n]: the step of the epoch in which every row trains; struct
+    ure_shard: file_tags), else 0: at most 65535 steps, not ATen's huge-n randperm, and not URE_HOST_TAGS=0 (honour_env=False: the caller
+    asks for tags itself, the limits alone apply)."""
+    import os
+    if honour_env and os.environ.get('URE_HOST_TAGS', '1') == '0':
+        return 0
+    return int(batch) if 0 < -(-n // max(int(batch), 1)) <= 65535 and n < RANDPERM_HUGE_N else 0
 
 
 def epoch_perms(seeds, n, threads=0, pooled=False):
@@ -424,7 +514,7 @@ def epoch_perms(seeds, n, threads=0, pooled=False):
     out = POOL.take((len(seeds), n), torch.int32) if pooled else torch.empty(len(seeds), n, dtype=torch.int32)
     if len(seeds) == 0 or n == 0:
         return out
-    if n >= (2 ** 32 - 1) // 20:          # ATen switches algorithm for huge n: use torch itself
+    if n >= RANDPERM_HUGE_N:
         for t, s in enumerate(seeds):
             out[t] = epoch_perm(s, n)
         return out
@@ -456,7 +546,7 @@ def epoch_tags_device(seeds, n, batch, device, bounds=None, method=None):
     chunks of epochs TrainJob.run waits for; None when the device path does not apply (URE_DEVICE_TAGS=0, no device, too many rows or steps)."""
     n, batch = int(n), int(batch)
     if (device is None or torch.device(device).type != 'cuda' or not device_tags_wanted() or n < 1 or n > DEVICE_TAGS_MAX_ROWS
-            or batch < 1 or -(-n // batch) > 65535 or len(seeds) == 0):
+            or tags_batch_for(n, batch, honour_env=False) < 1 or len(seeds) == 0):
         return None
     t = _task_of(dict(start_state=None, n_user=0, n_item=0, k=0, epochs=len(seeds), with_total_test=True, n_rows=n, shuffle=True,
                       device=torch.device(device), tags_batch=batch, seeds=list(seeds)), buffers=False)
@@ -470,23 +560,22 @@ def epoch_perms_async(seeds, n, threads=0, pooled=False, device=None, tags_batch
     are already drawn, so expanding them needs nothing from torch's generator and overlaps with the
     caller's next draws (the next shard's model init); the native call runs without the GIL.
     With `device` the worker also uploads the permutations on a side stream as soon as they exist;
-    result() is then the DEVICE tensor, carrying `_ure_event` (recorded after the copy: consumers
-    make their stream wait for it, engine.TrainJob does) and `_ure_host` (the pinned source,
-    handed back by release() once the copy is done)."""
+    result() is then the DEVICE tensor, whose Arrival (one chunk, whole=True) holds the copy's event --
+    engine.TrainJob makes its stream wait for it -- and the pinned source, handed back by release()."""
     global _EXPANDER
     if _EXPANDER is None:
         from concurrent.futures import ThreadPoolExecutor
         _EXPANDER = ThreadPoolExecutor(max_workers=1, thread_name_prefix='ure-perms')
     from . import _native as nv
     nv.lib()                                            # load the library on the calling thread
-    if len(seeds) == 0 or n == 0 or n >= (2 ** 32 - 1) // 20:
+    if len(seeds) == 0 or n == 0 or n >= RANDPERM_HUGE_N:
         out = epoch_perms(seeds, n, threads, pooled)    # nothing to expand, or ATen's huge-n algorithm (torch itself): done here
 
         class _Done:
             def result(self_inner):
                 return out
         return _Done()
-    tags_batch = int(tags_batch) if 0 < -(-n // max(int(tags_batch), 1)) <= 65535 else 0
+    tags_batch = tags_batch_for(n, tags_batch, honour_env=False)
     word = torch.int16 if tags_batch else torch.int32
     out = POOL.take((len(seeds), n), word) if pooled else torch.empty(len(seeds), n, dtype=word)
     sd = np.asarray(seeds, dtype=np.uint64).astype(np.int64)
@@ -517,7 +606,9 @@ def epoch_perms_async(seeds, n, threads=0, pooled=False, device=None, tags_batch
                 on_dev.copy_(out, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(st)
-        on_dev._ure_event, on_dev._ure_host = ev, out
+        whole = Chunk(len(sd))
+        whole.put(ev)
+        on_dev._ure_arrival = Arrival([whole], host=out, whole=True)
         return on_dev
     return _EXPANDER.submit(work)
 
@@ -549,7 +640,7 @@ class _DrawsTask:
         nv.lib()
         self.args = (start_state, n_user, n_item, k, epochs, with_total_test, n_rows, shuffle, int(threads or 0), want_perms)
         self.device = torch.device(device) if device is not None and torch.device(device).type == 'cuda' else None
-        self.host = self.on_dev = self.ready = self.stream = None
+        self.host = self.on_dev = self.ready = self.stream = self.arrival = None
         self.init_value = self.perms_value = None
         self.init_done, self.error = threading.Event(), None
         self.sharers = 1                            # inits of the same call running beside this one (start_inits)
@@ -562,12 +653,10 @@ class _DrawsTask:
         """-> (word type, epochs, rows) of the buffers chunks() fills and uploads, or None (no permutations, or not on a device)."""
         _, tags_batch = self._buffer_args
         _, _, _, _, epochs, _, n_rows, shuffle, _, want_perms = self.args
-        big = n_rows >= (2 ** 32 - 1) // 20
-        # tags_batch = B > 0: the permutations leave the host as BATCH TAGS (uint16 [epochs, n_rows]: the step of the epoch in which
-        # every interaction trains; struct ure_shard: file_tags; engine.TrainJob tells them from permutations by their dtype) -- half
-        # the bytes on PCIe, and no partition phases on the device.  Only on the chunked device path.
-        self.tags_batch = int(tags_batch) if (self.device is not None and 0 < -(-n_rows // max(int(tags_batch), 1)) <= 65535) else 0
-        if not (want_perms and shuffle and n_rows > 0 and epochs > 0 and not big):
+        # tags_batch = B > 0: the permutations leave the host as BATCH TAGS (tags_batch_for; engine.TrainJob tells them from permutations
+        # by their dtype) -- half the bytes on PCIe, and no partition phases on the device.  Only on the chunked device path.
+        self.tags_batch = tags_batch_for(n_rows, tags_batch, honour_env=False) if self.device is not None else 0
+        if not (want_perms and shuffle and n_rows > 0 and epochs > 0 and n_rows < RANDPERM_HUGE_N):
             return None
         return (torch.int16 if self.tags_batch else torch.int32), epochs, n_rows
 
@@ -578,14 +667,12 @@ class _DrawsTask:
         self.host, self.on_dev, self.ready = host, on_dev, ready
         if on_dev is None:
             return
-        on_dev._ure_host, on_dev._ure_shared = host, shared
         # chunks of at least chunk_epochs epochs and ~4 MB: every chunk costs its worker ~0.1 ms of Python (slices, a copy,
         # an event) under the GIL, and a request of 16 small shards had 112 of them competing with the calling thread
         chunk_epochs = max(int(chunk_epochs), -(-(4 << 20) // ((2 if self.tags_batch else 4) * n_rows)))
-        on_dev._ure_chunks = [(min(epochs, c0 + chunk_epochs), threading.Event(), [None]) for c0 in range(0, epochs, chunk_epochs)]
+        self.arrival = on_dev._ure_arrival = Arrival([Chunk(min(epochs, c0 + chunk_epochs)) for c0 in range(0, epochs, chunk_epochs)], host, shared)
         if self.error is not None:                  # the init failed before the buffers were there: never leave a consumer waiting
-            for _, flag, _ in on_dev._ure_chunks:
-                flag.set()
+            self.arrival.fail(self.error)
 
     def make_buffers(self):
         """The permutations' host and device buffers and events, on the CALLING thread (the pool and the allocator see the caller's
@@ -606,9 +693,8 @@ class _DrawsTask:
         """Never leave a consumer waiting: init() / the chunk flags are released, the exception is kept for result()."""
         self.error = exc
         self.init_done.set()
-        if self.on_dev is not None:
-            for _, flag, _ in self.on_dev._ure_chunks:
-                flag.set()
+        if self.arrival is not None:
+            self.arrival.fail(exc)
 
     def _upload_stream(self):
         """The side stream of the calling worker thread."""
@@ -689,9 +775,9 @@ class _DrawsTask:
         self.perms_value = on_dev
         first = True
         c0 = 0
-        for c1, flag, slot in on_dev._ure_chunks:
+        for chunk in self.arrival.chunks:
+            c1 = chunk.end
             if _TEST_CHUNK_DELAY_S:
-                import time
                 time.sleep(_TEST_CHUNK_DELAY_S)
             if self.tags_batch:
                 nv.check(L.ure_host_randperm_tags(sd_ptr + 8 * c0, c1 - c0, n_rows, self.tags_batch, host_ptr + row_bytes * c0, threads), 'ure_host_randperm_tags')
@@ -704,8 +790,7 @@ class _DrawsTask:
                 on_dev[c0:c1].copy_(host[c0:c1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(st)
-            slot[0] = ev
-            flag.set()
+            chunk.put(ev)
             mark(f'w: chunk to {c1}')
             c0 = c1
             yield
@@ -713,9 +798,8 @@ class _DrawsTask:
 
 class ShardDraws:
     """Handle of rng.shard_draws_async / draws_batch_async: init() blocks until the model init is there (on the device when a
-    device was given); perms() returns the permutations -- at once when they arrive in chunks (a device tensor whose
-    `_ure_chunks` = [(first epoch after the chunk, threading.Event set once the chunk's upload is queued, [its HIP event])]
-    tell a consumer when each part may be read: engine.TrainJob.run does), otherwise after the worker is done."""
+    device was given); perms() returns the permutations -- at once when they arrive in chunks (a device tensor whose Arrival
+    tells a consumer when each chunk of epochs may be read: engine.TrainJob.run asks it), otherwise after the worker is done."""
 
     def __init__(self, future, task):
         self._future, self._task = future, task
@@ -915,7 +999,7 @@ def device_tags(tasks, bounds=None, defer=False, method=None):
     ready.record(main)
     for side in sides:
         side.wait_event(ready)
-    chunks = [(c1, threading.Event(), [None]) for c1, *_ in launches]    # (the same for every shard: a launch holds chunk c of all of them)
+    chunks = [Chunk(c1) for c1, *_ in launches]         # (the same for every shard: a launch holds chunk c of all of them)
 
     def fire(c):
         c1, lo, hi, how, side = launches[c]
@@ -927,8 +1011,7 @@ def device_tags(tasks, bounds=None, defer=False, method=None):
             nv.check(L.ure_device_randperm_tags(ptr, hi - lo, n_max, block.data_ptr(), words, n_p, sides[side].cuda_stream), 'ure_device_randperm_tags')
         ev = torch.cuda.Event()
         ev.record(sides[side])
-        chunks[c][2][0] = ev
-        chunks[c][1].set()
+        chunks[c].put(ev)
     mark('tags: uploaded')
     if not defer:
         for c in range(len(launches)):
@@ -937,27 +1020,19 @@ def device_tags(tasks, bounds=None, defer=False, method=None):
     for t, (_, e, n_rows), o in zip(tasks, plans, offs):
         on_dev = dev_all[o:o + e * n_rows].view(e, n_rows)
         t.host, t.on_dev, t.ready = None, on_dev, ready
-        on_dev._ure_host, on_dev._ure_shared = None, None
-        on_dev._ure_keep = tuple(keep)                            # (alive as long as the tags are: the side streams work on them)
-        on_dev._ure_flags = flags
-        on_dev._ure_chunks = list(chunks)
-        on_dev._ure_methods = [how for *_, how, _ in launches]
+        t.arrival = on_dev._ure_arrival = Arrival(chunks, flags=flags, keep=keep)      # (keep: alive as long as the tags are)
+        on_dev._ure_methods = [how for *_, how, _ in launches]                         # (bench.py reads it: each chunk's shuffle)
         t.perms_value = on_dev
     return fire if defer else True
 
 
 def device_tags_check(perms):
-    """After the request's device work is done (the caller has synchronised): did a workgroup of perm_tags_kernel give up, did the resolve
-    pass of perm_chain.hip meet a link it cannot follow?  Neither can happen -- and their tags match no batch, so nothing trained on them --,
-    but tags that were not made must not go unnoticed.  perms: the tag tensors of the call's shards (shared flag words; read once)."""
+    """Arrival.check for the orders of a call (the request's device work is done)."""
     seen = set()
     for p in perms:
-        for f in getattr(p, '_ure_flags', None) or ():
-            if f.data_ptr() not in seen:
-                seen.add(f.data_ptr())
-                if bool(f.ne(0).any()):
-                    from ._native import NativeError
-                    raise NativeError('device shuffle: a permutation was given up (URE_DEVICE_TAGS=0 takes the host path)')
+        a = Arrival.of(p)
+        if a is not None:
+            a.check(seen)
 
 
 def _task_of(sp, buffers=True):
