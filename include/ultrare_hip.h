@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define URE_ABI_VERSION 9
+#define URE_ABI_VERSION 10
 #define URE_MAX_MODELS_PER_CALL 32
 #define URE_SCORE_PARTIALS 2048       /* length of ure_score's sse buffer */
 
@@ -435,6 +435,28 @@ int ure_eval_subset(const int32_t *sub_users, int32_t n_sub, const int32_t *sub_
 
 /* sisa.py:55-56,110-111: dst[rows[t]][:] = src[rows[t]][:]. */
 int ure_merge_rows(float *dst, const float *src, const int64_t *rows, int64_t n_rows, int d, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Full-catalogue top-k recommendation (ABI 10; csrc/mf_recommend.hip)
+ * ------------------------------------------------------------------------- */
+/* For each query row q: the k items with the highest ensemble score for user users[q], where
+ * score(u, i) is bit for bit what ure_score writes for the pair over the same n_models tables
+ * (chunks of URE_MAX_MODELS_PER_CALL with first / last): the per-model dot products in its order, added in
+ * model order from 0, divided by (float)n_models.  Order: score descending (NaN below -inf, -0.0 == +0.0),
+ * then item id ascending.  Exclusion (optional, both or neither, device): query row q excludes
+ * excl_items[excl_off[q] .. excl_off[q+1]) (excl_off [n_query + 1] int64; each row sorted, unique, in
+ * [0, n_item)).  A row with fewer than k eligible items is padded with item -1 and score NaN.
+ * scores / items (device) [n_query][k]; 1 <= k <= 128, d a power of two in [4, 256], any n_models >= 1.
+ * Table pointers are host arrays of device pointers, as in ure_score.  users (device) [n_query] MUST be in
+ * [0, n_user): the library does not check them.  scratch (device) holds ure_recommend_scratch bytes (0: may
+ * be NULL); it grows with n_query * k, never with n_query * n_item.  The model list goes to the device for
+ * the call (stream-ordered allocation, freed on `stream`).  Bitwise reproducible, and each row is the same
+ * however the users are batched.  ure_recommend_scratch returns -1 for arguments ure_recommend_topk rejects. */
+int64_t ure_recommend_scratch(int64_t n_query, int32_t n_item, int32_t k);
+int ure_recommend_topk(const float *const *U_tables, const float *const *V_tables, int32_t n_models,
+                       const int32_t *users, int64_t n_query, int32_t n_item, int32_t d,
+                       const int64_t *excl_off, const int32_t *excl_items, int32_t k,
+                       float *scores, int32_t *items, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * OT balanced grouping (utils.py:628-656)

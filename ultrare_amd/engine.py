@@ -1069,3 +1069,64 @@ def merge_rows(dst, src, rows, stream=None):
     nv.check(nv.lib().ure_merge_rows(nv.ptr(dst), nv.ptr(src), nv.ptr(rows), rows.numel(), dst.shape[1],
                                      nv.stream_handle(stream)), 'ure_merge_rows')
     return dst
+
+
+RECOMMEND_MAX_K = 128    # kRecMaxK of csrc/mf_recommend.hip
+
+
+def exclusion_rows(csr, users):
+    """The exclusion CSR of ure_recommend_topk for a batch of users: (off [n + 1] int64, items int32) with query row q holding
+    the column indices of `csr`'s row users[q] (a scipy CSR with user ids as rows, as read.readSparseMat returns), sorted and
+    unique.  Host only."""
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    indptr, indices = np.asarray(csr.indptr, dtype=np.int64), np.asarray(csr.indices)
+    if users.size and (users.min() < 0 or users.max() >= len(indptr) - 1):
+        raise ValueError(f'user ids outside the exclusion matrix\'s {len(indptr) - 1} rows')
+    rows = [np.unique(indices[indptr[u]:indptr[u + 1]]).astype(np.int32) for u in users]
+    off = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    return off, (np.concatenate(rows) if rows else np.zeros(0, dtype=np.int32)).astype(np.int32)
+
+
+def recommend(tables, d, users, k, excl=None, stream=None):
+    """Top-k items of every user of `users` over the whole catalogue (ure_recommend_topk): tables = [(U, V)] device tensors of
+    width d, the scores those of ure_score over the same list (the ensemble mean of baseTest), excl = (off, items) from
+    exclusion_rows or None.  Returns (scores [n, k] float32, items [n, k] int64) on the device; padding is (NaN, -1)."""
+    users = users.detach().cpu().numpy() if torch.is_tensor(users) else np.asarray(users)
+    users = users.astype(np.int64).reshape(-1)
+    if not tables:
+        raise ValueError('recommend needs at least one model')
+    n_user, n_item = int(tables[0][0].shape[0]), int(tables[0][1].shape[0])
+    if not 1 <= int(k) <= RECOMMEND_MAX_K:
+        raise ValueError(f'k = {k} outside [1, {RECOMMEND_MAX_K}]')
+    if users.size == 0:
+        raise ValueError('recommend needs at least one user')
+    if users.min() < 0 or users.max() >= n_user:
+        raise ValueError(f'user ids outside [0, {n_user})')
+    if excl is not None:
+        off, items = (np.asarray(excl[0], dtype=np.int64), np.asarray(excl[1], dtype=np.int32))
+        if off.shape != (len(users) + 1,) or off[0] != 0 or off[-1] != len(items) or np.any(np.diff(off) < 0):
+            raise ValueError('exclusion offsets do not describe one row per user')
+        if items.size and (items.min() < 0 or items.max() >= n_item):
+            raise ValueError(f'excluded items outside [0, {n_item})')
+    for U, V in tables:
+        if not (U.is_cuda and V.is_cuda):
+            raise nv.NativeError('recommend runs on the HIP device only (no CPU fallback)')
+        assert U.shape == (n_user, d) and V.shape == (n_item, d) and U.is_contiguous() and V.is_contiguous() and U.dtype == V.dtype == torch.float32
+    dev = tables[0][0].device
+    n, k = len(users), int(k)
+    uid = to_device_async(users.astype(np.int32), dev)
+    e_off = e_items = None
+    if excl is not None:
+        e_off = to_device_async(off, dev)
+        e_items = to_device_async(items if items.size else np.zeros(1, dtype=np.int32), dev)
+    L = nv.lib()
+    nbytes = int(L.ure_recommend_scratch(n, n_item, k))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+    items_out = torch.empty(n, k, dtype=torch.int32, device=dev)
+    Up = (ctypes.c_void_p * len(tables))(*[U.data_ptr() for U, _ in tables])
+    Vp = (ctypes.c_void_p * len(tables))(*[V.data_ptr() for _, V in tables])
+    nv.check(L.ure_recommend_topk(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(e_off), nv.ptr(e_items), k, nv.ptr(scores),
+                                  nv.ptr(items_out), nv.ptr(scratch), scratch.numel(), nv.stream_handle(stream)), 'ure_recommend_topk')
+    return scores, items_out.long()

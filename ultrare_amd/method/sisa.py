@@ -22,7 +22,7 @@ from torch import nn
 from .. import engine
 from ..read import as_loader
 from .scratch import PERM_THREADS, Scratch, prepare_shard, snapshot_limit
-from .utils import MF, baseTest, padded_tables, seed_all
+from .utils import MF, baseTest, padded_tables, recommend, seed_all
 
 
 
@@ -461,6 +461,11 @@ class Sisa(Scratch):
         return self.model_list
 
     # ------------------------------------------------------------------ unlearn
+    def recommend(self, users, top_k=10, exclude=None):
+        """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers
+        from the retrained shards.  Every rank of a parallel run holds the merged models and answers its own queries."""
+        return recommend(self.model_list, users, top_k, exclude)
+
     def unlearn(self, model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir):
         '''
         train_dlist:   list of dataloader[n_group]

@@ -4,6 +4,7 @@ the reference), backed by the HIP engine.
   seed_all     utils.py:21-25
   MF           utils.py:30-43    two embedding tables; forward = row-wise dot
   baseTest     utils.py:115-187  ensemble mean score, RMSE, HR@10, NDCG@10
+  recommend    (new)             top-k items over the whole catalogue from the same ensemble mean
   computeNDCG / computeDCG  utils.py:190-210
   ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD)
   saveObject / loadObject / timefn  utils.py:319-326, 616-626
@@ -104,6 +105,17 @@ def baseTest(dataloader, models, loss_fn=None, device=None, verbose=0, top_k=10)
     if verbose == 2:
         print(f'Test - RMSE: {rmse:>.4f}, NDCG: {ndcg:>.3f}, HR: {hr:>.3f}')
     return rmse, ndcg, hr
+
+
+def recommend(models, users, top_k=10, exclude=None):
+    """The top_k items of each user in `users` over the whole catalogue, by the score baseTest gives the pair (the mean of
+    `models`, bit for bit), ties by ascending item id.  exclude: a scipy CSR with user ids as rows (read.readSparseMat of the
+    training set) whose items are never returned.  Returns (scores [n, top_k], items [n, top_k] int64) on the device; a user
+    with fewer eligible items than top_k gets (NaN, -1) at the end.  The full model is recommend([model], ...)."""
+    tabs = [padded_tables(m) for m in models]
+    users = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
+    excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
+    return engine.recommend([(U, V) for U, V, _ in tabs], tabs[0][2], users, top_k, excl)
 
 
 def computeNDCG(r, top_k):

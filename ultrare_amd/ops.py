@@ -11,8 +11,11 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.ot_cost_mfma(X, C)                (same, |x|^2 - 2 x.c + |c|^2 on the matrix cores; cross-check only)
     torch.ops.ultrare.ot_centroids(X, label, k)         utils.py:648      cluster means, numpy's fp32 order
     torch.ops.ultrare.merge_rows(dst, src, rows)        sisa.py:55-56     dst[rows] = src[rows]  (in place)
+    torch.ops.ultrare.recommend_topk(Us, Vs, users, excl_off, excl_items, k)
+                                                        (new)             full-catalogue top-k of the ensemble mean
 """
 import ctypes
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -94,3 +97,17 @@ def merge_rows(dst: torch.Tensor, src: torch.Tensor, rows: torch.Tensor) -> None
     assert dst.is_contiguous() and src.is_contiguous() and dst.shape == src.shape
     rows = rows.to(torch.int64).contiguous()
     nv.check(nv.lib().ure_merge_rows(nv.ptr(dst), nv.ptr(src), nv.ptr(rows), rows.numel(), dst.shape[1], nv.stream_handle()), 'ure_merge_rows')
+
+
+@torch.library.custom_op('ultrare::recommend_topk', mutates_args=())
+def recommend_topk(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.Tensor, excl_off: Optional[torch.Tensor],
+                   excl_items: Optional[torch.Tensor], k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(*Us, *Vs, users, *[t for t in (excl_off, excl_items) if t is not None])
+    assert len(Us) == len(Vs) and (excl_off is None) == (excl_items is None)
+    excl = None if excl_off is None else (excl_off.cpu().numpy(), excl_items.cpu().numpy())
+    return engine.recommend(list(zip(Us, Vs)), Us[0].shape[1], users, k, excl)
+
+
+@recommend_topk.register_fake
+def _(Us, Vs, users, excl_off, excl_items, k):
+    return Us[0].new_empty(users.numel(), k), Us[0].new_empty(users.numel(), k, dtype=torch.int64)
