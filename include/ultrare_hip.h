@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define URE_ABI_VERSION 10
+#define URE_ABI_VERSION 11
 #define URE_MAX_MODELS_PER_CALL 32
 #define URE_SCORE_PARTIALS 2048       /* length of ure_score's sse buffer */
 
@@ -457,6 +457,32 @@ int ure_recommend_topk(const float *const *U_tables, const float *const *V_table
                        const int32_t *users, int64_t n_query, int32_t n_item, int32_t d,
                        const int64_t *excl_off, const int32_t *excl_items, int32_t k,
                        float *scores, int32_t *items, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Exact full-catalogue ranks of (user, item) pairs (ABI 11; csrc/mf_rank.hip)
+ * ------------------------------------------------------------------------- */
+/* For each query row q (user users[q]) and each target t of tgt_items[tgt_off[q] .. tgt_off[q+1]): ranks[t] = the
+ * number of items j in [0, n_item), not in row q's exclusion list, whose key is greater than the target's.  The key is
+ * ure_recommend_topk's: score descending (NaN below -inf, -0.0 == +0.0), then item id ascending, with score(u, i) bit
+ * for bit what ure_score writes for the pair over the same n_models tables (any n_models >= 1).  Keys are unique, so a
+ * target never counts itself, equal targets of a row get equal ranks, and a target of rank r < k is item r of the row
+ * ure_recommend_topk returns under the same exclusion.  A target in its own row's exclusion list gets -1.
+ * tgt_off (device) [n_query + 1] int64, tgt_off[0] = 0, non-decreasing; tgt_items (device) [n_targets] in [0, n_item),
+ * any order, duplicates allowed, rows may be empty; ranks (device) [n_targets] int32, in input order.  Exclusion
+ * (optional, both or neither, device): as in ure_recommend_topk (excl_off [n_query + 1]; rows sorted, unique, in
+ * [0, n_item)).  d a power of two in [4, 256].  Table pointers are host arrays of device pointers, as in ure_score.
+ * users, the offsets and the items MUST be in range: the library does not check them.  scratch (device) holds
+ * ure_rank_pairs_scratch(n_query, n_targets, n_item, d) bytes with n_targets = tgt_off[n_query]; it grows with
+ * n_targets, never with n_query * n_item.  The library reads n_targets on the device only: a call whose scratch is
+ * short of it computes nothing.  The model list goes to the device for the call (stream-ordered allocation, freed on
+ * `stream`).  Bitwise reproducible, and each row is the same however the users are batched.
+ * ure_rank_pairs_scratch returns -1 for arguments ure_rank_pairs rejects. */
+int64_t ure_rank_pairs_scratch(int64_t n_query, int64_t n_targets, int32_t n_item, int32_t d);
+int ure_rank_pairs(const float *const *U_tables, const float *const *V_tables, int32_t n_models,
+                   const int32_t *users, int64_t n_query, int32_t n_item, int32_t d,
+                   const int64_t *tgt_off, const int32_t *tgt_items,
+                   const int64_t *excl_off, const int32_t *excl_items,
+                   int32_t *ranks, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * OT balanced grouping (utils.py:628-656)

@@ -11,7 +11,7 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'libultrare_hip.so')
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_MODELS_PER_CALL = 32
 
 _vp = ctypes.c_void_p
@@ -110,6 +110,9 @@ _PROTOTYPES = {
     'ure_recommend_scratch': (_i64, [_i64, _i32, _i32]),
     'ure_recommend_topk': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp,
                                           _vp, _i64, _vp]),
+    'ure_rank_pairs_scratch': (_i64, [_i64, _i64, _i32, _i32]),
+    'ure_rank_pairs': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _i64, _vp]),
     'ure_ot_cost': (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     'ure_ot_cost_mfma': (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     'ure_ot_centroids': (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),

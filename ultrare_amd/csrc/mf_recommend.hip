@@ -1,9 +1,6 @@
 // mf_recommend.hip -- full-catalogue top-k recommendation from an ensemble for gfx950.
 //
-// score(u, i) = (sum over models, in list order, of U_m[u] . V_m[i]) / S with every dot product in
-// score_kernel's (mf_eval.hip) order: partial j = a.x*b.x + three fmaf over columns 4j .. 4j+3, the d/4
-// partials added by group_sum's balanced tree over contiguous halves, the model results added into one
-// float starting from 0.  The scores equal what ure_score writes for the same pairs, bit for bit.
+// The scores and the key order are those of rec_score.h (bit for bit ure_score's ensemble mean).
 //
 // One fused pass scores and selects; the score matrix never reaches HBM.  A workgroup owns a tile of
 // QT = 4 * QW users (QW per wave) and streams the item tiles of its split: per model, the users' U rows
@@ -15,13 +12,10 @@
 // depend on the order in which candidates arrive.  With several item splits per user tile each split
 // writes its own sorted top-k; rec_merge_splits_kernel merges them split by split.
 //
-// Key order: score descending (NaN below -inf, -0.0 == +0.0), then item id ascending.  The 64-bit key
-// (order_bits(score) << 32 | ~item) is larger for the better item and 0 only for padding (item -1, NaN).
-#include "ure_internal.h"
+#include "rec_score.h"
 
 namespace ure {
 
-constexpr int kRecItems = 64;        // items per tile: one per lane, shared by the workgroup's 4 waves
 constexpr int kRecCand = 64;         // candidate slots per user
 constexpr int kRecMaxK = 128;
 constexpr int kRecTargetBlocks = 1024;   // splits fill about 4 workgroups per CU at small n_query
@@ -43,49 +37,21 @@ __global__ void rec_tables_kernel(RecTables T, int n, int m0, int S, const float
     }
 }
 
-__device__ __forceinline__ uint32_t order_bits(float s)
+int rec_upload_tables(const float *const *U_tables, const float *const *V_tables, int n_models, hipStream_t st, const float ***out)
 {
-    if (s != s) return 0u;                                  // NaN below every number
-    uint32_t b = __float_as_uint(s);
-    if ((b << 1) == 0u) b = 0u;                             // -0.0 == +0.0
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);      // -inf -> 0x007FFFFF > 0
-}
-
-__device__ __forceinline__ uint64_t rec_key(float s, int item)
-{
-    return ((uint64_t)order_bits(s) << 32) | (uint64_t)(~(uint32_t)item);
-}
-
-// Orders this wave's LDS accesses before and after (LDS operations of one wave complete in issue order).
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// out[t] = the tree sum over partials [J0, J0 + N) of user row t (u + t * D) against the item row v.
-template <int D, int QW, int J0, int N>
-__device__ __forceinline__ void rec_dot(float (&out)[QW], const float *v, const float *u)
-{
-    if constexpr (N == 1) {
-        const float4 b = *reinterpret_cast<const float4 *>(v + J0 * 4);
-#pragma unroll
-        for (int t = 0; t < QW; ++t) {
-            const float4 a = *reinterpret_cast<const float4 *>(u + t * D + J0 * 4);
-            float p = a.x * b.x;
-            p = fmaf(a.y, b.y, p);
-            p = fmaf(a.z, b.z, p);
-            p = fmaf(a.w, b.w, p);
-            out[t] = p;
+    const float **tab = nullptr;
+    URE_HIP(hipMallocAsync(reinterpret_cast<void **>(&tab), sizeof(float *) * 2 * (size_t)n_models, st));
+    for (int m0 = 0; m0 < n_models; m0 += URE_MAX_MODELS_PER_CALL) {
+        RecTables T;
+        const int c = std::min(n_models - m0, URE_MAX_MODELS_PER_CALL);
+        for (int j = 0; j < c; ++j) {
+            T.U[j] = U_tables[m0 + j];
+            T.V[j] = V_tables[m0 + j];
         }
-    } else {
-        float r[QW];
-        rec_dot<D, QW, J0, N / 2>(out, v, u);
-        rec_dot<D, QW, J0 + N / 2, N / 2>(r, v, u);
-#pragma unroll
-        for (int t = 0; t < QW; ++t) out[t] += r[t];
+        hipLaunchKernelGGL(rec_tables_kernel, dim3(1), dim3(kWave), 0, st, T, c, m0, n_models, tab);
     }
+    *out = tab;
+    return 0;
 }
 
 // Merges nc candidates (ck / cs) into the sorted list (tk / ts, k entries, padding keys 0 at the end) by
@@ -170,7 +136,6 @@ __global__ __launch_bounds__(kBlock) void rec_topk_kernel(RecArgs A)
     const int split = blockIdx.y;
     const int ib = (int)std::min<int64_t>((int64_t)split * A.span, A.n_item);
     const int ie = (int)std::min<int64_t>((int64_t)ib + A.span, A.n_item);
-    const float n_s = (float)A.n_models;
 
     if (tid < QT) uid[tid] = q0 + tid < A.n_query ? A.users[q0 + tid] : 0;
     for (int e = tid; e < QT * k; e += kBlock) {
@@ -184,30 +149,10 @@ __global__ __launch_bounds__(kBlock) void rec_topk_kernel(RecArgs A)
     __syncthreads();
 
     for (int i0 = ib; i0 < ie; i0 += kRecItems) {
-        float acc[QW];
+        float sv[QW];
+        rec_score_tile<LPR, QW>(sv, A.tab, A.n_models, Us, Vs, uid, q0, A.n_query, i0, ie);
 #pragma unroll
-        for (int t = 0; t < QW; ++t) acc[t] = 0.f;
-        for (int m = 0; m < A.n_models; ++m) {
-            const float *Um = A.tab[m], *Vm = A.tab[A.n_models + m];
-            __syncthreads();
-            for (int f = tid; f < QT * LPR; f += kBlock) {
-                const int r = f / LPR, c = f % LPR;
-                const float4 x = q0 + r < A.n_query ? ldg_f4(Um + (size_t)uid[r] * D + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4 *>(Us + r * D + c * 4) = x;
-            }
-            for (int f = tid; f < kRecItems * LPR; f += kBlock) {
-                const int r = f / LPR, c = f % LPR;
-                const float4 x = i0 + r < ie ? ldg_f4(Vm + (size_t)(i0 + r) * D + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4 *>(Vs + r * VS + c * 4) = x;
-            }
-            __syncthreads();
-            float p[QW];
-            rec_dot<D, QW, 0, LPR>(p, Vs + lane * VS, Us + w * QW * D);
-#pragma unroll
-            for (int t = 0; t < QW; ++t) acc[t] += p[t];
-        }
-#pragma unroll
-        for (int t = 0; t < QW; ++t) sc[(w * QW + t) * kRecItems + lane] = acc[t] / n_s;   // score_kernel: acc / (float)n_total
+        for (int t = 0; t < QW; ++t) sc[(w * QW + t) * kRecItems + lane] = sv[t];
         wave_lds_sync();
 
         // selection: wave w keeps the lists of its QW users (one user at a time: the state is wave-uniform, in LDS)
@@ -430,16 +375,7 @@ int ure_recommend_topk(const float *const *U_tables, const float *const *V_table
 
     // the model table lives on the device for the call: any number of models in one pass
     const float **tab = nullptr;
-    URE_HIP(hipMallocAsync(reinterpret_cast<void **>(&tab), sizeof(float *) * 2 * (size_t)n_models, st));
-    for (int m0 = 0; m0 < n_models; m0 += URE_MAX_MODELS_PER_CALL) {
-        RecTables T;
-        const int c = std::min(n_models - m0, URE_MAX_MODELS_PER_CALL);
-        for (int j = 0; j < c; ++j) {
-            T.U[j] = U_tables[m0 + j];
-            T.V[j] = V_tables[m0 + j];
-        }
-        hipLaunchKernelGGL(rec_tables_kernel, dim3(1), dim3(kWave), 0, st, T, c, m0, n_models, tab);
-    }
+    if (int rc = rec_upload_tables(U_tables, V_tables, n_models, st, &tab)) return rc;
     A.tab = tab;
     int rc = 0;
     switch (d / 4) {

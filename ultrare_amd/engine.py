@@ -1130,3 +1130,59 @@ def recommend(tables, d, users, k, excl=None, stream=None):
     nv.check(L.ure_recommend_topk(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(e_off), nv.ptr(e_items), k, nv.ptr(scores),
                                   nv.ptr(items_out), nv.ptr(scratch), scratch.numel(), nv.stream_handle(stream)), 'ure_recommend_topk')
     return scores, items_out.long()
+
+
+def _check_rows(off, items, n_rows, n_item, what):
+    """(off int64 [n_rows + 1], items int32) of a per-query CSR, or ValueError: offsets from 0 to len(items), non-decreasing,
+    items in [0, n_item)."""
+    off, items = np.asarray(off, dtype=np.int64).reshape(-1), np.asarray(items).reshape(-1)
+    if off.shape != (n_rows + 1,) or off[0] != 0 or off[-1] != len(items) or np.any(np.diff(off) < 0):
+        raise ValueError(f'{what} offsets do not describe one row per user')
+    if items.size and (items.min() < 0 or items.max() >= n_item):
+        raise ValueError(f'{what} items outside [0, {n_item})')
+    return off, items.astype(np.int32)
+
+
+def rank_pairs(tables, d, users, targets, excl=None, stream=None):
+    """Exact full-catalogue rank of every (user, target item) pair (ure_rank_pairs): tables = [(U, V)] device tensors of width d,
+    targets = (off [n + 1], items) with query row q's targets items[off[q]:off[q + 1]] (any order, duplicates, empty rows),
+    excl = (off, items) from exclusion_rows or None.  rank = the number of non-excluded items whose (score, id) key beats the
+    target's -- the position recommend would give it -- or -1 for an excluded target.  Returns ranks [len(items)] int32 on the
+    device, in input order."""
+    users = users.detach().cpu().numpy() if torch.is_tensor(users) else np.asarray(users)
+    users = users.astype(np.int64).reshape(-1)
+    if not tables:
+        raise ValueError('rank_pairs needs at least one model')
+    n_user, n_item = int(tables[0][0].shape[0]), int(tables[0][1].shape[0])
+    if users.size == 0:
+        raise ValueError('rank_pairs needs at least one user')
+    if users.min() < 0 or users.max() >= n_user:
+        raise ValueError(f'user ids outside [0, {n_user})')
+    t_off, t_items = _check_rows(*(t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in targets), len(users), n_item, 'target')
+    if excl is not None:
+        e_off_h, e_items_h = _check_rows(*(t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in excl), len(users), n_item, 'exclusion')
+    for U, V in tables:
+        if not (U.is_cuda and V.is_cuda):
+            raise nv.NativeError('rank_pairs runs on the HIP device only (no CPU fallback)')
+        assert U.shape == (n_user, d) and V.shape == (n_item, d) and U.is_contiguous() and V.is_contiguous() and U.dtype == V.dtype == torch.float32
+    dev = tables[0][0].device
+    n, n_t = len(users), len(t_items)
+    ranks = torch.empty(max(n_t, 1), dtype=torch.int32, device=dev)
+    if n_t == 0:
+        return ranks[:0]
+    uid = to_device_async(users.astype(np.int32), dev)
+    d_off, d_items = to_device_async(t_off, dev), to_device_async(t_items, dev)
+    e_off = e_items = None
+    if excl is not None:
+        e_off = to_device_async(e_off_h, dev)
+        e_items = to_device_async(e_items_h if e_items_h.size else np.zeros(1, dtype=np.int32), dev)
+    L = nv.lib()
+    nbytes = int(L.ure_rank_pairs_scratch(n, n_t, n_item, d))
+    if nbytes < 0:
+        raise ValueError(f'ure_rank_pairs_scratch refused n_query = {n}, n_targets = {n_t}, n_item = {n_item}, d = {d}')
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    Up = (ctypes.c_void_p * len(tables))(*[U.data_ptr() for U, _ in tables])
+    Vp = (ctypes.c_void_p * len(tables))(*[V.data_ptr() for _, V in tables])
+    nv.check(L.ure_rank_pairs(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(d_off), nv.ptr(d_items), nv.ptr(e_off), nv.ptr(e_items),
+                              nv.ptr(ranks), nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_rank_pairs')
+    return ranks

@@ -22,7 +22,7 @@ from torch import nn
 from .. import engine
 from ..read import as_loader
 from .scratch import PERM_THREADS, Scratch, prepare_shard, snapshot_limit
-from .utils import MF, baseTest, padded_tables, recommend, seed_all
+from .utils import MF, baseTest, padded_tables, rank_eval, recommend, seed_all
 
 
 
@@ -465,6 +465,12 @@ class Sisa(Scratch):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers
         from the retrained shards.  Every rank of a parallel run holds the merged models and answers its own queries."""
         return recommend(self.model_list, users, top_k, exclude)
+
+    def rank_eval(self, test_data, exclude=None, ks=(10, 20)):
+        """Full-ranking HR@K / Recall@K / NDCG@K / MRR of the current ensemble on a test loader (utils.rank_eval over
+        self.model_list): after unlearn it evaluates the retrained shards.  Every rank of a parallel run holds the merged models
+        and answers for itself."""
+        return rank_eval(self.model_list, test_data, exclude, ks)
 
     def unlearn(self, model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir):
         '''

@@ -5,6 +5,7 @@ the reference), backed by the HIP engine.
   MF           utils.py:30-43    two embedding tables; forward = row-wise dot
   baseTest     utils.py:115-187  ensemble mean score, RMSE, HR@10, NDCG@10
   recommend    (new)             top-k items over the whole catalogue from the same ensemble mean
+  rank_eval    (new)             full-ranking HR@K / Recall@K / NDCG@K / MRR of the test pairs (rank_metrics: the reduction)
   computeNDCG / computeDCG  utils.py:190-210
   ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD)
   saveObject / loadObject / timefn  utils.py:319-326, 616-626
@@ -116,6 +117,69 @@ def recommend(models, users, top_k=10, exclude=None):
     users = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
     excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
     return engine.recommend([(U, V) for U, V, _ in tabs], tabs[0][2], users, top_k, excl)
+
+
+def relevant_pairs(test_data, n_item):
+    """The distinct (user, item) pairs of a test loader (accepted as baseTest accepts one), grouped by user:
+    (users [n] int64 ascending, off [n + 1] int64, items int32 ascending within each user)."""
+    ds = as_loader(test_data).dataset
+    u, i = np.asarray(ds.users, dtype=np.int64), np.asarray(ds.items, dtype=np.int64)
+    if i.size and (i.min() < 0 or i.max() >= n_item):
+        raise ValueError(f'test items outside [0, {n_item})')
+    pair = np.unique(u * n_item + i)
+    pu, pi = pair // n_item, pair % n_item
+    users, counts = np.unique(pu, return_counts=True)
+    off = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum(counts, out=off[1:])
+    return users, off, pi.astype(np.int32)
+
+
+def rank_metrics(off, ranks, ks=(10, 20)):
+    """Full-ranking metrics from the ranks of each user's relevant items (user q's at ranks[off[q]:off[q + 1]], -1 for an
+    excluded one, which does not count).  Per user over its R_u counted ranks, users with none skipped:
+      HR@K = [min rank < K]    Recall@K = #{rank < K} / |R_u|    MRR = 1 / (1 + min rank)
+      NDCG@K = sum over rank < K of 1 / log2(rank + 2), over the ideal sum of 1 / log2(i + 2) for i < min(|R_u|, K)
+    Returns {'hr@K', 'recall@K', 'ndcg@K' for each K, 'mrr', 'n_users', 'n_pairs'}: float64 means over the counted users,
+    n_pairs the counted ranks."""
+    off = np.asarray(off, dtype=np.int64)
+    ranks = np.asarray(ranks.cpu() if torch.is_tensor(ranks) else ranks, dtype=np.int64).reshape(-1)
+    n = len(off) - 1
+    row = np.repeat(np.arange(n), np.diff(off))
+    ok = ranks >= 0
+    row, r = row[ok], ranks[ok]
+    R = np.bincount(row, minlength=n)
+    keep = R > 0
+    best = np.full(n, np.iinfo(np.int64).max)
+    np.minimum.at(best, row, r)
+    best = best[keep].astype(np.float64)
+    out = {}
+    for K in ks:
+        K = int(K)
+        hit = r < K
+        n_hit = np.bincount(row[hit], minlength=n)[keep]
+        dcg = np.bincount(row[hit], weights=1.0 / np.log2(r[hit] + 2.0), minlength=n)[keep]
+        ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(K) + 2.0))])[np.minimum(R[keep], K)]
+        out[f'hr@{K}'] = float(np.mean(best < K)) if keep.any() else 0.0
+        out[f'recall@{K}'] = float(np.mean(n_hit / R[keep])) if keep.any() else 0.0
+        out[f'ndcg@{K}'] = float(np.mean(dcg / ideal)) if keep.any() else 0.0
+    out['mrr'] = float(np.mean(1.0 / (1.0 + best))) if keep.any() else 0.0
+    out['n_users'] = int(keep.sum())
+    out['n_pairs'] = int(len(r))
+    return out
+
+
+def rank_eval(models, test_data, exclude=None, ks=(10, 20)):
+    """Full-ranking evaluation of the ensemble mean of `models` (the score baseTest gives a pair, bit for bit): every distinct
+    (user, item) pair of `test_data` (a test loader, as baseTest takes) is ranked among ALL items the user has not trained on
+    -- exclude: a scipy CSR with user ids as rows, read.readSparseMat of the training set -- by (score, id) as recommend orders
+    them, and HR@K, Recall@K, NDCG@K and MRR are taken from those ranks (rank_metrics; every test pair is relevant, no rating
+    threshold).  These are NOT baseTest's HR@10 / NDCG@10, which rank a user's test items only against each other.  A test pair
+    that is also in `exclude` does not count.  Returns the dict of rank_metrics."""
+    tabs = [padded_tables(m) for m in models]
+    users, off, items = relevant_pairs(test_data, int(tabs[0][1].shape[0]))
+    excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
+    ranks = engine.rank_pairs([(U, V) for U, V, _ in tabs], tabs[0][2], users, (off, items), excl)
+    return rank_metrics(off, ranks, ks)
 
 
 def computeNDCG(r, top_k):

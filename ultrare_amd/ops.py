@@ -13,6 +13,8 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.merge_rows(dst, src, rows)        sisa.py:55-56     dst[rows] = src[rows]  (in place)
     torch.ops.ultrare.recommend_topk(Us, Vs, users, excl_off, excl_items, k)
                                                         (new)             full-catalogue top-k of the ensemble mean
+    torch.ops.ultrare.rank_pairs(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items)
+                                                        (new)             exact full-catalogue rank of each target pair
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -111,3 +113,17 @@ def recommend_topk(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.
 @recommend_topk.register_fake
 def _(Us, Vs, users, excl_off, excl_items, k):
     return Us[0].new_empty(users.numel(), k), Us[0].new_empty(users.numel(), k, dtype=torch.int64)
+
+
+@torch.library.custom_op('ultrare::rank_pairs', mutates_args=())
+def rank_pairs(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.Tensor, tgt_off: torch.Tensor, tgt_items: torch.Tensor,
+               excl_off: Optional[torch.Tensor], excl_items: Optional[torch.Tensor]) -> torch.Tensor:
+    _dev(*Us, *Vs, users, tgt_off, tgt_items, *[t for t in (excl_off, excl_items) if t is not None])
+    assert len(Us) == len(Vs) and (excl_off is None) == (excl_items is None)
+    excl = None if excl_off is None else (excl_off.cpu().numpy(), excl_items.cpu().numpy())
+    return engine.rank_pairs(list(zip(Us, Vs)), Us[0].shape[1], users, (tgt_off.cpu().numpy(), tgt_items.cpu().numpy()), excl)
+
+
+@rank_pairs.register_fake
+def _(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items):
+    return Us[0].new_empty(tgt_items.numel(), dtype=torch.int32)
