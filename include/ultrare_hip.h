@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define URE_ABI_VERSION 11
+#define URE_ABI_VERSION 12
 #define URE_MAX_MODELS_PER_CALL 32
 #define URE_SCORE_PARTIALS 2048       /* length of ure_score's sse buffer */
 
@@ -483,6 +483,46 @@ int ure_rank_pairs(const float *const *U_tables, const float *const *V_tables, i
                    const int64_t *tgt_off, const int32_t *tgt_items,
                    const int64_t *excl_off, const int32_t *excl_items,
                    int32_t *ranks, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Reductions of a user-by-user distance matrix (ABI 12; csrc/pair_dist.hip): the k-medoids, label
+ * propagation and k-nearest-neighbour comparison clusterers of utils.py:422-611, never materialising D
+ * ------------------------------------------------------------------------- */
+/* Source of D (metric):
+ *   URE_DIST_GIVEN      src = G, a row-major float32 n x n array (device), D[u, v] = G[u * n + v]; d is ignored, n <= 1518500249.
+ *   URE_DIST_EUCLIDEAN  src = X [n x d] float32 (device), any d >= 1: D[u, v] = sqrt(sum_j (x_uj - x_vj)^2), the difference form.
+ *   URE_DIST_COSINE     1 - x_u.x_v / (|x_u| |x_v|) clamped to [0, 2]; 1 when either row is zero; D[u, u] = 0.
+ *   URE_DIST_MANHATTAN  sum_j |x_uj - x_vj|.
+ * A streamed D[u, v] sums over j = 0 .. d - 1 in order in float32 (fmaf per term; |x|^2 the same way), so it is a pure
+ * function of rows u and v, D[u, v] == D[v, u] bit for bit and D[u, u] == 0.  Every entry below is bitwise reproducible
+ * (no float atomics) and independent of the grid and of how query rows are batched.  Index arguments (query, cols,
+ * label) MUST be in range: the library does not check them.  All run on `stream`. */
+#define URE_DIST_GIVEN 0
+#define URE_DIST_EUCLIDEAN 1
+#define URE_DIST_COSINE 2
+#define URE_DIST_MANHATTAN 3
+/* kNN (utils.py:422-455): for each query row q (row query[q] of D, or q when query == NULL; n_query >= 1), the n_nb
+ * (1 <= n_nb <= min(n, 128)) smallest keys (D[row, v], v) over all columns v, ascending -- exact ties by ascending v, the
+ * row itself included --: dist [n_query x n_nb] float32, idx [n_query x n_nb] int32.  The columns are split into `splits`
+ * ranges (0: chosen from n_query) whose lists a second kernel merges; the result does not depend on it.  scratch (device)
+ * holds ure_pair_knn_scratch(n_query, n, n_nb, splits) bytes (n_query * n_nb * 8 per effective split, never n * n); the
+ * scratch function returns -1 for arguments ure_pair_knn rejects. */
+int64_t ure_pair_knn_scratch(int64_t n_query, int64_t n, int32_t n_nb, int32_t splits);
+int ure_pair_knn(const float *src, int64_t n, int32_t d, int32_t metric, const int32_t *query, int64_t n_query, int32_t n_nb,
+                 int32_t splits, float *dist, int32_t *idx, void *scratch, int64_t scratch_bytes, void *stream);
+/* Row sums R[u] = sum_v D[u, v] [n] float32, in np.sum(D, axis=1)'s float32 order (pairwise sums of buffers of 8192
+ * columns, added in order), so bit for bit np.sum on the given path. */
+int ure_pair_rowsum(const float *src, int64_t n, int32_t d, int32_t metric, float *R, void *stream);
+/* Columns out[u * m + j] = D[u, cols[j]] [n x m] float32 (cols device int32, m >= 1): the medoid distances. */
+int ure_pair_cols(const float *src, int64_t n, int32_t d, int32_t metric, const int32_t *cols, int32_t m, float *out, void *stream);
+/* Label-grouped kernel sums (utils.py:471-475): W[u, g] = sum over i with label[i] == g of exp(-D[i, u]) [n x k] float64,
+ * each term float32 expf, summed in float64 over i = 0, 1, ... in order.  label (device) [n] int32 in [0, k); 1 <= k <= 128. */
+int ure_pair_label_expsum(const float *src, int64_t n, int32_t d, int32_t metric, const int32_t *label, int32_t k, double *W, void *stream);
+/* utils.py:484-497 (host): balanced assignment by descending weight.  The (user, group) pairs of w [n x k] float64 are taken
+ * in descending weight, exact ties by descending flat index u * k + g (sortArr(w, 'des') reverses an ascending argsort); each
+ * user gets the first group with room left, at most `capacity` users per group (capacity * k >= n).  *inertia (optional) =
+ * np.sum(w[arange(n), label]), numpy's float64 pairwise sum. */
+int ure_host_assign_desc_f64(const double *w, int64_t n, int32_t k, int64_t capacity, int32_t *label, double *inertia);
 
 /* ---------------------------------------------------------------------------
  * OT balanced grouping (utils.py:628-656)

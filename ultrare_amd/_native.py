@@ -11,7 +11,7 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'libultrare_hip.so')
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_MODELS_PER_CALL = 32
 
 _vp = ctypes.c_void_p
@@ -113,6 +113,12 @@ _PROTOTYPES = {
     'ure_rank_pairs_scratch': (_i64, [_i64, _i64, _i32, _i32]),
     'ure_rank_pairs': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _i64, _vp]),
+    'ure_pair_knn_scratch': (_i64, [_i64, _i64, _i32, _i32]),
+    'ure_pair_knn': (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'ure_pair_rowsum': (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    'ure_pair_cols': (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    'ure_pair_label_expsum': (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    'ure_host_assign_desc_f64': (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
     'ure_ot_cost': (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     'ure_ot_cost_mfma': (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     'ure_ot_centroids': (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),

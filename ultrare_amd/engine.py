@@ -1186,3 +1186,99 @@ def rank_pairs(tables, d, users, targets, excl=None, stream=None):
     nv.check(L.ure_rank_pairs(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(d_off), nv.ptr(d_items), nv.ptr(e_off), nv.ptr(e_items),
                               nv.ptr(ranks), nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_rank_pairs')
     return ranks
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Reductions of a user-by-user distance matrix (csrc/pair_dist.hip): the k-medoids, LPA and kNN comparison clusterers.
+# metric None / 'given': src is the float32 n x n array D itself; 'euclidean' / 'cosine' / 'manhattan': src is X [n x d]
+# and D is streamed from it, never materialised.
+# ---------------------------------------------------------------------------------------------------------------------
+PAIR_METRICS = {'given': 0, 'euclidean': 1, 'cosine': 2, 'manhattan': 3}
+
+
+def pair_source(src, metric=None):
+    """(device float32 tensor, n, d, metric code) of a distance source, or TypeError / ValueError: the given array must be a
+    square float32 array (no silent cast), X a 2-D float array with n >= 1, d >= 1."""
+    name = 'given' if metric is None else metric
+    if name not in PAIR_METRICS:
+        raise ValueError(f'metric must be None (a given n x n array) or one of euclidean / cosine / manhattan, not {metric!r}')
+    if name == 'given':
+        if (src.dtype != torch.float32) if torch.is_tensor(src) else (np.asarray(src).dtype != np.float32):
+            raise TypeError('a given distance array must be float32 (n x n)')
+        if tuple(src.shape)[:1] * 2 != tuple(src.shape) or src.shape[0] < 1:
+            raise ValueError(f'a given distance array must be square, not {tuple(src.shape)}')
+    elif len(src.shape) != 2 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError(f'the embedding must be 2-D with n, d >= 1, not {tuple(src.shape)}')
+    if torch.is_tensor(src):
+        if not src.is_cuda:
+            raise nv.NativeError('pair distances run on the HIP device only (no CPU fallback)')
+        t = src.to(torch.float32).contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(src, dtype=np.float32)).to(_device())
+    n, d = int(t.shape[0]), int(t.shape[1])
+    return t, n, d, PAIR_METRICS[name]
+
+
+def _index_tensor(ids, dev, hi, what):
+    ids = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+    ids = ids.astype(np.int64).reshape(-1)
+    if ids.size == 0:
+        raise ValueError(f'{what}: need at least one')
+    if ids.min() < 0 or ids.max() >= hi:
+        raise ValueError(f'{what} outside [0, {hi})')
+    return to_device_async(ids.astype(np.int32), dev)
+
+
+def pair_knn(src, n_nb, metric=None, query=None, splits=0, stream=None):
+    """The n_nb nearest columns of each query row of D (ure_pair_knn): query None = every row.  Returns (dist [n_q, n_nb]
+    float32, idx [n_q, n_nb] int64) on the device, ascending by (distance, column); the row itself is in its own list."""
+    t, n, d, code = pair_source(src, metric)
+    n_nb = int(n_nb)
+    if not 1 <= n_nb <= min(n, 128):
+        raise ValueError(f'n_nb must be in [1, min(n, 128)] = [1, {min(n, 128)}], not {n_nb}')
+    q = None if query is None else _index_tensor(query, t.device, n, 'query rows')
+    nq = n if q is None else int(q.numel())
+    L = nv.lib()
+    nbytes = int(L.ure_pair_knn_scratch(nq, n, n_nb, int(splits)))
+    if nbytes < 0:
+        raise ValueError(f'ure_pair_knn_scratch refused n_query = {nq}, n = {n}, n_nb = {n_nb}, splits = {splits}')
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+    dist = torch.empty(nq, n_nb, dtype=torch.float32, device=t.device)
+    idx = torch.empty(nq, n_nb, dtype=torch.int32, device=t.device)
+    nv.check(L.ure_pair_knn(nv.ptr(t), n, d, code, nv.ptr(q), nq, n_nb, int(splits), nv.ptr(dist), nv.ptr(idx), nv.ptr(scratch), nbytes,
+                            nv.stream_handle(stream)), 'ure_pair_knn')
+    return dist, idx.long()
+
+
+def pair_rowsum(src, metric=None, stream=None):
+    """R[u] = sum_v D[u, v] [n] float32 on the device (ure_pair_rowsum), in np.sum(D, axis=1)'s pairwise order."""
+    t, n, d, code = pair_source(src, metric)
+    R = torch.empty(n, dtype=torch.float32, device=t.device)
+    nv.check(nv.lib().ure_pair_rowsum(nv.ptr(t), n, d, code, nv.ptr(R), nv.stream_handle(stream)), 'ure_pair_rowsum')
+    return R
+
+
+def pair_cols(src, cols, metric=None, stream=None):
+    """D[:, cols] [n, m] float32 on the device (ure_pair_cols)."""
+    t, n, d, code = pair_source(src, metric)
+    c = _index_tensor(cols, t.device, n, 'columns')
+    out = torch.empty(n, int(c.numel()), dtype=torch.float32, device=t.device)
+    nv.check(nv.lib().ure_pair_cols(nv.ptr(t), n, d, code, nv.ptr(c), int(c.numel()), nv.ptr(out), nv.stream_handle(stream)), 'ure_pair_cols')
+    return out
+
+
+def pair_label_expsum(src, label, k, metric=None, stream=None):
+    """W[u, g] = sum over i with label[i] == g of exp(-D[i, u]) [n, k] float64 on the device (ure_pair_label_expsum)."""
+    t, n, d, code = pair_source(src, metric)
+    k = int(k)
+    if not 1 <= k <= 128:
+        raise ValueError(f'k must be in [1, 128], not {k}')
+    lab = label.detach().cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
+    lab = lab.astype(np.int64).reshape(-1)
+    if lab.shape != (n,) or lab.min() < 0 or lab.max() >= k:
+        raise ValueError(f'label must be n = {n} values in [0, {k})')
+    lab_d = to_device_async(lab.astype(np.int32), t.device)
+    W = torch.empty(n, k, dtype=torch.float64, device=t.device)
+    nv.check(nv.lib().ure_pair_label_expsum(nv.ptr(t), n, d, code, nv.ptr(lab_d), k, nv.ptr(W), nv.stream_handle(stream)),
+             'ure_pair_label_expsum')
+    return W

@@ -11,7 +11,7 @@ from os.path import abspath, exists, join
 
 import numpy as np
 
-from .method.utils import atomic_save, kmeans, ot_cluster
+from .method.utils import _dense_f32, atomic_save, kmeans, kmedoids, lpa, ot_cluster
 
 DATA_DIR = abspath(os.environ.get('ULTRARE_DATA_DIR', join(os.getcwd(), 'data')))
 SAVE_DIR = abspath(os.environ.get('ULTRARE_SAVE_DIR', join(os.getcwd(), 'result')))
@@ -35,8 +35,10 @@ class Group(object):
 
         [trans_var, cluster_var] = var.strip().split('-')
         # 'ot' is the published path (group.py:35-45); 'kmeans' / 'bkmeans' are the comparison clusterers the
-        # reference imports but never dispatches (group.py:5, utils.py:354-418): an optional addition here
-        assert cluster_var in ['ot', 'kmeans', 'bkmeans'], "cluster_var must be 'ot' (published path), 'kmeans' or 'bkmeans'"
+        # reference imports but never dispatches (group.py:5, utils.py:354-418): an optional addition here, as are
+        # '(b)kmedoids' and '(b)lpa' (utils.py:458-611) on the euclidean distances of the embedding, streamed
+        assert cluster_var in ['ot', 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa', 'blpa'], \
+            "cluster_var must be 'ot' (published path), 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa' or 'blpa'"
         if trans_var == 'rating':
             embedding = np.asarray(self.rating.todense(), dtype=np.float32)
         elif trans_var == 'emb':
@@ -45,8 +47,14 @@ class Group(object):
             raise ValueError(var)
         if cluster_var == 'ot':
             _, label = ot_cluster(embedding, n_group)
-        else:
+        elif cluster_var in ('kmeans', 'bkmeans'):
             label = kmeans(n_group, len(embedding), embedding, balanced=cluster_var == 'bkmeans')
+        elif cluster_var in ('kmedoids', 'bkmedoids'):
+            X = _dense_f32(embedding)
+            label = kmedoids(n_group, len(X), X, balanced=cluster_var == 'bkmedoids', metric='euclidean')
+        else:
+            X = _dense_f32(embedding)
+            label = lpa(n_group, len(X), X, balanced=cluster_var == 'blpa', metric='euclidean')
 
         if verbose:
             print(''.join(str(i) + ': ' + str(int((label == i).sum())) + ', ' for i in range(n_group)))

@@ -8,6 +8,10 @@ the reference), backed by the HIP engine.
   rank_eval    (new)             full-ranking HR@K / Recall@K / NDCG@K / MRR of the test pairs (rank_metrics: the reduction)
   computeNDCG / computeDCG  utils.py:190-210
   ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD)
+  kmeans       utils.py:354-418  (balanced) k-means, a comparison clusterer
+  findNeighbor utils.py:422-455  the k-nearest-neighbour user graph
+  lpa          utils.py:458-519  (balanced) label propagation, a comparison clusterer
+  kmedoids     utils.py:546-611  (balanced) k-medoids, a comparison clusterer
   saveObject / loadObject / timefn  utils.py:319-326, 616-626
 
 Training does not go through a `baseTrain(dataloader, model, loss_fn, opt, ...)` loop:
@@ -369,6 +373,143 @@ def kmeans(n_group, n_user, sp_mat, balanced=False, n_init=5, max_iter=10):
     tmp_inertia, fin_label = 1e10, None
     for _ in range(n_init):
         label, inertia = singleKmeans(n_group, n_user, sp_mat, balanced, max_iter)
+        if inertia < tmp_inertia:
+            tmp_inertia = inertia
+            fin_label = label
+    return fin_label
+
+
+# ---------------------------------------------------------------------------
+# The user-by-user distance clusterers (utils.py:422-611): the kNN user graph, label propagation and k-medoids.  The
+# reference builds a dense n x n array for them (146 MB at ml-1m, 105 GB at n = 162,000); here each needs only a
+# reduction of that matrix -- a row's nearest columns, the row sums and the medoid columns, or per-row sums of exp(-D)
+# grouped by label -- which csrc/pair_dist.hip computes from tiles that never leave the chip.  `metric=None` takes the
+# reference's own contract, a float32 n x n array; 'euclidean' / 'cosine' / 'manhattan' take X [n x d] and stream D.
+# The assignments (argmin / argmax, or the balanced greedy fill over a global sort) run on the host.
+# ---------------------------------------------------------------------------
+def _pair_input(k, n_user, arr, metric, k_max=None):
+    """The device distance source of a clusterer call, after the checks that need no device."""
+    if not torch.is_tensor(arr):
+        arr = _dense_f32(arr) if metric is not None else np.asarray(arr)
+    n = int(arr.shape[0]) if len(arr.shape) else 0
+    if n != n_user:
+        raise ValueError(f'n_user = {n_user} but the input has {n} rows')
+    if not 1 <= k <= n:
+        raise ValueError(f'need 1 <= k <= n clusters, not k = {k}, n = {n}')
+    if k_max is not None and k > k_max:
+        raise ValueError(f'at most {k_max} groups, not {k}')
+    return engine.pair_source(arr, metric)[0]
+
+
+def findNeighbor(cache_dir, sp_mat, n_user, var='euclidean', n_neighbor=10):
+    """utils.py:422-455: nei_idx int [n_user, n_neighbor], the nearest users of each user by `var` ('euclidean', 'cosine' or
+    'manhattan'; ascending distance, exact ties by ascending id, the user itself included), and nei_val float16 = -distance.
+    sp_mat: csr_matrix or array [n_user, n_embedding].  Saves np.save(cache_dir + var, [nei_idx, nei_val]) as the reference does.
+    As shipped, the reference never reads that cache (`if cache_dir == True` is false for any path), so this always computes
+    and then saves.  The distances are the difference form in float32 (csrc/pair_dist.hip), not sklearn's; n_neighbor <= 128."""
+    if var not in ('euclidean', 'cosine', 'manhattan'):
+        raise ValueError(f"var must be 'euclidean', 'cosine' or 'manhattan', not {var!r}")
+    X = _dense_f32(sp_mat)
+    if X.shape[0] != n_user:
+        raise ValueError(f'n_user = {n_user} but sp_mat has {X.shape[0]} rows')
+    dist, idx = engine.pair_knn(X, n_neighbor, var)
+    nei_idx = idx.cpu().numpy().astype(int)
+    nei_val = (-dist).cpu().numpy().astype(np.float16)
+    np.save(cache_dir + var, [nei_idx, nei_val])
+    return nei_idx, nei_val
+
+
+def _kmedoids_run(k, n, src, R, balanced, max_iter, metric):
+    L = nv.lib()
+    group_len = int(np.ceil(n / k))
+    cen_idx = np.random.choice(n, k, replace=False)
+    label = np.zeros(n, dtype=np.int32)
+    new_label = np.empty(n, dtype=np.int32)
+    inertia = ctypes.c_double(0.0)
+    for _ in range(max_iter):
+        dist = np.ascontiguousarray(engine.pair_cols(src, cen_idx, metric).cpu().numpy())
+        nv.check(L.ure_host_kmeans_assign(dist.ctypes.data, n, k, group_len if balanced else 0, new_label.ctypes.data,
+                                          ctypes.byref(inertia)), 'ure_host_kmeans_assign')
+        if (new_label == label).all():
+            break
+        label = new_label.copy()
+        # as shipped (utils.py:589-594): the new medoid is the member with the smallest sum over ALL n columns (first
+        # minimum), not over its own cluster as in textbook PAM
+        for c in range(k):
+            members = np.flatnonzero(label == c)
+            if members.size == 0:
+                raise ValueError(f'cluster {c} lost all its members (the reference fails on argmin of an empty array)')
+            cen_idx[c] = members[np.argmin(R[members])]
+    return label.astype(np.int64), float(inertia.value), cen_idx
+
+
+def singleKmedoids(k, n_user, dist_arr, balanced, max_iter, metric=None, return_medoids=False):
+    """utils.py:546-594: one k-medoids run from k medoids drawn by np.random.choice(n_user, k, replace=False) (numpy's global
+    generator).  dist_arr: the float32 n x n array (metric None), or X [n x d] with D streamed by `metric`.  Each round assigns
+    every user to its nearest medoid (argmin, first minimum) or, balanced, fills groups of ceil(n / k) in ascending distance
+    (ure_host_kmeans_assign); the new medoid of a cluster is its member with the smallest row sum over ALL users, as shipped
+    (not textbook PAM, which sums over the cluster).  An empty cluster raises ValueError.  Returns (label int64 [n_user],
+    inertia = np.sum of the assigned distances in float32), and the final medoids when return_medoids."""
+    src = _pair_input(k, n_user, dist_arr, metric)
+    R = engine.pair_rowsum(src, metric).cpu().numpy()
+    label, inertia, cen_idx = _kmedoids_run(k, n_user, src, R, balanced, max_iter, metric)
+    return (label, inertia, cen_idx) if return_medoids else (label, inertia)
+
+
+def kmedoids(n_group, n_user, arr, balanced=False, n_init=5, max_iter=10, metric=None):
+    """utils.py:597-611: the labels of the best of n_init singleKmedoids runs (smallest inertia below 1e10; None when no run
+    gets there, as kmeans).  The row sums are computed once and shared by every run."""
+    src = _pair_input(n_group, n_user, arr, metric)
+    R = engine.pair_rowsum(src, metric).cpu().numpy()
+    tmp_inertia, fin_label = 1e10, None
+    for _ in range(n_init):
+        label, inertia, _ = _kmedoids_run(n_group, n_user, src, R, balanced, max_iter, metric)
+        if inertia < tmp_inertia:
+            tmp_inertia = inertia
+            fin_label = label
+    return fin_label
+
+
+def _lpa_run(n_group, n, src, balanced, max_iter, metric):
+    L = nv.lib()
+    group_len = int(np.ceil(n / n_group))
+    label = np.random.randint(0, n_group, size=(n))
+    inertia = 0.0
+    for _ in range(max_iter):
+        W = np.ascontiguousarray(engine.pair_label_expsum(src, label, n_group, metric).cpu().numpy())
+        if not balanced:
+            new_label = W.argmax(axis=1)
+            inertia = float(np.sum(W[np.arange(n), new_label]))
+        else:
+            lab32, inert = np.empty(n, dtype=np.int32), ctypes.c_double(0.0)
+            nv.check(L.ure_host_assign_desc_f64(W.ctypes.data, n, n_group, group_len, lab32.ctypes.data, ctypes.byref(inert)),
+                     'ure_host_assign_desc_f64')
+            new_label, inertia = lab32.astype(np.int64), float(inert.value)
+        if (new_label == label).all():
+            break
+        label = new_label
+    return np.asarray(label, dtype=np.int64), inertia
+
+
+def singleLPA(n_group, n_user, dist_arr, balanced, n_neighbor, max_iter=10, metric=None):
+    """utils.py:458-499: label propagation from labels drawn by np.random.randint(0, n_group, size=n_user).  Each round the
+    weight of user u for group g is W[u, g] = sum over users i labelled g of exp(-D[i, u]) (float32 exp, float64 sums); the
+    new label is the heaviest group (argmax, first maximum) or, balanced, groups of ceil(n / n_group) filled in descending
+    weight (ure_host_assign_desc_f64).  n_neighbor is unused, as in the reference.  dist_arr: the float32 n x n array
+    (metric None) or X [n x d] with D streamed by `metric`; n_group <= 128.  Returns (label int64, inertia = np.sum of the
+    chosen weights).  The reference's progress prints are not reproduced."""
+    src = _pair_input(n_group, n_user, dist_arr, metric, k_max=128)
+    return _lpa_run(n_group, n_user, src, balanced, max_iter, metric)
+
+
+def lpa(n_group, n_user, dist_arr, balanced=False, n_init=5, max_iter=10, metric=None):
+    """utils.py:502-519: the labels of the n_init singleLPA run with the SMALLEST inertia below 1e10, as shipped (a larger
+    weight is the better grouping); None when no run gets there, as kmeans.  Reference defect fixed: utils.py:515 passes
+    n_user into singleLPA's `balanced` slot, so the reference always runs balanced LPA; here `balanced` is honoured."""
+    src = _pair_input(n_group, n_user, dist_arr, metric, k_max=128)
+    tmp_inertia, fin_label = 1e10, None
+    for _ in range(n_init):
+        label, inertia = _lpa_run(n_group, n_user, src, balanced, max_iter, metric)
         if inertia < tmp_inertia:
             tmp_inertia = inertia
             fin_label = label

@@ -15,6 +15,7 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         (new)             full-catalogue top-k of the ensemble mean
     torch.ops.ultrare.rank_pairs(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items)
                                                         (new)             exact full-catalogue rank of each target pair
+    torch.ops.ultrare.pair_knn(X, query, n_nb, metric)  utils.py:422-455  the n_nb nearest users of each query row, D streamed
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -127,3 +128,15 @@ def rank_pairs(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.Tens
 @rank_pairs.register_fake
 def _(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items):
     return Us[0].new_empty(tgt_items.numel(), dtype=torch.int32)
+
+
+@torch.library.custom_op('ultrare::pair_knn', mutates_args=())
+def pair_knn(X: torch.Tensor, query: Optional[torch.Tensor], n_nb: int, metric: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(X, *([query] if query is not None else []))
+    return engine.pair_knn(X, n_nb, None if metric == 'given' else metric, query)
+
+
+@pair_knn.register_fake
+def _(X, query, n_nb, metric):
+    n_q = X.shape[0] if query is None else query.numel()
+    return X.new_empty(n_q, n_nb), X.new_empty(n_q, n_nb, dtype=torch.int64)
