@@ -23,7 +23,10 @@ it starts N rank processes before anything touches the GPU and relays rank 0's J
     32 shards, d = 128) and configs[4] (16-shard learn + unlearn through Sisa, wall time).
   --split 1 runs a workload in that split mode as the headline instead.
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` and `cpu_baseline`.
+A plain run does what the headline needs and no more: set-up, W warm-up and K timed steps, --dump-outputs, ONE JSON line on
+rank 0 (driver contract).  --full adds everything else the line can hold, each leg as it was before the option existed: the
+step kernel's `roofline` (a profiled pass of its own) and the second timed region with every tag resident; at N = 1
+`cpu_baseline`, `unlearn` / `value_request`, `ot` and `roofline_hbm`; at N > 1 `exchange` and `north_star_splits`.
 """
 import argparse
 import importlib.util
@@ -58,6 +61,9 @@ def parse():
                     help='1: ONE job, its shards placed across the ranks (strong scaling); 0: every rank its own job (weak)')
     ap.add_argument('--splits', default='auto',
                     help="extra legs at N > 1: comma list of config2,config3,config4 ; 'auto' = all three ; 'none'")
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beyond the headline (roofline, resident-tag region, CPU baseline, unlearn, OT, configs[3] shape; '
+                         'N > 1: exchange, north-star splits); the --no-* options below pick among them')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-unlearn', action='store_true', help='skip the learn/unlearn wall-time leg')
     ap.add_argument('--no-hbm-leg', action='store_true', help='N = 1: skip the configs[3]-shape leg (roofline_hbm)')
@@ -185,10 +191,11 @@ class Dist:
 NO_RESIDENT = False
 
 
-def train_leg(D, workload, n_shards, d, batch, steps, warmup, split, roofline_steps=0, keep_job=False, data=None):
+def train_leg(D, workload, n_shards, d, batch, steps, warmup, split, roofline_steps=0, keep_job=False, data=None, resident=True):
     """Make the workload resident, run W warm-up and K timed bench steps of the rank's shards, return the
     measurements.  split: ONE job (same data on every rank), shards placed by assign_shards; otherwise
-    every rank generates and trains its own job."""
+    every rank generates and trains its own job.  resident=False: the second timed region (every tag resident) is
+    not run; the job is sized for it all the same, so its inits, seeds and tags do not depend on that choice."""
     from ultrare_amd import engine, rng, synth
     from ultrare_amd.method.sisa import assign_shards
     spec = synth.ML1M if workload == 'ml1m' else synth.ML25M
@@ -299,11 +306,11 @@ def train_leg(D, workload, n_shards, d, batch, steps, warmup, split, roofline_st
     # ---- timed region: exactly K steps, barrier + synchronize on both sides; the epochs' shuffles inside it ----------------------
     shuffles_timed = (timed_to - b1) * len(mine) if fire else 0
     r = timed(steps, timed_to if fire else None)
-    resident = None
-    if resident_steps:
+    res = None
+    if resident_steps and resident:
         fire_until(epochs)
         torch.cuda.synchronize()
-        resident = timed(resident_steps)
+        res = timed(resident_steps)
     out = {'spec': spec, 'data': data, 'groups': groups, 'mine': mine, 'owner': owner, 'sizes': sizes, 'all_sizes': all_sizes,
            'tps': tps, 'epochs': epochs, 'wall': r['wall'], 'my_wall': r['my_wall'], 'dev_ms': r['dev_ms'], 'n_total': r['n_total'], 'n_inter': r['n_inter'],
            't_rng': t_rng, 't_tags': t_tags, 't0_tick': r['t0_tick'], 'n_launch': r['n_launch'], 'shards': shards, 'job': job, 'waited_ms': r['waited_ms'],
@@ -311,7 +318,7 @@ def train_leg(D, workload, n_shards, d, batch, steps, warmup, split, roofline_st
            'value': r['n_total'] / r['wall'] if r['wall'] > 0 else 0.0,
            'batch_tags': ('device (rng.device_tags -> csrc/perm_chain.hip on a side stream, in the product\'s chunks), launched inside the timed region' if dev_tags else
                           'host-made, resident before the timed region'),
-           'shuffles_in_timed_region': shuffles_timed, 'resident': resident}
+           'shuffles_in_timed_region': shuffles_timed, 'resident': res}
     if not keep_job and job is not None:
         job.close()
         out['job'] = None
@@ -701,13 +708,16 @@ def main():
     a.shards = a.shards or (5 if a.workload == 'ml1m' else 32)
     a.d = a.d or (32 if a.workload == 'ml1m' else 128)
     split = bool(a.split) and D.pg is not None
-    leg = train_leg(D, a.workload, a.shards, a.d, a.batch, a.steps, a.warmup, split, a.roofline_steps, keep_job=True)
+    # (the job is sized for the roofline pass and the resident-tag region whether they run or not: a plain run's steps, inits and tags are
+    # those of a --full run.  --dump-outputs writes the tables as they stand after the resident-tag region, so a plain run that dumps runs it)
+    leg = train_leg(D, a.workload, a.shards, a.d, a.batch, a.steps, a.warmup, split, a.roofline_steps, keep_job=True,
+                    resident=a.full or bool(a.dump_outputs))
     spec, job = leg['spec'], leg['job']
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, leg, rank, world)
 
-    roofline = roofline_of(a, leg, a.d, a.batch) if job is not None and (rank == 0) else None
-    if job is not None and rank != 0:
+    roofline = roofline_of(a, leg, a.d, a.batch) if a.full and job is not None and (rank == 0) else None
+    if a.full and job is not None and rank != 0:
         job.run_profiled(a.roofline_steps * leg['tps'])          # every rank does the same work outside the timed region
 
     arch = ''
@@ -756,7 +766,7 @@ def main():
             real_stdout.write(json.dumps(finite(out)) + '\n')
             real_stdout.flush()
 
-    if D.pg is not None:
+    if a.full and D.pg is not None:
         # ---- N > 1 extras: the exchange over RCCL and the north-star splits.  A watchdog prints the
         # line with what is there and ends the process if a collective never returns.
         def expire():
@@ -783,7 +793,7 @@ def main():
         if which:
             attempt('north_star_splits', lambda: split_legs(a, D, which))
         dog.cancel()
-    else:
+    elif a.full:
         # ---- N = 1 extras (rank 0 is the only rank): CPU baseline and the unlearn half of the metric
         # (an extra that fails -- a box short of memory, a guard of a measurement tripping -- costs its own object, never the line: the
         # headline and its roofline are already in `out`)
@@ -847,6 +857,8 @@ def main():
                 return hbm_leg(a, D)
             guarded('roofline_hbm', hbm)
     emit()
+    if job is not None:
+        job.close()
     if D.pg is not None:
         D.pg.destroy_process_group()
 

@@ -106,9 +106,9 @@ def _bench(args, timeout=900):
 def test_bench_gpus_2_starts_two_ranks_itself():
     """`python bench.py --gpus 2` with no launcher: the script starts both ranks (here over gloo, both on
     the one visible GPU), rank 0 prints the one JSON line with n_gpus == 2, the exchange leg ran the
-    all-gather, and the configs[2] split placed ONE job's 8 shards over both ranks."""
+    all-gather, and the configs[2] split placed ONE job's 8 shards over both ranks (--full: the legs beyond the headline)."""
     out = _bench(['--gpus', '2', '--backend', 'gloo', '--force-device', '0', '--steps', '2', '--warmup', '1',
-                  '--roofline-steps', '1', '--splits', 'config2'])
+                  '--roofline-steps', '1', '--splits', 'config2', '--full'])
     assert out['n_gpus'] == 2 and out['scaling'] == 'weak' and out['value'] > 0
     assert out['interactions_timed'] > 2 * 2 * 5 * 100000          # both ranks' shards were counted
     ex = out['exchange']
@@ -121,7 +121,7 @@ def test_bench_gpus_2_starts_two_ranks_itself():
 def test_bench_rccl_calls_on_one_rank():
     """The RCCL half of the N > 1 path on a one-GPU box: a one-rank nccl process group runs the same
     init / barrier / all_reduce / all_gather_into_tensor calls the 8-GPU run makes."""
-    out = _bench(['--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1', '--roofline-steps', '1', '--splits', 'config2'])
+    out = _bench(['--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1', '--roofline-steps', '1', '--splits', 'config2', '--full'])
     assert out['n_gpus'] == 1 and out['exchange']['backend'] == 'nccl' and out['exchange']['received_ok']
     assert out['north_star_splits']['config2']['shards_per_rank'] == [8]
 
@@ -130,6 +130,25 @@ def test_bench_split_mode_headline():
     out = _bench(['--gpus', '2', '--backend', 'gloo', '--force-device', '0', '--steps', '2', '--warmup', '1', '--roofline-steps', '1',
                   '--split', '1', '--shards', '8', '--d', '64', '--splits', 'none'])
     assert out['n_gpus'] == 2 and out['scaling'] == 'strong' and out['config']['shards_per_gpu'] == 4
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the line holds the headline and nothing measured beside it; the tables a plain run leaves (--dump-outputs)
+    are, bit for bit, those of a --full run of the same arguments."""
+    common = ['--gpus', '1', '--steps', '2', '--warmup', '1', '--roofline-steps', '1']
+    out = _bench(common)
+    assert out['value'] > 0 and out['ms_per_step'] > 0 and out['steps'] == 2 and out['warmup'] == 1 and out['n_gpus'] == 1
+    assert out['unit'] == 'interactions/s' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert out['roofline'] is None and out['cpu_baseline'] is None and out['unlearn'] is None and out['value_resident_tags'] is None
+    assert not {'ot', 'roofline_hbm', 'value_request', 'exchange', 'north_star_splits'} & set(out)
+    plain = _bench(common + ['--dump-outputs', str(tmp_path / 'plain')])
+    full = _bench(common + ['--full', '--no-cpu-baseline', '--no-unlearn', '--no-ot', '--no-hbm-leg', '--dump-outputs', str(tmp_path / 'full')])
+    assert plain['roofline'] is None and full['roofline']['frac'] > 0
+    assert plain['interactions_timed'] == full['interactions_timed'] == out['interactions_timed']
+    files = sorted(os.listdir(tmp_path / 'full'))
+    assert files and files == sorted(os.listdir(tmp_path / 'plain'))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'plain' / f), np.load(tmp_path / 'full' / f)), f
 
 
 def test_cli_under_two_ranks_writes_one_set_of_artifacts(tmp_path):

@@ -17,12 +17,12 @@ stats() {   # name, script, args...
   [ -n "$f" ] && cp "$f" "$OUT/${name}_kernel_stats.csv"
   rm -rf "$OUT/trace_$name"
 }
-python3 "$ROOT/bench.py" > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"; echo "bench rc=$?"
-python3 "$ROOT/bench.py" --workload ml25m --no-cpu-baseline > "$OUT/bench_ml25m.json" 2> "$OUT/bench_ml25m.err"; echo "bench ml25m rc=$?"
-python3 "$ROOT/bench.py" --gpus 2 --backend gloo --force-device 0 > "$OUT/bench_2ranks_gloo_one_gpu.json" 2> "$OUT/bench_2ranks.err"; echo "bench 2 ranks rc=$?"
-python3 "$ROOT/bench.py" --gpus 1 --force-dist --no-cpu-baseline > "$OUT/bench_1rank_rccl.json" 2> "$OUT/bench_1rank_rccl.err"; echo "bench rccl rc=$?"
-stats bench "$ROOT/bench.py" --no-cpu-baseline
-stats bench_ml25m "$ROOT/bench.py" --workload ml25m --no-cpu-baseline --no-unlearn --steps 5 --warmup 1
+python3 "$ROOT/bench.py" --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"; echo "bench rc=$?"
+python3 "$ROOT/bench.py" --full --workload ml25m --no-cpu-baseline > "$OUT/bench_ml25m.json" 2> "$OUT/bench_ml25m.err"; echo "bench ml25m rc=$?"
+python3 "$ROOT/bench.py" --full --gpus 2 --backend gloo --force-device 0 > "$OUT/bench_2ranks_gloo_one_gpu.json" 2> "$OUT/bench_2ranks.err"; echo "bench 2 ranks rc=$?"
+python3 "$ROOT/bench.py" --full --gpus 1 --force-dist --no-cpu-baseline > "$OUT/bench_1rank_rccl.json" 2> "$OUT/bench_1rank_rccl.err"; echo "bench rccl rc=$?"
+stats bench "$ROOT/bench.py" --full --no-cpu-baseline
+stats bench_ml25m "$ROOT/bench.py" --full --workload ml25m --no-cpu-baseline --no-unlearn --steps 5 --warmup 1
 stats e2e_sisa "$ROOT/tools/e2e_sisa.py"
 stats ot "$ROOT/tools/profile_ot.py" --rounds 4
 python3 "$ROOT/tools/pmc_traffic.py" "$OUT/pmc" --tag "$TAG" > "$OUT/pmc_ml1m.log" 2>&1; echo "pmc ml1m rc=$?"

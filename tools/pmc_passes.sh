@@ -16,7 +16,7 @@ while read -r group; do
   [ -z "$group" ] && continue
   n=$((n+1))
   echo "pass $n: $group"
-  timeout -k 10 150 rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OUT/$n" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-unlearn --steps 5 --warmup 1 > "$OUT/$n.log" 2>&1
+  timeout -k 10 150 rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OUT/$n" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-unlearn --steps 5 --warmup 1 > "$OUT/$n.log" 2>&1
 done < <(if [ -n "$GROUPS_FILE" ]; then cat "$GROUPS_FILE"; else cat <<'GROUPS'
 FETCH_SIZE
 WRITE_SIZE

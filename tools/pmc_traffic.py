@@ -3,8 +3,8 @@
 
     python tools/pmc_traffic.py OUT_DIR [--tag r02] [-- bench.py arguments ...]
 
-Runs `rocprofv3 --pmc <GROUP> --kernel-trace --output-format csv -- python3 bench.py <args> --no-cpu-baseline
---no-unlearn --steps 5 --warmup 1`, one pass per counter group (FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum
+Runs `rocprofv3 --pmc <GROUP> --kernel-trace --output-format csv -- python3 bench.py <args> --full --no-cpu-baseline
+--no-unlearn --no-hbm-leg --steps 5 --warmup 1`, one pass per counter group (FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum
 TCC_REQ_sum), never combined with another tracing domain, and writes
     OUT_DIR/<tag>_pmc_hbm_traffic_<workload>_s<shards>_d<d>_b<batch>.json
 with per-kernel means, the corrected bytes per launch (gfx950: FETCH_SIZE counts 128-B requests at 64 B for wide
@@ -42,7 +42,7 @@ def main():
     shards = opt('--shards', '5' if workload == 'ml1m' else '32')
     d = opt('--d', '32' if workload == 'ml1m' else '128')
     batch = opt('--batch', '30000')
-    tail = ['--no-cpu-baseline', '--no-unlearn', '--no-hbm-leg'] + ([] if '--steps' in bench_args else ['--steps', '5']) + ([] if '--warmup' in bench_args else ['--warmup', '1'])
+    tail = ['--full', '--no-cpu-baseline', '--no-unlearn', '--no-hbm-leg'] + ([] if '--steps' in bench_args else ['--steps', '5']) + ([] if '--warmup' in bench_args else ['--warmup', '1'])
     cmd_tail = ['python3', os.path.join(ROOT, 'bench.py')] + bench_args + tail
     env = dict(os.environ, TMPDIR='/tmp')
     sums = defaultdict(lambda: defaultdict(lambda: [0.0, 0]))
