@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define URE_ABI_VERSION 12
+#define URE_ABI_VERSION 13
 #define URE_MAX_MODELS_PER_CALL 32
 #define URE_SCORE_PARTIALS 2048       /* length of ure_score's sse buffer */
 
@@ -560,6 +560,19 @@ int ure_ot_assign(const float *dist_host, int64_t n, int k, int32_t *label_host,
 int ure_ot_potentials(const float *dist, int64_t n, int k, int iters, double *pi_host, int64_t *misplaced, void *stream);
 int ure_ot_assign_warm(const float *dist_host, int64_t n, int k, const double *pi, int32_t *label_host, int32_t *plan_nk,
                        double *total_cost, int64_t *augmentations);
+/* Entropic OT (ABI 13; csrc/ot_sinkhorn.hip): an opt-in, non-parity alternative to the exact LP, solved on the device.
+ * Log-domain Sinkhorn with POT's sinkhorn_log semantics on M = dist^T (dist [k][n] fp32, device), a = 1/n, b = 1/k, from
+ * u = v = 0, in float64: per iteration v = log b - LSE_i(-M_ij / reg + u_i), u = log a - LSE_j(-M_ij / reg + v_j); every
+ * 10th iteration (0, 10, ...) err = || column sums of the plan - b ||_2 and the solve stops at the first err < stop_thr.
+ * reg is absolute, in the cost's units.  Outputs (device): v [k], u [n] (optional), label [n] int32 = first argmax_j of
+ * -M_ij / reg + v_j, cost_min [n] fp32 (optional) = min_j M_ij; (host) *iters = iterations run, *err = the last err.
+ * 1 <= k <= 1024, 1 <= n < 2^31, reg > 0 finite, num_iter_max >= 1, stop_thr >= 0; scratch (device) holds
+ * ure_ot_sinkhorn_scratch(n, k) bytes (O(n + k n / 256); -1 for n, k out of range).  The plan is never formed.  Bitwise
+ * reproducible; the host reads a stop word once per batch of 10-160 iterations and the call returns after synchronising
+ * `stream`.  A non-finite err is an error. */
+int64_t ure_ot_sinkhorn_scratch(int64_t n, int k);
+int ure_ot_sinkhorn(const float *dist, int64_t n, int k, double reg, int num_iter_max, double stop_thr, double *u, double *v,
+                    int32_t *label, float *cost_min, void *scratch, int64_t scratch_bytes, int32_t *iters, double *err, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Comparison clusterers (utils.py:354-418: k-means / balanced k-means on the user embedding;

@@ -11,7 +11,7 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'libultrare_hip.so')
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_MODELS_PER_CALL = 32
 
 _vp = ctypes.c_void_p
@@ -129,6 +129,9 @@ _PROTOTYPES = {
     'ure_ot_assign': (ctypes.c_int, [_vp, _i64, ctypes.c_int, _vp, _vp, ctypes.POINTER(ctypes.c_double)]),
     'ure_ot_potentials': (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_i64), _vp]),
     'ure_ot_assign_warm': (ctypes.c_int, [_vp, _i64, ctypes.c_int, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
+    'ure_ot_sinkhorn_scratch': (_i64, [_i64, ctypes.c_int]),
+    'ure_ot_sinkhorn': (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _i64,
+                                       ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_double), _vp]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

@@ -1282,3 +1282,45 @@ def pair_label_expsum(src, label, k, metric=None, stream=None):
     nv.check(nv.lib().ure_pair_label_expsum(nv.ptr(t), n, d, code, nv.ptr(lab_d), k, nv.ptr(W), nv.stream_handle(stream)),
              'ure_pair_label_expsum')
     return W
+
+
+SINKHORN_MAX_K = 1024
+
+
+def check_sinkhorn_args(reg, num_iter_max, stop_thr):
+    """The entropic solver's settings, checked before any device work (ValueError)."""
+    if isinstance(reg, bool) or not isinstance(reg, (int, float, np.floating, np.integer)) or not (np.isfinite(reg) and reg > 0):
+        raise ValueError(f'reg must be a finite number > 0, not {reg!r}')
+    if isinstance(num_iter_max, bool) or not isinstance(num_iter_max, (int, np.integer)) or not 1 <= num_iter_max < 2 ** 31:
+        raise ValueError(f'num_iter_max must be an integer >= 1, not {num_iter_max!r}')
+    if not isinstance(stop_thr, (int, float, np.floating, np.integer)) or not stop_thr >= 0:
+        raise ValueError(f'stop_thr must be a number >= 0, not {stop_thr!r}')
+
+
+def ot_sinkhorn(dist, reg=1e-3, num_iter_max=1000, stop_thr=1e-9, want_u=True, want_cost_min=False, stream=None):
+    """Log-domain Sinkhorn (ure_ot_sinkhorn) on a device cost matrix dist [k, n] float32 (ure_ot_cost's layout), uniform
+    marginals.  Returns a dict of device tensors label [n] int32, v [k] float64, u [n] float64 (want_u) and cost_min [n]
+    float32 (want_cost_min), and the host values iters (int) and err (float)."""
+    check_sinkhorn_args(reg, num_iter_max, stop_thr)
+    if not torch.is_tensor(dist) or not dist.is_cuda:
+        raise nv.NativeError('ot_sinkhorn runs on the HIP device only (no CPU fallback)')
+    if dist.dim() != 2 or dist.dtype != torch.float32:
+        raise ValueError(f'dist must be a [k, n] float32 tensor, not {tuple(dist.shape)} {dist.dtype}')
+    k, n = int(dist.shape[0]), int(dist.shape[1])
+    if not (1 <= k <= SINKHORN_MAX_K and 1 <= n < 2 ** 31):
+        raise ValueError(f'need 1 <= k <= {SINKHORN_MAX_K} and 1 <= n < 2^31, not k = {k}, n = {n}')
+    dist = dist.contiguous()
+    L, dev = nv.lib(), dist.device
+    nbytes = int(L.ure_ot_sinkhorn_scratch(n, k))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = {'label': torch.empty(n, dtype=torch.int32, device=dev), 'v': torch.empty(k, dtype=torch.float64, device=dev)}
+    if want_u:
+        out['u'] = torch.empty(n, dtype=torch.float64, device=dev)
+    if want_cost_min:
+        out['cost_min'] = torch.empty(n, dtype=torch.float32, device=dev)
+    iters, err = ctypes.c_int32(), ctypes.c_double()
+    nv.check(L.ure_ot_sinkhorn(nv.ptr(dist), n, k, float(reg), int(num_iter_max), float(stop_thr), nv.ptr(out.get('u')), nv.ptr(out['v']),
+                               nv.ptr(out['label']), nv.ptr(out.get('cost_min')), nv.ptr(scratch), nbytes, ctypes.byref(iters),
+                               ctypes.byref(err), nv.stream_handle(stream)), 'ure_ot_sinkhorn')
+    out['iters'], out['err'] = int(iters.value), float(err.value)
+    return out

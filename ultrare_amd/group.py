@@ -25,7 +25,9 @@ class Group(object):
         self.n_user = self.rating.shape[0] if rating is not None else (len(user_mat) if user_mat is not None else 0)
         self.n_item = self.rating.shape[1] if rating is not None else 0
 
-    def grouping(self, dataset='ml1m', n_group=2, var='emb-ot', verbose=True, data_dir=None):
+    def grouping(self, dataset='ml1m', n_group=2, var='emb-ot', verbose=True, data_dir=None, *, reg=1e-3):
+        """reg: the entropic regulariser of the 'sinkhorn' clusterer (absolute, in squared-distance units; ignored by the others
+        and not part of the cache file's name)."""
         assert n_group > 1
         label_dir = (data_dir or DATA_DIR) + '/' + dataset + '/val/' + var + str(n_group) + '.npy'
 
@@ -36,9 +38,10 @@ class Group(object):
         [trans_var, cluster_var] = var.strip().split('-')
         # 'ot' is the published path (group.py:35-45); 'kmeans' / 'bkmeans' are the comparison clusterers the
         # reference imports but never dispatches (group.py:5, utils.py:354-418): an optional addition here, as are
-        # '(b)kmedoids' and '(b)lpa' (utils.py:458-611) on the euclidean distances of the embedding, streamed
-        assert cluster_var in ['ot', 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa', 'blpa'], \
-            "cluster_var must be 'ot' (published path), 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa' or 'blpa'"
+        # '(b)kmedoids' and '(b)lpa' (utils.py:458-611) on the euclidean distances of the embedding, streamed, and 'sinkhorn':
+        # ot_cluster with entropic OT on the device in place of the exact LP (not parity: groups need not be balanced)
+        assert cluster_var in ['ot', 'sinkhorn', 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa', 'blpa'], \
+            "cluster_var must be 'ot' (published path), 'sinkhorn', 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa' or 'blpa'"
         if trans_var == 'rating':
             embedding = np.asarray(self.rating.todense(), dtype=np.float32)
         elif trans_var == 'emb':
@@ -47,6 +50,8 @@ class Group(object):
             raise ValueError(var)
         if cluster_var == 'ot':
             _, label = ot_cluster(embedding, n_group)
+        elif cluster_var == 'sinkhorn':
+            _, label = ot_cluster(embedding, n_group, solver='sinkhorn', reg=reg)
         elif cluster_var in ('kmeans', 'bkmeans'):
             label = kmeans(n_group, len(embedding), embedding, balanced=cluster_var == 'bkmeans')
         elif cluster_var in ('kmedoids', 'bkmedoids'):

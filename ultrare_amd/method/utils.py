@@ -7,7 +7,7 @@ the reference), backed by the HIP engine.
   recommend    (new)             top-k items over the whole catalogue from the same ensemble mean
   rank_eval    (new)             full-ranking HR@K / Recall@K / NDCG@K / MRR of the test pairs (rank_metrics: the reduction)
   computeNDCG / computeDCG  utils.py:190-210
-  ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD)
+  ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD; solver='sinkhorn': entropic OT on the device)
   kmeans       utils.py:354-418  (balanced) k-means, a comparison clusterer
   findNeighbor utils.py:422-455  the k-nearest-neighbour user graph
   lpa          utils.py:458-519  (balanced) label propagation, a comparison clusterer
@@ -294,14 +294,25 @@ def _ot_round(Xd, centroid, n, k, d, dist_d, label_d, cent_d, counts_d, pi=None,
 
 
 @timefn
-def ot_cluster(X, k, max_iters=10, timing=None):
+def ot_cluster(X, k, max_iters=10, timing=None, solver='exact', reg=1e-3, num_iter_max=1000, stop_thr=1e-9):
     """utils.py:628-656.  Initial centroids come from the global numpy generator, as in
-    the reference.  Returns (inertia, label[int64]).  timing (a list, optional): every round's parts in milliseconds (_ot_round)."""
+    the reference.  Returns (inertia, label[int64]).  timing (a list, optional): every round's parts in milliseconds (_ot_round).
+    solver='exact' (the default, the reference's arithmetic: exact EMD) or 'sinkhorn': every round's transport is
+    entropic OT solved on the device (_ot_cluster_sinkhorn), an opt-in that is not bit-parity with the reference; reg,
+    num_iter_max and stop_thr are its settings and are ignored by the exact solver."""
+    if solver not in ('exact', 'sinkhorn'):
+        raise ValueError(f"solver must be 'exact' or 'sinkhorn', not {solver!r}")
+    if solver == 'sinkhorn':
+        engine.check_sinkhorn_args(reg, num_iter_max, stop_thr)
     X = np.ascontiguousarray(X, dtype=np.float32)
     n, d = X.shape
     if k < 1 or k > n:
         raise ValueError('need 1 <= k <= n clusters')
+    if solver == 'sinkhorn' and k > engine.SINKHORN_MAX_K:
+        raise ValueError(f'the sinkhorn solver takes at most {engine.SINKHORN_MAX_K} clusters, not {k}')
     centroid = X[np.random.choice(n, size=k, replace=False)]
+    if solver == 'sinkhorn':
+        return _ot_cluster_sinkhorn(X, centroid, k, max_iters, reg, num_iter_max, stop_thr)
     dev = engine._device()
     Xd = torch.from_numpy(X).to(dev)
     dist_d = torch.empty(k, n, dtype=torch.float32, device=dev)
@@ -316,6 +327,44 @@ def ot_cluster(X, k, max_iters=10, timing=None):
     for _ in range(max_iters):
         dist, label, new_centroid = _ot_round(Xd, centroid, n, k, d, dist_d, label_d, cent_d, counts_d, pi, check, timing)
         inertia = np.min(dist, axis=0).sum()
+        if np.allclose(centroid, new_centroid):
+            break
+        centroid = new_centroid
+    print(f'{inertia:.3f}', end=' ')
+    return inertia, label.astype(np.int64)
+
+
+def _ot_cluster_sinkhorn(X, centroid, k, max_iters, reg, num_iter_max, stop_thr):
+    """ot_cluster's rounds with entropic OT in place of the exact LP: ure_ot_cost -> ure_ot_sinkhorn (labels = argmax of each
+    point's plan row, and every point's cheapest cost for the inertia) -> a stable sort of the labels -> ure_ot_centroids_members,
+    then utils.py's allclose stop.  Only n labels and n minima come to the host, never the [k, n] matrix.  Every round starts
+    from zero potentials.  ot_cluster.sinkhorn_stats: (iterations, marginal error) of every round."""
+    n, d = X.shape
+    L, st, dev = nv.lib(), nv.stream_handle(), engine._device()
+    Xd = torch.from_numpy(X).to(dev)
+    dist_d = torch.empty(k, n, dtype=torch.float32, device=dev)
+    cent_d = torch.empty(k, d, dtype=torch.float32, device=dev)
+    counts_d = torch.empty(k, dtype=torch.int32, device=dev)
+    stats = []
+    ot_cluster.sinkhorn_stats = stats
+    for rnd in range(max_iters):
+        cd = torch.from_numpy(np.ascontiguousarray(centroid, dtype=np.float32)).to(dev)
+        nv.check(L.ure_ot_cost(nv.ptr(Xd), nv.ptr(cd), n, k, d, nv.ptr(dist_d), st), 'ure_ot_cost')
+        r = engine.ot_sinkhorn(dist_d, reg, num_iter_max, stop_thr, want_u=False, want_cost_min=True)
+        stats.append((r['iters'], r['err']))
+        label = r['label'].cpu().numpy()
+        inertia = r['cost_min'].cpu().numpy().sum()                  # == np.min(dist, axis=0).sum(): the same float32 values and order
+        sizes = np.bincount(label, minlength=k)
+        if (sizes == 0).any():
+            raise ValueError(f'ot_cluster(solver=\'sinkhorn\'): round {rnd}: cluster(s) {np.flatnonzero(sizes == 0).tolist()} received no '
+                             f'point, so their centroid (utils.py:648) is undefined; reg = {reg:g} against costs up to '
+                             f'{float(dist_d.max()):.4g}: a larger reg balances the groups')
+        keys = label.astype(np.uint8 if k <= 256 else np.uint16)
+        order = torch.from_numpy(np.argsort(keys, kind='stable').astype(np.int32)).to(dev)
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
+        nv.check(L.ure_ot_centroids_members(nv.ptr(Xd), nv.ptr(order), nv.ptr(off), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
+                 'ure_ot_centroids_members')
+        new_centroid = cent_d.cpu().numpy()
         if np.allclose(centroid, new_centroid):
             break
         centroid = new_centroid

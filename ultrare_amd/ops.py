@@ -16,6 +16,9 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.rank_pairs(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items)
                                                         (new)             exact full-catalogue rank of each target pair
     torch.ops.ultrare.pair_knn(X, query, n_nb, metric)  utils.py:422-455  the n_nb nearest users of each query row, D streamed
+    torch.ops.ultrare.ot_sinkhorn(dist, reg, num_iter_max, stop_thr)
+                                                        (new)             log-domain Sinkhorn on a [k, n] cost matrix ->
+                                                                          (label, u, v, err, iters)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -140,3 +143,16 @@ def pair_knn(X: torch.Tensor, query: Optional[torch.Tensor], n_nb: int, metric: 
 def _(X, query, n_nb, metric):
     n_q = X.shape[0] if query is None else query.numel()
     return X.new_empty(n_q, n_nb), X.new_empty(n_q, n_nb, dtype=torch.int64)
+
+
+@torch.library.custom_op('ultrare::ot_sinkhorn', mutates_args=())
+def ot_sinkhorn(dist: torch.Tensor, reg: float, num_iter_max: int, stop_thr: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float, int]:
+    _dev(dist)
+    r = engine.ot_sinkhorn(dist, reg, num_iter_max, stop_thr)
+    return r['label'], r['u'], r['v'], r['err'], r['iters']
+
+
+@ot_sinkhorn.register_fake
+def _(dist, reg, num_iter_max, stop_thr):
+    k, n = dist.shape
+    return (dist.new_empty(n, dtype=torch.int32), dist.new_empty(n, dtype=torch.float64), dist.new_empty(k, dtype=torch.float64), 0.0, 0)
