@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define URE_ABI_VERSION 13
+#define URE_ABI_VERSION 14
 #define URE_MAX_MODELS_PER_CALL 32
 #define URE_SCORE_PARTIALS 2048       /* length of ure_score's sse buffer */
 
@@ -573,6 +573,36 @@ int ure_ot_assign_warm(const float *dist_host, int64_t n, int k, const double *p
 int64_t ure_ot_sinkhorn_scratch(int64_t n, int k);
 int ure_ot_sinkhorn(const float *dist, int64_t n, int k, double reg, int num_iter_max, double stop_thr, double *u, double *v,
                     int32_t *label, float *cost_min, void *scratch, int64_t scratch_bytes, int32_t *iters, double *err, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Learned shard combiner (ABI 14; csrc/mf_combine.hip): an opt-in, non-parity alternative to the plain mean of the shard
+ * scores (utils.py:140-145).  A generalised linear model over the S scores of a pair, fitted by Newton steps on the host
+ * from sufficient statistics that ONE pass over the pairs leaves on the device; the n x S score matrix is never written.
+ * ------------------------------------------------------------------------- */
+/* For a pair j = (u, i, r) and weights (w[0..S-1], b = w[S]), all in float64: p[j,s] = model s's float32 score, bit for bit
+ * ure_score's for that model alone (n_models = 1, first = 1, last = 0); x[j] = (p[j,0..S-1], 1);
+ * z[j] = b + sum_s w[s] * (double)p[j,s], added in the order b, s = 0, 1, ... and NOT contracted to fma (every product is
+ * rounded, then added), by both calls below.  link 0 ('linear'): mu = z, h = 1, loss = (mu - r)^2 / 2; link 1
+ * ('logistic'): mu = 1 / (1 + exp(-z)), h = mu (1 - mu), loss = max(z, 0) + log1p(exp(-|z|)) - r z.
+ * ure_combine_stats: out (device, ure_combine_stats_len(S) = 2 + (S+1) + (S+1)(S+2)/2 doubles) = { n, sum_j loss_j,
+ * g = sum_j (mu_j - r_j) x[j], H = sum_j h_j x[j] x[j]^T as its upper triangle, row-major }.  w: device, S + 1 doubles.
+ * scratch (device): ure_combine_stats_scratch(n, S) = min(ceil(n / 64), 2048) * ure_combine_stats_len(S) * 8 bytes of
+ * per-workgroup partial sums; both return -1 for S outside 1 .. URE_MAX_MODELS_PER_CALL (or n < 1).  No floating-point
+ * atomics: the order of every addition depends on (n, S) alone, so equal inputs give equal bytes on any stream.
+ * Nothing synchronises. */
+int64_t ure_combine_stats_len(int n_models);
+int64_t ure_combine_stats_scratch(int64_t n, int n_models);
+int ure_combine_stats(const float *const *U_tables, const float *const *V_tables, int n_models, const int32_t *uid, const int32_t *iid,
+                      const float *rating, int64_t n, int d, int link, const double *w, double *out, void *scratch, int64_t scratch_bytes,
+                      void *stream);
+/* pred[j] = (float)mu[j] with the weight row W[group_of_user[uid[j]]] of W (device, [n_groups][S + 1] doubles); row 0 when
+ * group_of_user (device int32 [n_user]) is NULL.  A user whose entry is negative (in no group) takes the mean ensemble
+ * w = 1/S, b = 0 under link 0 and NaN under link 1 (callers refuse such a map on the host).  sse (optional; needs rating):
+ * the partial sums of (pred[j] - rating[j])^2 laid out as ure_score lays them out (URE_SCORE_PARTIALS doubles), so that
+ * ure_eval_users and ure_eval_reduce run on the result unchanged. */
+int ure_score_weighted(const float *const *U_tables, const float *const *V_tables, int n_models, const int32_t *uid, const int32_t *iid,
+                       const float *rating, int64_t n, int d, int link, const double *W, int n_groups, const int32_t *group_of_user,
+                       int32_t n_user, float *pred, double *sse, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Comparison clusterers (utils.py:354-418: k-means / balanced k-means on the user embedding;

@@ -12,17 +12,12 @@
 // keys -- exactly the order of a stable ascending argsort read backwards -- and one
 // lane finishes the float64 DCG in numpy's summation order so that HR is exact and
 // NDCG is bit-identical whenever the two rankings agree with the reference's.
-#include "ure_internal.h"
+#include "score_dot.h"
 
 #include <cfloat>
 #include <climits>
 
 namespace ure {
-
-struct TableList {
-    const float *U[URE_MAX_MODELS_PER_CALL];
-    const float *V[URE_MAX_MODELS_PER_CALL];
-};
 
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void score_kernel(TableList T, int n_models, int n_total, int first, int last,
@@ -57,11 +52,7 @@ __global__ __launch_bounds__(kBlock) void score_kernel(TableList T, int n_models
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float p = a[k].x * b[k].x;
-                p = fmaf(a[k].y, b[k].y, p);
-                p = fmaf(a[k].z, b[k].z, p);
-                p = fmaf(a[k].w, b[k].w, p);
-                p = group_sum<LPR>(p);
+                const float p = pair_dot<LPR>(a[k], b[k]);
                 if (m0 + k < n_models) acc += p;
             }
         }

@@ -933,17 +933,24 @@ class EvalSet:
         nv.check(nv.lib().ure_eval_subset(nv.ptr(plan['users']), plan['n'], nv.ptr(plan['pairs']), plan['n_pairs'], nv.ptr(b['pred']), nv.ptr(self.rating),
                                           nv.ptr(b['hits']), nv.ptr(b['ndcg']), self.n, self.n_users, m, nv.ptr(out_sub[e0]), st), 'ure_eval_subset')
 
-    def evaluate(self, models, d, stream=None, top_k=10, out=None):
+    def evaluate(self, models, d, stream=None, top_k=10, out=None, combiner=None):
         """baseTest (utils.py:115-187) for an ensemble: `models` = list of (U, V) device
-        tensors with row stride d (the padded width).  Returns (rmse, ndcg, hr)."""
+        tensors with row stride d (the padded width).  Returns (rmse, ndcg, hr).
+        combiner (a combine.Combiner, optional): the pairs are scored with its fitted weights (score_weighted) instead of the
+        plain mean; the ranking and the reduction are the same calls on the same buffers."""
         assert top_k == 10, 'the kernel implements the reference default top_k=10'
+        if combiner is not None and combiner.n_models != len(models):
+            raise ValueError(f'the combiner was fitted on {combiner.n_models} models, not {len(models)}')
         if self.n == 0:
             if out is not None:
                 return out.fill_(float('nan'))
             return float('nan'), float('nan'), float('nan')
         L, st = nv.lib(), nv.stream_handle(stream)
         S = len(models)
-        for c0 in range(0, S, nv.MAX_MODELS_PER_CALL):
+        if combiner is not None:
+            W, gou = combiner.on_device(self.device, int(models[0][0].shape[0]))
+            score_weighted(models, d, self.uid, self.iid, self.rating, combiner.link_code, W, gou, pred=self.pred, sse=self.sse, stream=stream)
+        for c0 in (range(0, S, nv.MAX_MODELS_PER_CALL) if combiner is None else ()):
             chunk = models[c0:c0 + nv.MAX_MODELS_PER_CALL]
             for U, V in chunk:
                 assert U.is_contiguous() and V.is_contiguous() and U.shape[1] == d and V.shape[1] == d
@@ -1324,3 +1331,120 @@ def ot_sinkhorn(dist, reg=1e-3, num_iter_max=1000, stop_thr=1e-9, want_u=True, w
                                ctypes.byref(err), nv.stream_handle(stream)), 'ure_ot_sinkhorn')
     out['iters'], out['err'] = int(iters.value), float(err.value)
     return out
+
+
+# ---------------------------------------------------------------------------
+# The learned shard combiner (csrc/mf_combine.hip; the host side of the fit is combine.py)
+# ---------------------------------------------------------------------------
+def _table_ptrs(tables, d, what):
+    """(U pointers, V pointers, S) of a list of padded device (U, V) for one call of the combiner kernels."""
+    S = len(tables)
+    if not 1 <= S <= nv.MAX_MODELS_PER_CALL:
+        raise ValueError(f'{what} takes 1 .. {nv.MAX_MODELS_PER_CALL} models, not {S}')
+    for U, V in tables:
+        if not (torch.is_tensor(U) and U.is_cuda and V.is_cuda):
+            raise nv.NativeError(f'{what} runs on the HIP device only (no CPU fallback)')
+        assert U.is_contiguous() and V.is_contiguous() and U.dtype == torch.float32 and V.dtype == torch.float32
+        assert U.shape[1] == d and V.shape[1] == d and U.shape[0] == tables[0][0].shape[0] and V.shape[0] == tables[0][1].shape[0]
+    return (ctypes.c_void_p * S)(*[U.data_ptr() for U, _ in tables]), (ctypes.c_void_p * S)(*[V.data_ptr() for _, V in tables]), S
+
+
+def _link_code(link):
+    from .combine import link_code
+    if isinstance(link, (int, np.integer)) and not isinstance(link, bool) and int(link) in (0, 1):
+        return int(link)
+    return link_code(link)
+
+
+class PairSet:
+    """Training pairs (uid int32, iid int32, rating float32 = rating / 5) resident on the device: a fit uploads them once
+    and makes every Newton pass over the same tensors."""
+
+    def __init__(self, uid, iid, rating, device=None):
+        uid = np.ascontiguousarray(uid, dtype=np.int32)
+        iid = np.ascontiguousarray(iid, dtype=np.int32)
+        rating = np.ascontiguousarray(rating, dtype=np.float32)
+        if not len(uid) == len(iid) == len(rating):
+            raise ValueError('uid, iid and rating differ in length')
+        self.n = len(uid)
+        if self.n and (uid.min() < 0 or iid.min() < 0):
+            raise ValueError('negative user or item id')
+        self.max_uid, self.max_iid = (int(uid.max()), int(iid.max())) if self.n else (-1, -1)
+        self.device = device or _device()
+        self.uid, self.iid, self.rating = upload_many([uid, iid, rating], self.device) if self.n else (None, None, None)
+
+    @classmethod
+    def from_device(cls, uid, iid, rating):
+        """Pairs that are on the device already (int32, int32, float32 tensors); the id range is read back once."""
+        ps = cls.__new__(cls)
+        ps.uid, ps.iid, ps.rating = uid.contiguous(), iid.contiguous(), rating.contiguous()
+        assert ps.uid.dtype == torch.int32 and ps.iid.dtype == torch.int32 and ps.rating.dtype == torch.float32
+        ps.n, ps.device = int(uid.numel()), uid.device
+        if not ps.n == ps.iid.numel() == ps.rating.numel():
+            raise ValueError('uid, iid and rating differ in length')
+        if ps.n and (int(ps.uid.min()) < 0 or int(ps.iid.min()) < 0):
+            raise ValueError('negative user or item id')
+        ps.max_uid, ps.max_iid = (int(ps.uid.max()), int(ps.iid.max())) if ps.n else (-1, -1)
+        return ps
+
+
+def combine_stats(tables, d, pairs, link, w, stream=None, as_tensor=False):
+    """One pass of ure_combine_stats: the float64 stats vector (n, loss, g, upper triangle of H: combine.unpack_stats) of
+    `pairs` (a PairSet, or a (uid, iid, rating) triple that is uploaded for this call) at the weights w (S + 1 float64, host
+    or device) for the padded device tables [(U, V)].  Returns a numpy vector (synchronises), or the device tensor."""
+    code = _link_code(link)
+    Up, Vp, S = _table_ptrs(tables, d, 'combine_stats')
+    if not isinstance(pairs, PairSet):
+        pairs = PairSet(*pairs, device=tables[0][0].device)
+    if pairs.n < 1:
+        raise ValueError('combine_stats needs at least one pair')
+    if pairs.max_uid >= tables[0][0].shape[0] or pairs.max_iid >= tables[0][1].shape[0]:
+        raise ValueError(f'pair ids up to ({pairs.max_uid}, {pairs.max_iid}) outside the tables {tuple(tables[0][0].shape)}, {tuple(tables[0][1].shape)}')
+    dev = pairs.device
+    if not torch.is_tensor(w):
+        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
+    if w.dtype != torch.float64 or w.numel() != S + 1 or not w.is_cuda:
+        raise ValueError(f'w must hold {S + 1} float64 values on the device')
+    L = nv.lib()
+    nbytes = int(L.ure_combine_stats_scratch(pairs.n, S))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    combine_stats.last_scratch_bytes = nbytes
+    out = torch.empty(int(L.ure_combine_stats_len(S)), dtype=torch.float64, device=dev)
+    nv.check(L.ure_combine_stats(Up, Vp, S, nv.ptr(pairs.uid), nv.ptr(pairs.iid), nv.ptr(pairs.rating), pairs.n, d, code, nv.ptr(w.contiguous()),
+                                 nv.ptr(out), nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_combine_stats')
+    if as_tensor:
+        return out
+    if stream is not None:
+        stream.synchronize()
+    return out.cpu().numpy()
+
+
+def score_weighted(tables, d, uid, iid, rating, link, W, group_of_user=None, pred=None, sse=None, stream=None):
+    """ure_score_weighted on device pairs (uid, iid int32; rating float32, needed for sse): pred[j] = (float)link(b + sum_s
+    w[s] p[j, s]) with the row W[group_of_user[uid[j]]] of W (device float64 [G, S + 1]; row 0 without a map), and the
+    squared-error partials ure_eval_reduce takes.  -> (pred float32 [n], sse float64 [SCORE_PARTIALS]); nothing synchronises."""
+    code = _link_code(link)
+    Up, Vp, S = _table_ptrs(tables, d, 'score_weighted')
+    dev = tables[0][0].device
+    n = int(uid.numel())
+    if n < 1:
+        raise ValueError('score_weighted needs at least one pair')
+    if not (torch.is_tensor(W) and W.is_cuda and W.dtype == torch.float64 and W.dim() == 2 and W.shape[1] == S + 1 and W.shape[0] >= 1):
+        raise ValueError(f'W must be a device float64 [G, {S + 1}] tensor')
+    for t, dt, name in ((uid, torch.int32, 'uid'), (iid, torch.int32, 'iid'), (rating, torch.float32, 'rating'), (group_of_user, torch.int32, 'group_of_user')):
+        if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise ValueError(f'{name} must be a contiguous device {dt} tensor')
+    if iid.numel() != n or (rating is not None and rating.numel() != n):
+        raise ValueError('uid, iid and rating differ in length')
+    if group_of_user is not None and group_of_user.numel() < 1:
+        raise ValueError('an empty group map')
+    if pred is None:
+        pred = torch.empty(n, dtype=torch.float32, device=dev)
+    if sse is None and rating is not None:
+        sse = torch.empty(SCORE_PARTIALS, dtype=torch.float64, device=dev)
+    assert pred.dtype == torch.float32 and pred.numel() >= n and pred.is_contiguous()
+    assert sse is None or (sse.dtype == torch.float64 and sse.numel() >= SCORE_PARTIALS and sse.is_contiguous())
+    nv.check(nv.lib().ure_score_weighted(Up, Vp, S, nv.ptr(uid), nv.ptr(iid), nv.ptr(rating), n, d, code, nv.ptr(W.contiguous()), int(W.shape[0]),
+                                         nv.ptr(group_of_user), int(group_of_user.numel()) if group_of_user is not None else 0,
+                                         nv.ptr(pred), nv.ptr(sse), nv.stream_handle(stream)), 'ure_score_weighted')
+    return pred, sse

@@ -22,7 +22,7 @@ from torch import nn
 from .. import engine
 from ..read import as_loader
 from .scratch import PERM_THREADS, Scratch, prepare_shard, snapshot_limit
-from .utils import MF, baseTest, padded_tables, rank_eval, recommend, seed_all
+from .utils import MF, baseTest, fit_combiner, padded_tables, rank_eval, recommend, seed_all
 
 
 
@@ -199,6 +199,7 @@ class Sisa(Scratch):
         self.parallel = bool(getattr(param, 'parallel', False))
         self.epoch_logs = bool(getattr(param, 'epoch_logs', True))   # parallel mode: rebuild the per-epoch test logs
         self.model_list = []
+        self.combiner = None
 
     def test(self, test_data, verbose, save_dir):
         dist = _dist()
@@ -215,6 +216,32 @@ class Sisa(Scratch):
         if len(save_dir) > 0:
             np.save(save_dir + '/log0', log)
         self.log0 = log
+
+    def fit_combiner(self, train_dlist, link='linear', l2=0.0, per_group=True):
+        """Fit the weights that combine the shard models (utils.fit_combiner over self.model_list) on the CURRENT training
+        loaders and keep them in self.combiner.  per_group: one weight row per shard's user group (loader g holds group g's
+        pairs, as learn takes them), else one row for all.  learn and unlearn drop the combiner: its weights were fitted on
+        ratings a deletion removes, so it is refitted on the post-deletion train_dlist.  Every rank of a parallel run holds
+        the merged models and fits its own (bitwise the same)."""
+        from ..combine import check_fit_args
+        check_fit_args(link, l2, 25, 1e-10)
+        if len(train_dlist) != self.n_group:
+            raise ValueError(f'{len(train_dlist)} training loaders for {self.n_group} groups')
+        if not self.model_list:
+            raise ValueError('fit_combiner needs trained models: call learn first')
+        self.combiner = fit_combiner(self.model_list, list(train_dlist), link, l2, groups=self.group_index if per_group else None)
+        return self.combiner
+
+    def test_combined(self, test_data, verbose, save_dir):
+        """Sisa.test with the fitted weights: (rmse, ndcg, hr), kept in self.log0c and saved as log0c.npy beside log0.npy.
+        Sisa.test and log0 stay the mean's."""
+        if getattr(self, 'combiner', None) is None:
+            raise ValueError('no combiner: call fit_combiner after learn / unlearn (a deletion drops the fitted weights)')
+        rmse, ndcg, hr = baseTest(test_data, self.model_list, nn.MSELoss(reduction='sum'), self.device, verbose, combiner=self.combiner)
+        self.log0c = {'total_rmse': rmse, 'total_ndcg': ndcg, 'total_hr': hr}
+        if len(save_dir) > 0:
+            np.save(save_dir + '/log0c', self.log0c)
+        return rmse, ndcg, hr
 
     # ------------------------------------------------------------------ helpers
     def _rows_dev(self, i):
@@ -438,6 +465,7 @@ class Sisa(Scratch):
         '''
         train_dlist:   list of dataloader[n_group]
         '''
+        self.combiner = None            # fitted on the models this call replaces
         assert len(train_dlist) == self.n_group
         assert len(test_dlist) == self.n_group
 
@@ -476,6 +504,7 @@ class Sisa(Scratch):
         '''
         train_dlist:   list of dataloader[n_group]
         '''
+        self.combiner = None            # fitted on the deleted users' ratings: refit on the post-deletion loaders
         self.model_list = model_list
 
         assert len(train_dlist) == self.n_group

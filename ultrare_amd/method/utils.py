@@ -4,6 +4,7 @@ the reference), backed by the HIP engine.
   seed_all     utils.py:21-25
   MF           utils.py:30-43    two embedding tables; forward = row-wise dot
   baseTest     utils.py:115-187  ensemble mean score, RMSE, HR@10, NDCG@10
+  fit_combiner (new)             fitted weights of the shard scores in place of their mean (baseTest(..., combiner=))
   recommend    (new)             top-k items over the whole catalogue from the same ensemble mean
   rank_eval    (new)             full-ranking HR@K / Recall@K / NDCG@K / MRR of the test pairs (rank_metrics: the reduction)
   computeNDCG / computeDCG  utils.py:190-210
@@ -30,6 +31,7 @@ from torch import nn
 
 from .. import _native as nv
 from .. import engine
+from ..combine import Combiner, check_fit_args, first_group_map, mean_weights, newton_fit
 from ..read import as_loader
 from ..rng import seed_all  # noqa: F401  (re-exported under the reference's name)
 
@@ -100,16 +102,65 @@ def padded_tables(model):
     return fix(U), fix(V), d
 
 
-def baseTest(dataloader, models, loss_fn=None, device=None, verbose=0, top_k=10):
+def baseTest(dataloader, models, loss_fn=None, device=None, verbose=0, top_k=10, combiner=None):
     """utils.py:115-187: (rmse, ndcg, hr) of the mean-ensemble of `models` on a test
-    loader.  loss_fn / device are accepted for signature compatibility."""
+    loader.  loss_fn / device are accepted for signature compatibility.  combiner (fit_combiner's result, optional): the
+    pairs are scored with its fitted weights instead of the mean; without one nothing changes."""
     ev = as_loader(dataloader).eval_set()
     tabs = [padded_tables(m) for m in models]
     d = tabs[0][2]
-    rmse, ndcg, hr = ev.evaluate([(U, V) for U, V, _ in tabs], d, top_k=top_k)
+    if combiner is None:
+        rmse, ndcg, hr = ev.evaluate([(U, V) for U, V, _ in tabs], d, top_k=top_k)
+    else:
+        rmse, ndcg, hr = ev.evaluate([(U, V) for U, V, _ in tabs], d, top_k=top_k, combiner=combiner)
     if verbose == 2:
         print(f'Test - RMSE: {rmse:>.4f}, NDCG: {ndcg:>.3f}, HR: {hr:>.3f}')
     return rmse, ndcg, hr
+
+
+def fit_combiner(models, train_data, link='linear', l2=0.0, groups=None, max_iter=25, tol=1e-10):
+    """Fit the weights that combine the scores of `models` (the learned third stage of SISA) on training pairs.
+    For a pair, z = b + sum_s w[s] * score_s; link='linear' predicts z and minimises the squared error, link='logistic'
+    predicts sigmoid(z) and minimises the cross-entropy against the rating / 5; plus (l2 / 2) |w - 1/S|^2, which pulls towards
+    the mean ensemble.  train_data: one loader or a list of loaders (as Sisa's train_dlist).  groups (index lists, as
+    Group.grouping returns): one independent fit per group -- with a list of loaders, loader g holds group g's pairs (their
+    numbers must agree); with one loader, its pairs are split by the first group that lists the user and the pairs of users in
+    no group are left out.  Without groups: one fit over all pairs.  A group without pairs keeps the mean's weights.
+    Each Newton pass is one launch over pairs that went to the device once (engine.combine_stats); the solve of at most 33
+    unknowns runs on the host.  Returns a Combiner for baseTest(..., combiner=); ValueError for bad settings (before any device
+    work) and for a singular system (naming l2)."""
+    check_fit_args(link, l2, max_iter, tol)
+    S = len(models)
+    if not 1 <= S <= nv.MAX_MODELS_PER_CALL:
+        raise ValueError(f'fit_combiner takes 1 .. {nv.MAX_MODELS_PER_CALL} models, not {S}')
+    many = isinstance(train_data, (list, tuple))
+    loaders = [as_loader(l) for l in (train_data if many else [train_data])]
+    if not loaders:
+        raise ValueError('fit_combiner needs training data')
+    if groups is not None and many and len(groups) != len(loaders):
+        raise ValueError(f'{len(groups)} groups for {len(loaders)} loaders: with a list of loaders, loader g holds the pairs of group g')
+    triples = [l.dataset.triples() for l in loaders]
+    if groups is not None and not many:
+        uid, iid, r = triples[0]
+        n_ids = max(int(uid.max()) + 1 if len(uid) else 0, 1 + max((int(max(g)) for g in groups if len(g)), default=0))
+        of = first_group_map(groups, n_ids)[uid]
+        triples = [(uid[of == g], iid[of == g], r[of == g]) for g in range(len(groups))]
+    tabs = [padded_tables(m) for m in models]
+    tables, d = [(U, V) for U, V, _ in tabs], tabs[0][2]
+    dev = tables[0][0].device
+    sets = [engine.PairSet(*t, device=dev) for t in triples]           # on the device once per fit, not once per pass
+    per_set = lambda theta: [engine.combine_stats(tables, d, ps, link, theta) for ps in sets if ps.n]
+    if groups is None:
+        if not any(ps.n for ps in sets):
+            raise ValueError('fit_combiner needs at least one training pair')
+        # the loaders' stats vectors added in index order: one solve, no second pass over the data
+        fits = [newton_fit(lambda theta: np.sum(per_set(theta), axis=0) if len(sets) > 1 else per_set(theta)[0], S, link, l2, max_iter, tol)]
+    else:
+        empty = {'theta': mean_weights(S), 'n': 0, 'iters': 0, 'loss_before': 0.0, 'loss_after': 0.0, 'grad_norm': 0.0}
+        fits = [newton_fit(lambda theta, ps=ps: engine.combine_stats(tables, d, ps, link, theta), S, link, l2, max_iter, tol) if ps.n else empty
+                for ps in sets]
+    return Combiner(np.stack([f['theta'] for f in fits]), link, None if groups is None else [list(g) for g in groups],
+                    **{key: [f[key] for f in fits] for key in ('n', 'iters', 'loss_before', 'loss_after', 'grad_norm')})
 
 
 def recommend(models, users, top_k=10, exclude=None):

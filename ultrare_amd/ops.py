@@ -19,6 +19,10 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.ot_sinkhorn(dist, reg, num_iter_max, stop_thr)
                                                         (new)             log-domain Sinkhorn on a [k, n] cost matrix ->
                                                                           (label, u, v, err, iters)
+    torch.ops.ultrare.combine_stats(Us, Vs, uid, iid, rating, link, w)
+                                                        (new)             the combiner fit's float64 stats vector of a pair set
+    torch.ops.ultrare.score_weighted(Us, Vs, uid, iid, rating, link, W, group_of_user)
+                                                        (new)             (pred, sse partials) with fitted weight rows
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -156,3 +160,37 @@ def ot_sinkhorn(dist: torch.Tensor, reg: float, num_iter_max: int, stop_thr: flo
 def _(dist, reg, num_iter_max, stop_thr):
     k, n = dist.shape
     return (dist.new_empty(n, dtype=torch.int32), dist.new_empty(n, dtype=torch.float64), dist.new_empty(k, dtype=torch.float64), 0.0, 0)
+
+
+def _pairs(uid, iid, rating):
+    return uid.to(torch.int32).contiguous(), iid.to(torch.int32).contiguous(), rating.to(torch.float32).contiguous()
+
+
+@torch.library.custom_op('ultrare::combine_stats', mutates_args=())
+def combine_stats(Us: List[torch.Tensor], Vs: List[torch.Tensor], uid: torch.Tensor, iid: torch.Tensor, rating: torch.Tensor, link: int,
+                  w: torch.Tensor) -> torch.Tensor:
+    _dev(*Us, *Vs, uid, iid, rating, w)
+    assert len(Us) == len(Vs)
+    pairs = engine.PairSet.from_device(*_pairs(uid, iid, rating))
+    return engine.combine_stats(list(zip(Us, Vs)), Us[0].shape[1], pairs, link, w.to(torch.float64).contiguous(), as_tensor=True)
+
+
+@combine_stats.register_fake
+def _(Us, Vs, uid, iid, rating, link, w):
+    S = len(Us)
+    return w.new_empty(2 + (S + 1) + (S + 1) * (S + 2) // 2, dtype=torch.float64)
+
+
+@torch.library.custom_op('ultrare::score_weighted', mutates_args=())
+def score_weighted(Us: List[torch.Tensor], Vs: List[torch.Tensor], uid: torch.Tensor, iid: torch.Tensor, rating: torch.Tensor, link: int,
+                   W: torch.Tensor, group_of_user: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(*Us, *Vs, uid, iid, rating, W, *([group_of_user] if group_of_user is not None else []))
+    assert len(Us) == len(Vs)
+    uid, iid, rating = _pairs(uid, iid, rating)
+    gou = None if group_of_user is None else group_of_user.to(torch.int32).contiguous()
+    return engine.score_weighted(list(zip(Us, Vs)), Us[0].shape[1], uid, iid, rating, link, W.to(torch.float64).contiguous(), gou)
+
+
+@score_weighted.register_fake
+def _(Us, Vs, uid, iid, rating, link, W, group_of_user):
+    return Us[0].new_empty(uid.numel()), Us[0].new_empty(engine.SCORE_PARTIALS, dtype=torch.float64)
