@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define URE_ABI_VERSION 14
+#define URE_ABI_VERSION 15
 #define URE_MAX_MODELS_PER_CALL 32
 #define URE_SCORE_PARTIALS 2048       /* length of ure_score's sse buffer */
 
@@ -603,6 +603,27 @@ int ure_combine_stats(const float *const *U_tables, const float *const *V_tables
 int ure_score_weighted(const float *const *U_tables, const float *const *V_tables, int n_models, const int32_t *uid, const int32_t *iid,
                        const float *rating, int64_t n, int d, int link, const double *W, int n_groups, const int32_t *group_of_user,
                        int32_t n_user, float *pred, double *sse, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Batched ridge solves (ABI 15; csrc/mf_ridge.hip): fold-in of new users and the half sweeps of ALS.  Opt-in, non-parity:
+ * the reference has no fold-in.
+ * ------------------------------------------------------------------------- */
+/* F (device, [n_fixed][d] fp32, d the padded stride) is a FIXED table; off [m + 1] int64, idx [nnz] int32, val [nnz] fp32
+ * (rating / 5) are a device CSR of m segments.  For segment s with entries j = off[s] .. off[s + 1] - 1 (n_s of them), all in
+ * float64: f_j = F[idx[j]][0:k], G = sum_j f_j f_j^T + (l2 + l2_n n_s) I, b = sum_j val[j] f_j, x = G^-1 b by Cholesky and
+ * two triangular solves; X[s][0:k] = (float)x, rounded once at the store, X[s][k:d] = 0 (X device, [m][d]).  An empty
+ * segment gives the zero row.  A pivot that is not positive and finite, an index outside [0, n_fixed) or a solution that is
+ * not finite fills X[s][0:k] with NaN and counts in status (device, int32 [2], cleared by the call): status[0] = failed
+ * segments, status[1] = the smallest failed segment index (-1: none).  order (device, int32 [m], optional): workgroup b
+ * takes segment order[b] -- the host passes the longest first; it changes no output byte.  1 <= k <= d, d a power of two in
+ * 4 .. 128 (the triangle of a padded 256 does not fit in LDS), 0 <= m < 2^31, l2 and l2_n finite and >= 0.
+ * ure_ridge_rows_scratch(m, k) = 0 bytes (G never leaves the chip; -1 for m < 0 or k outside 1 .. 128); scratch may be NULL.
+ * No floating-point atomics and no sum across workgroups: a row's bytes depend on its own segment alone, on any stream, in
+ * any order, whatever other segments share the call.  Nothing synchronises. */
+int64_t ure_ridge_rows_scratch(int64_t m, int k);
+int ure_ridge_rows(const float *F, int64_t n_fixed, int d, int k, const int64_t *off, const int32_t *idx, const float *val, int64_t m,
+                   const int32_t *order, double l2, double l2_n, float *X, int32_t *status, void *scratch, int64_t scratch_bytes,
+                   void *stream);
 
 /* ---------------------------------------------------------------------------
  * Comparison clusterers (utils.py:354-418: k-means / balanced k-means on the user embedding;

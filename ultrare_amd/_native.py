@@ -11,7 +11,7 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'libultrare_hip.so')
-ABI_VERSION = 14
+ABI_VERSION = 15
 MAX_MODELS_PER_CALL = 32
 
 _vp = ctypes.c_void_p
@@ -138,6 +138,9 @@ _PROTOTYPES = {
                                          _vp, _vp, _vp, _i64, _vp]),
     'ure_score_weighted': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int,
                                           _vp, ctypes.c_int, _vp, _i32, _vp, _vp, _vp]),
+    'ure_ridge_rows_scratch': (_i64, [_i64, ctypes.c_int]),
+    'ure_ridge_rows': (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _vp, ctypes.c_double, ctypes.c_double,
+                                      _vp, _vp, _vp, _i64, _vp]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

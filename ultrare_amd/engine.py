@@ -1448,3 +1448,85 @@ def score_weighted(tables, d, uid, iid, rating, link, W, group_of_user=None, pre
                                          nv.ptr(group_of_user), int(group_of_user.numel()) if group_of_user is not None else 0,
                                          nv.ptr(pred), nv.ptr(sse), nv.stream_handle(stream)), 'ure_score_weighted')
     return pred, sse
+
+
+# ---------------------------------------------------------------------------
+# Batched ridge solves (csrc/mf_ridge.hip; the contract and the CSR builder are ridge.py)
+# ---------------------------------------------------------------------------
+class SegmentSet:
+    """A CSR of rating entries grouped by segment, resident on the device: segment s (a user, or an item) holds the ids of
+    the fixed table's rows it rated and the ratings / 5, in the order given (a stable sort on the host).  The counterpart of
+    PairSet for ridge_rows; `order` lists the segments longest first."""
+
+    def __init__(self, seg_ids, other_ids, rating, n_seg, device=None):
+        from .ridge import segment_csr
+        off, idx, val, order = segment_csr(seg_ids, other_ids, rating, n_seg)
+        self.m, self.nnz = int(n_seg), len(idx)
+        self.max_other = int(idx.max()) if self.nnz else -1
+        self.counts = np.diff(off)
+        self.device = device or _device()
+        self.off, self.order = upload_many([off, order], self.device)
+        # (a kernel argument must not be NULL: an empty set keeps one unused entry)
+        self.idx, self.val = upload_many([idx if self.nnz else np.zeros(1, np.int32), val if self.nnz else np.zeros(1, np.float32)], self.device)
+
+    @classmethod
+    def from_device(cls, off, idx, val):
+        """A CSR that is on the device already (int64 [m + 1], int32, float32 tensors); no `order`.  The offsets and the id
+        range are read back once."""
+        ss = cls.__new__(cls)
+        assert off.dtype == torch.int64 and idx.dtype == torch.int32 and val.dtype == torch.float32
+        host = off.cpu().numpy()
+        ss.m, ss.nnz = len(host) - 1, int(idx.numel())
+        if ss.m < 0 or host[0] != 0 or host[-1] != ss.nnz or (np.diff(host) < 0).any() or val.numel() != ss.nnz:
+            raise ValueError('off must rise from 0 to the number of entries')
+        if ss.nnz and int(idx.min()) < 0:
+            raise ValueError('negative id')
+        ss.max_other = int(idx.max()) if ss.nnz else -1
+        ss.counts, ss.device, ss.order = np.diff(host), off.device, None
+        ss.off = off.contiguous()
+        ss.idx = idx.contiguous() if ss.nnz else torch.zeros(1, dtype=torch.int32, device=off.device)
+        ss.val = val.contiguous() if ss.nnz else torch.zeros(1, dtype=torch.float32, device=off.device)
+        return ss
+
+
+def ridge_rows(F, d, k, segs, l2, l2_n=0.0, stream=None, order='longest'):
+    """ure_ridge_rows: X [m, d] float32, row s the ridge solution of segment s of `segs` (a SegmentSet) against the first k
+    columns of the fixed device table F [n_fixed, d] at strength l2 + l2_n * n_s; columns k .. d - 1 are zero.  order:
+    'longest' (the set's own longest-first list), None (index order) or an int32 list of segments; it changes no byte.  Reads
+    the status words back (synchronises) and raises ValueError naming l2 and the first failing segment when a system was not
+    positive definite; the exception carries X (the failed rows NaN), `failed` and `segment`."""
+    from .ridge import MAX_D, check_ridge_args
+    l2, l2_n = check_ridge_args(l2, l2_n)
+    if d > MAX_D:
+        raise ValueError(f'ridge_rows serves padded widths up to {MAX_D}: the float64 triangle of width {d} does not fit in LDS')
+    if not 1 <= k <= d or d != pad_dim(d):
+        raise ValueError(f'need 1 <= k <= d with d a padded width, not k = {k}, d = {d}')
+    if not (torch.is_tensor(F) and F.is_cuda):
+        raise nv.NativeError('ridge_rows runs on the HIP device only (no CPU fallback)')
+    if not (F.dtype == torch.float32 and F.dim() == 2 and F.shape[1] == d and F.is_contiguous() and F.shape[0] >= 1):
+        raise ValueError(f'F must be a contiguous float32 [n, {d}] tensor')
+    if segs.max_other >= F.shape[0]:
+        raise ValueError(f'ids up to {segs.max_other} outside the fixed table of {F.shape[0]} rows')
+    dev = F.device
+    if isinstance(order, str):
+        if order != 'longest':
+            raise ValueError(f"order must be 'longest', None or a list of segments, not {order!r}")
+        order = segs.order
+    elif order is not None and not torch.is_tensor(order):
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.shape != (segs.m,) or (np.sort(order) != np.arange(segs.m)).any():
+            raise ValueError('order must list every segment once')
+        order = torch.from_numpy(order).to(dev)
+    X = torch.empty(segs.m, d, dtype=torch.float32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_ridge_rows(nv.ptr(F), int(F.shape[0]), d, k, nv.ptr(segs.off), nv.ptr(segs.idx), nv.ptr(segs.val), segs.m, nv.ptr(order),
+                                     l2, l2_n, nv.ptr(X), nv.ptr(status), None, 0, nv.stream_handle(stream)), 'ure_ridge_rows')
+    if stream is not None:
+        stream.synchronize()
+    failed, first = (int(v) for v in status.cpu().numpy())
+    if failed:
+        err = ValueError(f'ridge_rows: {failed} of {segs.m} systems are not positive definite, first segment {first} '
+                         f'({int(segs.counts[first])} entries, width {k}) at l2 = {l2:g}, l2_n = {l2_n:g}: a larger l2 makes them definite')
+        err.X, err.failed, err.segment = X, failed, first
+        raise err
+    return X

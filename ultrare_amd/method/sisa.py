@@ -22,6 +22,7 @@ from torch import nn
 from .. import engine
 from ..read import as_loader
 from .scratch import PERM_THREADS, Scratch, prepare_shard, snapshot_limit
+from . import utils
 from .utils import MF, baseTest, fit_combiner, padded_tables, rank_eval, recommend, seed_all
 
 
@@ -200,6 +201,7 @@ class Sisa(Scratch):
         self.epoch_logs = bool(getattr(param, 'epoch_logs', True))   # parallel mode: rebuild the per-epoch test logs
         self.model_list = []
         self.combiner = None
+        self.folded = {}                # user -> group of the users fold_in added since the last learn
 
     def test(self, test_data, verbose, save_dir):
         dist = _dist()
@@ -466,6 +468,7 @@ class Sisa(Scratch):
         train_dlist:   list of dataloader[n_group]
         '''
         self.combiner = None            # fitted on the models this call replaces
+        self.folded = {}                # the folded rows are replaced with the tables
         assert len(train_dlist) == self.n_group
         assert len(test_dlist) == self.n_group
 
@@ -488,6 +491,111 @@ class Sisa(Scratch):
         engine.mark('tested')
         return self.model_list
 
+    # ------------------------------------------------------------------ fold-in
+    def _merged_table(self):
+        """The one merged user table, with every model pointed at it (models handed to unlearn may be copies)."""
+        merged = self.model_list[0].user_mat.weight.detach()
+        if not merged.is_contiguous():
+            merged = merged.contiguous()
+        for m in self.model_list:
+            if m.user_mat.weight.data_ptr() != merged.data_ptr():
+                m.user_mat.weight = nn.Parameter(merged, requires_grad=False)
+        return merged
+
+    def _set_rows(self, users, rows=None):
+        """merged[users] = rows (zero without rows) through engine.merge_rows."""
+        merged = self._merged_table()
+        at = engine.to_device_async(np.asarray(users, dtype=np.int64), merged.device)
+        src = torch.zeros_like(merged)
+        if rows is not None:
+            src.index_copy_(0, at, rows)
+        engine.merge_rows(merged, src, at)
+
+    def fold_in(self, data, l2, groups=None, l2_n=0.0, against='home'):
+        """Add the users of `data` (a loader, or a (uid, iid, rating / 5) triple) between retrainings, without training: each
+        gets the ridge row of its ratings against frozen item tables (utils.fold_in; utils.trainer_l2 gives the l2 of the
+        trainer's own fixed point).  groups: one group id per distinct user, in ascending user id; None sends each user, in
+        ascending id, to the currently smallest group (lowest id on ties), which keeps the balance the grouping bought.
+        against='home': the item table of the user's group -- how every trained user's row came to be, so the row behaves like
+        its neighbours under the mean and under any combiner; 'ensemble': the mean item table, which minimises the error of the
+        score actually served.  The rows go into the merged user table all models share, the users are appended to
+        group_index[g] and recorded in self.folded[user] = g, and a fitted combiner is dropped (its group lists no longer cover
+        the users).  A user that a group already lists, or with an id >= n_user (the tables do not grow), is refused with
+        ValueError before any device work.  Returns (users ascending int64, their groups int64).  forget_folded deletes them
+        exactly."""
+        from ..ridge import check_ridge_args
+        check_ridge_args(l2, l2_n)
+        if against not in ('home', 'ensemble'):
+            raise ValueError(f"against must be 'home' or 'ensemble', not {against!r}")
+        if not self.model_list:
+            raise ValueError('fold_in needs trained models: call learn first')
+        uid, iid, r = utils._rating_triple(data)
+        users = np.unique(uid)
+        if len(users) == 0:
+            raise ValueError('fold_in needs at least one rating')
+        if users[0] < 0 or users[-1] >= self.n_user:
+            raise ValueError(f'users {users[(users < 0) | (users >= self.n_user)].tolist()} outside [0, {self.n_user}): the tables do not grow')
+        if len(iid) and (iid.min() < 0 or iid.max() >= self.n_item):
+            raise ValueError(f'items outside [0, {self.n_item})')
+        listed = np.zeros(self.n_user, dtype=bool)
+        for g in self.group_index:
+            ids = np.asarray(g, dtype=np.int64)
+            listed[ids[(ids >= 0) & (ids < self.n_user)]] = True
+        if listed[users].any():
+            raise ValueError(f'users {users[listed[users]].tolist()} are already in a group: unlearn them first')
+        if groups is None:
+            sizes = [len(g) for g in self.group_index]
+            home = np.empty(len(users), dtype=np.int64)
+            for q in range(len(users)):
+                g = min(range(self.n_group), key=lambda c: (sizes[c], c))
+                home[q] = g
+                sizes[g] += 1
+        else:
+            home = np.asarray(groups).reshape(-1)
+            if len(home) != len(users):
+                raise ValueError(f'{len(home)} group ids for {len(users)} distinct users')
+            if not np.issubdtype(home.dtype, np.integer) or (home < 0).any() or (home >= self.n_group).any():
+                raise ValueError(f'group ids must be integers in 0 .. {self.n_group - 1}')
+            home = home.astype(np.int64)
+        # ---- device work
+        if against == 'ensemble':
+            got, rows = utils.fold_in(self.model_list, (uid, iid, r), l2, l2_n, 'mean')
+            assert np.array_equal(got, users)
+            self._set_rows(users, rows)
+        else:
+            of_user = np.full(self.n_user, -1, dtype=np.int64)
+            of_user[users] = home
+            for g in np.unique(home):
+                pick = of_user[uid] == g
+                got, rows = utils.fold_in(self.model_list, (uid[pick], iid[pick], r[pick]), l2, l2_n, int(g))
+                self._set_rows(got, rows)
+        for g in np.unique(home):
+            self.group_index[g] = list(self.group_index[g]) + users[home == g].tolist()
+        self.forget_rows()
+        self.folded.update({int(u): int(g) for u, g in zip(users, home)})
+        self.combiner = None
+        return users, home
+
+    def forget_folded(self, users):
+        """Exact deletion of users that fold_in added, without retraining: a folded row depends on nothing but frozen item
+        tables and the user's own ratings, and no other parameter depends on it.  Zeroes their rows, removes them from their
+        group's list and from self.folded, and drops a fitted combiner.  ValueError (before any change) when some user was not
+        folded in, listing those that need unlearn."""
+        users = np.unique(np.asarray(list(users), dtype=np.int64).reshape(-1))
+        trained = [int(u) for u in users if int(u) not in self.folded]
+        if trained:
+            raise ValueError(f'users {trained} were not folded in: deleting them needs unlearn')
+        if len(users) == 0:
+            return
+        self._set_rows(users)
+        gone = set(users.tolist())
+        for g in sorted({self.folded[int(u)] for u in users}):
+            self.group_index[g] = [u for u in self.group_index[g] if int(u) not in gone]
+        for u in users:
+            del self.folded[int(u)]
+        self.forget_rows()
+        self.combiner = None
+
     # ------------------------------------------------------------------ unlearn
     def recommend(self, users, top_k=10, exclude=None):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers
@@ -503,6 +611,10 @@ class Sisa(Scratch):
     def unlearn(self, model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir):
         '''
         train_dlist:   list of dataloader[n_group]
+
+        A user that fold_in added is deleted exactly and without retraining by forget_folded.  Passed here, it retrains its
+        home shard like any other user; the folded users of every retrained shard leave self.folded, since their rows now
+        come from that shard's training.
         '''
         self.combiner = None            # fitted on the deleted users' ratings: refit on the post-deletion loaders
         self.model_list = model_list
@@ -517,6 +629,7 @@ class Sisa(Scratch):
         users = np.asarray(list(del_user), dtype=np.int64).reshape(-1)
         users = users[(users >= 0) & (users < len(first_group))]
         retrain_gid = set(int(g) for g in np.unique(first_group[users]) if g >= 0)
+        self.folded = {u: g for u, g in getattr(self, 'folded', {}).items() if g not in retrain_gid}
 
         model_before_unlearn = model_list[0]
         merged = model_before_unlearn.user_mat.weight.detach().clone().contiguous()

@@ -7,6 +7,9 @@ the reference), backed by the HIP engine.
   fit_combiner (new)             fitted weights of the shard scores in place of their mean (baseTest(..., combiner=))
   recommend    (new)             top-k items over the whole catalogue from the same ensemble mean
   rank_eval    (new)             full-ranking HR@K / Recall@K / NDCG@K / MRR of the test pairs (rank_metrics: the reduction)
+  fold_in      (new)             rows for new users against frozen item tables (one batched ridge solve on the device)
+  als_sweeps   (new)             alternating least squares from a model's tables by the same solve
+  trainer_l2   (new)             the ridge strength at which fold_in gives the trainer's own fixed point
   computeNDCG / computeDCG  utils.py:190-210
   ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD; solver='sinkhorn': entropic OT on the device)
   kmeans       utils.py:354-418  (balanced) k-means, a comparison clusterer
@@ -161,6 +164,117 @@ def fit_combiner(models, train_data, link='linear', l2=0.0, groups=None, max_ite
                 for ps in sets]
     return Combiner(np.stack([f['theta'] for f in fits]), link, None if groups is None else [list(g) for g in groups],
                     **{key: [f[key] for f in fits] for key in ('n', 'iters', 'loss_before', 'loss_after', 'grad_norm')})
+
+
+def trainer_l2(n_rows, batch, lam):
+    """The ridge strength l2 at which a ridge row (fold_in, als_sweeps) is the fixed point of the trainer for that row
+    under a frozen opposite table: lam * ceil(n_rows / batch) / 2, with n_rows the shard's ratings and batch its batch size.
+    Derivation.  The loss of a step is the SUM of the squared errors of its batch, so a rating j of row x with opposite row
+    v_j contributes the gradient 2 e_j v_j, e_j = x . v_j - r_j, once per epoch.  Weight decay adds lam * x to the gradient
+    of EVERY row at every optimizer step, ceil(n_rows / batch) times per epoch.  Summed over an epoch the drift of x is
+    2 sum_j e_j v_j + lam * ceil(n_rows / batch) * x, and it vanishes where
+        (sum_j v_j v_j^T + (lam * ceil(n_rows / batch) / 2) I) x = sum_j r_j v_j,
+    the ridge system of strength l2 = lam * ceil(n_rows / batch) / 2.  Momentum scales every gradient by the same
+    1 / (1 - mu) in the long run and does not move the fixed point; the learning rate and its decay do not enter either.
+    (With several steps per epoch the trainer cycles around this point with an amplitude of the order of the learning rate;
+    with one step per epoch it converges to it.)"""
+    n_rows, batch = int(n_rows), int(batch)
+    if n_rows < 0 or batch < 1:
+        raise ValueError(f'need n_rows >= 0 and batch >= 1, not {n_rows}, {batch}')
+    return float(lam) * (-(-n_rows // batch)) / 2.0
+
+
+def _rating_triple(data):
+    """(uid int64, iid int64, rating / 5 float32) of a loader (as baseTest accepts one) or of such a triple."""
+    if isinstance(data, (tuple, list)) and len(data) == 3:
+        uid, iid, r = (np.asarray(a).reshape(-1) for a in data)
+    else:
+        uid, iid, r = as_loader(data).dataset.triples()
+    if not len(uid) == len(iid) == len(r):
+        raise ValueError('uid, iid and rating differ in length')
+    return uid.astype(np.int64), iid.astype(np.int64), r.astype(np.float32)
+
+
+def _check_item_table(item_table, S):
+    if isinstance(item_table, str):
+        if item_table != 'mean':
+            raise ValueError(f"item_table must be a model index or 'mean', not {item_table!r}")
+    elif isinstance(item_table, bool) or not isinstance(item_table, (int, np.integer)) or not 0 <= int(item_table) < S:
+        raise ValueError(f"item_table must be a model index in 0 .. {S - 1} or 'mean', not {item_table!r}")
+
+
+def fold_in(models, data, l2, l2_n=0.0, item_table='mean'):
+    """Rows for the users of `data` with the item tables held fixed: user u's row is the ridge solution
+    (sum_j v_j v_j^T + (l2 + l2_n n_u) I)^-1 sum_j r_j v_j over u's n_u ratings, solved in float64 on the device
+    (engine.ridge_rows), one workgroup per user.  data: a loader as baseTest accepts one, or a (uid, iid, rating / 5) triple.
+    item_table: an int s -- against model s's item table -- or 'mean': the float64 mean of the S item tables rounded to float32
+    once (the table whose scores the mean ensemble serves, up to that rounding).  trainer_l2 gives the l2 of the trainer's own
+    fixed point.  Returns (users ascending int64, rows [n, k] float32 on the device).  ValueError for bad settings (before any
+    device work) and for a system that is not positive definite (naming l2)."""
+    from ..ridge import check_ridge_args
+    l2, l2_n = check_ridge_args(l2, l2_n)
+    S = len(models)
+    if S < 1:
+        raise ValueError('fold_in needs at least one model')
+    _check_item_table(item_table, S)
+    uid, iid, r = _rating_triple(data)
+    if len(uid) and (uid.min() < 0 or iid.min() < 0):
+        raise ValueError('negative user or item id')
+    users, seg = np.unique(uid, return_inverse=True)
+    if isinstance(item_table, str):
+        tabs = [padded_tables(m) for m in models]
+        d = tabs[0][2]
+        acc = tabs[0][1].double()
+        for _, V, _ in tabs[1:]:
+            acc = acc + V.double()
+        V = (acc / S).float().contiguous()
+    else:
+        _, V, d = padded_tables(models[int(item_table)])
+    k = int(models[0].k)
+    segs = engine.SegmentSet(seg, iid, r, len(users), device=V.device)
+    X = engine.ridge_rows(V, d, k, segs, l2, l2_n)
+    return users.astype(np.int64), X[:, :k].contiguous()
+
+
+def _ridge_objective_dev(U, V, k, pairs, reg_u, reg_v, chunk=1 << 20):
+    """sum e^2 + sum_rows reg_row |x|^2 in float64 on the device (a diagnostic of als_sweeps, not a hot path)."""
+    uid, iid, val = pairs
+    tot = torch.zeros((), dtype=torch.float64, device=U.device)
+    for a in range(0, uid.numel(), chunk):
+        u, i = uid[a:a + chunk].long(), iid[a:a + chunk].long()
+        e = (U[u, :k].double() * V[i, :k].double()).sum(dim=1) - val[a:a + chunk].double()
+        tot = tot + (e * e).sum()
+    tot = tot + (reg_u * (U[:, :k].double() ** 2).sum(dim=1)).sum() + (reg_v * (V[:, :k].double() ** 2).sum(dim=1)).sum()
+    return float(tot)
+
+
+def als_sweeps(model, train_data, l2, l2_n=0.0, sweeps=1):
+    """Alternating least squares from `model`'s tables on the device: each sweep solves every user row against V
+    (engine.ridge_rows over the users' segments), then every item row against the new U; a row without ratings becomes zero.
+    Returns (MF.from_tables(U, V), objectives): the float64 value of sum e^2 + sum_rows (l2 + l2_n n_row) |x|^2 (ratings as
+    the float32 rating / 5 the kernel reads) before the first and after every half sweep, 1 + 2 * sweeps numbers computed on
+    the device.  Each half sweep minimises the objective exactly over its block.  No RNG is drawn; opt-in, not wired into Sisa
+    or the CLI."""
+    from ..ridge import check_ridge_args
+    l2, l2_n = check_ridge_args(l2, l2_n)
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or sweeps < 0:
+        raise ValueError(f'sweeps must be an integer >= 0, not {sweeps!r}')
+    uid, iid, r = _rating_triple(train_data)
+    U, V, d = padded_tables(model)
+    k, dev = int(model.k), U.device
+    n_user, n_item = int(U.shape[0]), int(V.shape[0])
+    by_user = engine.SegmentSet(uid, iid, r, n_user, device=dev)
+    by_item = engine.SegmentSet(iid, uid, r, n_item, device=dev)
+    pairs = engine.upload_many([uid.astype(np.int32), iid.astype(np.int32), r], dev)
+    reg_u = torch.from_numpy(l2 + l2_n * by_user.counts.astype(np.float64)).to(dev)
+    reg_v = torch.from_numpy(l2 + l2_n * by_item.counts.astype(np.float64)).to(dev)
+    objectives = [_ridge_objective_dev(U, V, k, pairs, reg_u, reg_v)]
+    for _ in range(int(sweeps)):
+        U = engine.ridge_rows(V, d, k, by_user, l2, l2_n)
+        objectives.append(_ridge_objective_dev(U, V, k, pairs, reg_u, reg_v))
+        V = engine.ridge_rows(U, d, k, by_item, l2, l2_n)
+        objectives.append(_ridge_objective_dev(U, V, k, pairs, reg_u, reg_v))
+    return MF.from_tables(U[:, :k].clone().contiguous(), V[:, :k].clone().contiguous()), np.asarray(objectives, dtype=np.float64)
 
 
 def recommend(models, users, top_k=10, exclude=None):

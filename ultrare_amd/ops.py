@@ -23,6 +23,8 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         (new)             the combiner fit's float64 stats vector of a pair set
     torch.ops.ultrare.score_weighted(Us, Vs, uid, iid, rating, link, W, group_of_user)
                                                         (new)             (pred, sse partials) with fitted weight rows
+    torch.ops.ultrare.ridge_rows(F, off, idx, val, k, l2, l2_n)
+                                                        (new)             the ridge solution of every CSR segment against F
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -194,3 +196,15 @@ def score_weighted(Us: List[torch.Tensor], Vs: List[torch.Tensor], uid: torch.Te
 @score_weighted.register_fake
 def _(Us, Vs, uid, iid, rating, link, W, group_of_user):
     return Us[0].new_empty(uid.numel()), Us[0].new_empty(engine.SCORE_PARTIALS, dtype=torch.float64)
+
+
+@torch.library.custom_op('ultrare::ridge_rows', mutates_args=())
+def ridge_rows(F: torch.Tensor, off: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, k: int, l2: float, l2_n: float) -> torch.Tensor:
+    _dev(F, off, idx, val)
+    segs = engine.SegmentSet.from_device(off.to(torch.int64), idx.to(torch.int32), val.to(torch.float32))
+    return engine.ridge_rows(F, F.shape[1], k, segs, l2, l2_n)
+
+
+@ridge_rows.register_fake
+def _(F, off, idx, val, k, l2, l2_n):
+    return F.new_empty(off.numel() - 1, F.shape[1])
