@@ -97,6 +97,80 @@ def test_argument_errors_are_reported_not_crashed(lib):
         lib.check(L.ure_ot_assign(None, 0, 0, None, None, None), 'ure_ot_assign')
 
 
+# ure_job_create's refusals: every one is decided on the host before the first HIP call, so descriptors with made-up device
+# pointers reach them without a GPU.  Each case = the base descriptor plus the changes of its shards, and a part of the message.
+_SNAPSHOT_FIELDS = ('snapU', 'snapV', 'snap_a', 'snap', 'row_slot')
+_BASE = dict(N=100, n_user=8, n_item=8, d=16, batch=10, epochs=2, n_active=16, n_slots=256, n_units=0, lazy_rows=1, lam=0.1, mu=0.9)
+_PTR = 0x1000
+REFUSALS = [
+    ('d_differs', [{}, dict(d=32)], 'share d'),
+    ('steps_65534', [dict(N=70000, n_slots=70000, batch=1)], '70000 steps/epoch'),
+    ('n_multi', [dict(touch_mode=1, n_multi=-1)], 'n_multi outside'),
+    ('inv_stage', [dict(inv_stage=None)], 'lacks inv_stage'),
+    ('snapU_only', [dict(snapU=_PTR)], 'incomplete snapshot set'),
+    ('snap_without_snap_a', [dict(snap=_PTR)], 'incomplete snapshot set'),
+    ('modes_1_0', [dict(touch_mode=1), {}], 'shard 1: every shard of a job must ask for it'),
+    ('mode_4', [dict(touch_mode=4)], 'touch_mode is 0, 1, 2 or 3'),
+    ('modes_1_2', [dict(touch_mode=1), dict(touch_mode=2)], 'same touch mode'),
+    ('mode2_steps', [dict(touch_mode=2, batch=1)], 'at most 63 steps'),
+    ('mode2_full_snapshots', [dict(touch_mode=2, snapU=_PTR, snapV=_PTR, snap_a=_PTR)], 'compact snapshots only'),
+    ('mode2_row_slot', [dict(touch_mode=2, snap=_PTR, snap_a=_PTR)], 'needs row_slot'),
+    ('mode3_steps', [dict(touch_mode=3, N=2000, n_slots=2000, batch=1)], 'at most 1008 steps'),
+    ('mode3_n_split', [dict(touch_mode=3, n_multi=1, n_split=2)], 'n_split <= n_multi'),
+    ('mode3_batch', [dict(touch_mode=3, N=300000, n_slots=300000, batch=250000)], 'at most 200,000'),
+    ('mode1_lazy_rows', [dict(touch_mode=1, lazy_rows=0)], 'needs lazy_rows'),
+    ('mode1_steps', [dict(touch_mode=1, N=40000, n_slots=40000, batch=1)], 'more than 32000 steps'),
+    ('mode1_schedules', [dict(touch_mode=1), dict(touch_mode=1, lam=0.2)], 'schedules differ'),
+]
+
+
+def _fake_shards(lib, changes):
+    """The base descriptor once per entry of `changes` (+ that entry's fields); -> (array, the host arrays it points to)."""
+    arr = (lib.UreShard * len(changes))()
+    lr = (ctypes.c_float * _BASE['epochs'])(*([1e-3] * _BASE['epochs']))
+    for S, change in zip(arr, changes):
+        for name, typ in lib.UreShard._fields_:
+            if typ is ctypes.c_void_p and name not in _SNAPSHOT_FIELDS:
+                setattr(S, name, _PTR)
+        S.U[0] = S.U[1] = S.V[0] = S.V[1] = _PTR
+        S.lr_host = ctypes.cast(lr, ctypes.c_void_p)
+        for name, value in {**_BASE, **change}.items():
+            setattr(S, name, value)
+    return arr, lr
+
+
+def test_job_create_refuses_a_zeroed_descriptor_by_name(lib):
+    L = lib.lib()
+    out = ctypes.c_void_p()
+    assert L.ure_job_create((lib.UreShard * 1)(), 1, ctypes.byref(out)) != 0
+    assert b'shard 0 has an invalid descriptor' in L.ure_last_error()
+
+
+@pytest.mark.parametrize('changes,message', [c[1:] for c in REFUSALS], ids=[c[0] for c in REFUSALS])
+def test_job_create_refusal_table(lib, changes, message):
+    L = lib.lib()
+    out = ctypes.c_void_p()
+    arr, keep = _fake_shards(lib, changes)
+    assert L.ure_job_create(arr, len(changes), ctypes.byref(out)) != 0
+    err = L.ure_last_error().decode()
+    assert err.startswith('ure_job_create:') and message in err, err
+    assert not out.value
+
+
+def test_job_create_without_a_device_reports_the_hip_error(lib):
+    """The valid base descriptor passes every check; on a host without a device the first HIP call fails, and the half-made job
+    is taken apart the same way a refused one is."""
+    if torch.cuda.is_available():
+        pytest.skip('a device is visible: the made-up pointers must not reach it')
+    L = lib.lib()
+    out = ctypes.c_void_p()
+    for changes in ([{}], [dict(touch_mode=1)] * 2):
+        arr, keep = _fake_shards(lib, changes)
+        assert L.ure_job_create(arr, len(changes), ctypes.byref(out)) != 0
+        assert L.ure_last_error().decode().startswith('ure_job_create:')
+        assert not out.value
+
+
 # ---------------------------------------------------------------- exact OT (host function)
 @pytest.mark.parametrize('k', [4, 5, 7])
 def test_ot_assign_matches_reference_lp(lib, k):

@@ -520,3 +520,27 @@ def test_touch_index_mode_refusals():
     job = engine.TrainJob(shards, inits, perms, 16, 20, 1, 1e-3, 0.1, 0.9, 0.95, touch='index')
     assert job.touch and not job.index                 # more than 1,008 steps per epoch: windows
     job.close()
+
+
+# ---------------------------------------------------------------- library-owned memory comes from a cache of blocks
+@pytest.mark.parametrize('mode,B,env,kw', [('windows', 437, '0', dict(touch=True)), ('ahead', 3000, '1', dict(touch=True, final_only=True)),
+                                           ('index', 437, '1', dict(touch='index'))])
+def test_touch_memory_from_the_block_cache_is_filled_again(mode, B, env, kw, monkeypatch):
+    """A closed job's blocks (csrc/block_cache.cpp) go to the next job of the process with what the last one left in them: masks of
+    its last window, the 0xFF hand-over bytes overwritten, a slot index.  The same job made, trained, read and closed twice in one
+    process gives the same tables and losses to the last bit only if ure_job_create fills every block again.  The three jobs are the
+    smallest that between them make every group of arrays: row masks, work-order masks and the pass masks of epochs of two windows
+    (mode 1, 65 steps), the second set of work-order masks and the hand-over bytes (mode 2), the index block (mode 3)."""
+    from ultrare_amd import engine
+    monkeypatch.setenv('URE_TOUCH_INDEX', env)
+    k, E = 16, 2
+    out = []
+    for _ in range(2):
+        parts, inits, perms, shards = _setup(1, k, B, E)
+        job = engine.TrainJob(shards, inits, perms, k, B, E, 1e-3, 0.1, 0.9, 0.95, **kw)
+        assert job.touch and (job.ahead, job.index) == (mode == 'ahead', mode == 'index')
+        job.run()
+        out.append(tuple(t.clone() for t in job.tables(0)) + (job.epoch_sse(0).copy(),))
+        job.close()
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+    assert np.array_equal(out[0][2], out[1][2])

@@ -1,12 +1,15 @@
 """Per-kernel register / spill / scratch / LDS figures of the gfx950 code objects inside a built library.
 
     python tools/isa_report.py [LIB.so] [--json] [--filter SUBSTR]
+    python tools/isa_report.py --diff OLD.so NEW.so
 
 The library holds one clang offload bundle per HIP translation unit; each bundle carries one ELF
 code object for gfx950 whose NT_AMDGPU_METADATA note (msgpack) lists every kernel with its
 .vgpr_count, .vgpr_spill_count, .sgpr_spill_count, .private_segment_fixed_size ...  This reads the
 bundles directly (no GPU, no roc-obj tooling) and prints the table tests/test_cpu_host.py checks:
-no step kernel may spill.
+no step kernel may spill.  --diff compares two libraries function by function (machine code and metadata row; not file by
+file: a code object's hash follows its source text) and exits non-zero if a kernel differs: how a host-only change shows
+that it is one.
 """
 import json
 import os
@@ -105,25 +108,26 @@ def metadata(elf):
     return None
 
 
-def kernel_descriptors(elf):
-    """{kernel symbol: its 64-byte kernel descriptor} of one ELF64 code object (the `<kernel>.kd` objects of .rodata)."""
+def symbols(elf):
+    """(name, type, size, the bytes the symbol covers in its section) for every defined symbol of one ELF64 code object."""
     shoff, = struct.unpack_from('<Q', elf, 0x28)
     shentsize, shnum, shstrndx = struct.unpack_from('<HHH', elf, 0x3A)
     secs = [struct.unpack_from('<IIQQQQIIQQ', elf, shoff + k * shentsize) for k in range(shnum)]
-    out = {}
     for (_, typ, _, _, off, size, link, _, _, entsize) in secs:
         if typ not in (2, 11) or not entsize:          # SHT_SYMTAB / SHT_DYNSYM
             continue
         str_off = secs[link][4]
         for i in range(size // entsize):
             name_i, info, other, shndx, value, sym_size = struct.unpack_from('<IBBHQQ', elf, off + i * entsize)
-            end = elf.index(b'\0', str_off + name_i)
-            name = elf[str_off + name_i:end].decode()
-            if name.endswith('.kd') and sym_size == 64 and 0 < shndx < shnum:
+            if 0 < shndx < shnum and secs[shndx][1] != 8:          # (not SHT_NOBITS)
                 sec = secs[shndx]
                 at = sec[4] + (value - sec[3])
-                out[name[:-3]] = elf[at:at + 64]
-    return out
+                yield elf[str_off + name_i:elf.index(b'\0', str_off + name_i)].decode(), info & 15, sym_size, elf[at:at + sym_size]
+
+
+def kernel_descriptors(elf):
+    """{kernel symbol: its 64-byte kernel descriptor} of one ELF64 code object (the `<kernel>.kd` objects of .rodata)."""
+    return {name[:-3]: data for name, _, size, data in symbols(elf) if name.endswith('.kd') and size == 64}
 
 
 def demangle(names):
@@ -153,7 +157,35 @@ def kernels(lib=None):
     return rows
 
 
+def device_code(lib):
+    """{function symbol: (its machine code, its kernel descriptor, its row of the metadata note)} over all code objects of `lib`."""
+    out = {}
+    for elf in code_objects(lib):
+        rows = {k['.name']: k for k in (metadata(elf) or {}).get('amdhsa.kernels', [])}
+        kds = kernel_descriptors(elf)
+        for name, typ, size, data in symbols(elf):
+            if typ == 2 and size:                      # STT_FUNC
+                assert name not in out or out[name] == (data, kds.get(name), rows.get(name)), f'{name}: two different definitions in {lib}'
+                out[name] = (data, kds.get(name), rows.get(name))
+    return out
+
+
+def diff(old, new):
+    """Print the device functions whose code, descriptor or metadata differ between two libraries; -> their number."""
+    a, b = device_code(old), device_code(new)
+    names = sorted(n for n in set(a) | set(b) if a.get(n) != b.get(n))
+    for n, pretty in zip(names, demangle(names)):
+        what = 'only in ' + (old if n in a else new) if (n in a) != (n in b) else \
+               ' + '.join(w for w, x, y in zip(('code', 'descriptor', 'metadata'), a[n], b[n]) if x != y)
+        print(f'{pretty.split("(")[0]}: {what}')
+    print(f'{len(names)} of {len(set(a) | set(b))} device functions differ')
+    return len(names)
+
+
 if __name__ == '__main__':
+    if '--diff' in sys.argv:
+        i = sys.argv.index('--diff')
+        sys.exit(1 if diff(sys.argv[i + 1], sys.argv[i + 2]) else 0)
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     flt = sys.argv[sys.argv.index('--filter') + 1] if '--filter' in sys.argv else ''
     if flt in args:

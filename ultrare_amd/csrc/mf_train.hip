@@ -39,8 +39,7 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
+#include <type_traits>
 #include <vector>
 
 // Tuning knobs (defaults = the swept optimum; -D overrides are for sweeps only)
@@ -651,8 +650,7 @@ static void launch_index_epoch_start(const ure_job *job, int64_t tick, hipStream
     hipLaunchKernelGGL(idx_scan2_kernel, dim3(n_sh), dim3(1024), 0, st, job->dev, job->dev_aux, tick);
     hipLaunchKernelGGL(idx_scan3_kernel, dim3(step_blocks, kIdxSeg, n_sh), dim3(kBlock), 0, st, job->dev, job->dev_aux, tick);
     // (epochs of at most 63 steps: a step's share of 1,024 slots is a run worth sorting in LDS first)
-    constexpr bool staged_ok = true;
-    if (steps <= kIdxWin && staged_ok)
+    if (steps <= kIdxWin)
         hipLaunchKernelGGL(idx_scatter_short_kernel, dim3(wave_blocks, n_sh), dim3(kBlock), 0, st, job->dev, job->dev_aux, tick);
     else if (job->scatter_staged)
         hipLaunchKernelGGL((idx_scatter_staged_kernel<kIdxStagedWaves>), dim3((unsigned)chunks, n_sh), dim3(kIdxStagedWaves * kWave), 0, st, job->dev, job->dev_aux, tick);
@@ -691,7 +689,7 @@ static void launch_step(const ure_job *job, int64_t tick, hipStream_t st)
     int blocks = 1;
     for (size_t k = 0; k < job->host.size(); ++k) {
         const ure_shard_t &S = job->host[k];
-        const int64_t steps = ((int64_t)S.N + S.batch - 1) / S.batch;
+        const int64_t steps = job->aux_host[k].steps;
         if (tick >= steps * S.epochs) continue;
         const int64_t epoch = tick / steps;
         blocks = std::max(blocks, job->row_blocks[k] + tag_ride(job->aux_host[k], (int)(tick - epoch * steps), epoch + tag_ahead(S) < S.epochs).count);
@@ -710,6 +708,31 @@ static void launch_step(const ure_job *job, int64_t tick, hipStream_t st)
     hipLaunchKernelGGL((mf_step_kernel<LPR, V4>), grid, dim3(kBlock), 0, st, job->dev, job->dev_aux, tick, shard_fast);
 }
 
+// The launches above are compiled per table width: f(LPR, V4) with the lanes per row and the float4 per lane of width d as
+// std::integral_constant arguments.  false: a width the library has no kernels for (ure_job_create lets none through).
+// Every width takes its pair from lanes_per_row, so a -DURE_NARROW_MAX sweep build moves all of them with the macro (by default:
+// <1,1> <2,1> <4,1> <8,1> <8,2> <16,2> <32,2>).
+template <int D, class F>
+static void call_width(F &f)
+{
+    constexpr int LPR = lanes_per_row(D);
+    f(std::integral_constant<int, LPR>{}, std::integral_constant<int, D / (4 * LPR)>{});
+}
+template <class F>
+static bool with_width(int d, F f)
+{
+    switch (d) {
+        case 4: call_width<4>(f); return true;
+        case 8: call_width<8>(f); return true;
+        case 16: call_width<16>(f); return true;
+        case 32: call_width<32>(f); return true;
+        case 64: call_width<64>(f); return true;
+        case 128: call_width<128>(f); return true;
+        case 256: call_width<256>(f); return true;
+        default: return false;
+    }
+}
+
 }  // namespace ure
 
 using namespace ure;
@@ -718,318 +741,15 @@ using namespace ure;
 extern "C" int ure_debug_timeline(void *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(ure::g_timeline), &buf, sizeof(buf)); }
 #endif
 
+#include "mf_job.h"
+
 extern "C" {
-
-// Library-owned device memory of touch mode (masks, tables, the slot index) comes from a small cache of blocks instead of hipMalloc / hipFree
-// per job: a 32-shard job makes 32-128 allocations, each a driver call and a synchronous fill -- 24 ms of a 110 ms request at configs[3]'s
-// shape (k = 16), 28 ms at k = 128 --, and every request of a process asks for the same sizes again.  Blocks go back when their job is destroyed
-// (after the device has been waited for); up to kBlockCacheBytes are kept per device, the rest is freed.
-namespace ure {
-namespace {
-struct BlockCache {
-    std::multimap<size_t, void *> idle;
-    std::map<void *, size_t> size_of;
-    size_t held = 0;
-};
-std::mutex g_block_lock;
-std::map<int, BlockCache> g_block_cache;
-constexpr size_t kBlockCacheBytes = (size_t)8 << 30;
-
-hipError_t block_malloc(void **out, size_t bytes)
-{
-    bytes = (std::max<size_t>(bytes, 1) + ((size_t)256 << 10) - 1) / ((size_t)256 << 10) * ((size_t)256 << 10);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> hold(g_block_lock);
-        BlockCache &C = g_block_cache[dev];
-        auto it = C.idle.lower_bound(bytes);
-        if (it != C.idle.end() && it->first <= bytes + bytes / 4 + ((size_t)1 << 20)) {
-            *out = it->second;
-            C.held -= it->first;
-            C.idle.erase(it);
-            return hipSuccess;
-        }
-    }
-    hipError_t e = hipMalloc(out, bytes);
-    if (e != hipSuccess) {                                   // (out of memory with idle blocks held: give them back and ask once more)
-        std::vector<void *> drop;
-        {
-            std::lock_guard<std::mutex> hold(g_block_lock);
-            BlockCache &C = g_block_cache[dev];
-            for (auto &kv : C.idle) { drop.push_back(kv.second); C.size_of.erase(kv.second); }
-            C.idle.clear();
-            C.held = 0;
-        }
-        for (void *p : drop) (void)hipFree(p);
-        (void)hipGetLastError();
-        e = hipMalloc(out, bytes);
-    }
-    if (e == hipSuccess) {
-        std::lock_guard<std::mutex> hold(g_block_lock);
-        g_block_cache[dev].size_of[*out] = bytes;
-    }
-    return e;
-}
-
-void block_free(void *p)
-{
-    if (!p) return;
-    // (the device the block lives on, not the calling thread's current one: a job is destroyed on a worker thread, whose current device is 0
-    // whatever GPU its rank trains on)
-    int dev = 0;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) == hipSuccess) dev = attr.device;
-    else { (void)hipGetLastError(); (void)hipGetDevice(&dev); }
-    {
-        std::lock_guard<std::mutex> hold(g_block_lock);
-        BlockCache &C = g_block_cache[dev];
-        auto it = C.size_of.find(p);
-        if (it != C.size_of.end() && C.held + it->second <= kBlockCacheBytes) {
-            C.idle.emplace(it->second, p);
-            C.held += it->second;
-            return;
-        }
-        if (it != C.size_of.end()) C.size_of.erase(it);
-    }
-    (void)hipFree(p);
-}
-}  // namespace
-}  // namespace ure
-
-int ure_job_create(const ure_shard_t *shards, int n_shards, ure_job_t **out)
-{
-    URE_ARG(shards && out && n_shards > 0 && n_shards <= 65535);
-    auto *job = new ure::ure_job();
-    job->host.assign(shards, shards + n_shards);
-    for (int k = 0; k < n_shards; ++k) {
-        const ure_shard_t &S = shards[k];
-        const int n_rows = S.n_user + S.n_item;
-        const bool ok = S.N > 0 && S.n_user > 0 && S.n_item > 0 && S.batch > 0 && S.epochs > 0 && pow2(S.d) && S.d >= 4 &&
-                        S.d <= 256 && S.n_active >= 0 && S.n_active <= n_rows && S.units && S.n_units >= 0 &&
-                        S.n_units % (kBlock / lanes_per_row(S.d)) == 0 && S.n_slots >= S.N && S.ent_oid && S.ent_r && S.ent_tag && S.ent_src &&
-                        S.file_tag && S.sched && S.U[0] && S.U[1] && S.V[0] && S.V[1] && S.mU && S.mV && (S.perm || S.file_tags) && S.lr && S.sse &&
-                        (!S.lazy_rows || (S.U0 && S.V0 && S.lr_host));
-        if (!ok) { delete job; return fail(-1, "ure_job_create: shard %d has an invalid descriptor", k); }
-        if (S.d != shards[0].d) { delete job; return fail(-1, "ure_job_create: all shards of a job share d"); }
-        const int64_t steps = ((int64_t)S.N + S.batch - 1) / S.batch;
-        if (steps > 65534) { delete job; return fail(-1, "ure_job_create: shard %d needs %lld steps/epoch (> 65534)", k, (long long)steps); }
-        job->ticks = std::max(job->ticks, steps * S.epochs);
-        const int per_block = kBlock / lanes_per_row(S.d);
-        if (S.touch_mode && (S.n_multi < 0 || S.n_multi > S.n_active)) { delete job; return fail(-1, "ure_job_create: shard %d: n_multi outside [0, n_active]", k); }
-        const int blocks = S.touch_mode ? S.n_units / per_block + (S.n_active - S.n_multi + kBlock - 1) / kBlock      // units + candidate workgroups
-                                        : S.n_units / per_block + (S.lazy_rows ? 0 : (n_rows - S.n_active + per_block - 1) / per_block);
-        job->row_blocks.push_back(blocks);
-        job->max_n = std::max(job->max_n, S.N);
-        job->max_slots = std::max(job->max_slots, S.n_slots);
-        const bool small = tag_partitioned(S.N);
-        if (small && !(S.inv_stage && S.inv_off)) { delete job; return fail(-1, "ure_job_create: shard %d lacks inv_stage / inv_off", k); }
-        (small ? job->small_shards : job->large_shards) = true;
-        if (small) job->max_small_n = std::max(job->max_small_n, S.N);
-    }
-    job->d = shards[0].d;
-    if (const char *e = std::getenv("URE_SHARD_FAST")) { job->shard_fast = e[0] != '0'; job->shard_sliced = e[0] == '2'; }
-    if (const char *e = std::getenv("URE_INDEX_STAGED")) job->scatter_staged = e[0] != '0';
-    for (int k = 0; k < n_shards; ++k) {
-        const ure_shard_t &S = shards[k];
-        job->lr_host.emplace_back(S.lr_host ? std::vector<float>(S.lr_host, S.lr_host + S.epochs) : std::vector<float>());
-        job->host[k].lr_host = nullptr;                       // the caller's array need not outlive this call
-        job->max_lazy = std::max<int64_t>(job->max_lazy, S.lazy_rows ? (int64_t)(S.n_user + S.n_item - S.n_active) * (S.d / 4) : 0);
-        if (S.snapU || S.snapV || S.snap) {
-            const bool full = S.snapU && S.snapV && !S.snap, compact = S.snap && !S.snapU && !S.snapV && S.lazy_rows;
-            if (!(full || compact) || (S.lazy_rows && !S.snap_a)) { delete job; return fail(-1, "ure_job_create: shard %d has an incomplete snapshot set (full: snapU + snapV; compact: snap with lazy_rows; snap_a with lazy_rows)", k); }
-            job->snapshots = true;
-            const int64_t rows = compact ? S.n_active : S.n_user + S.n_item;
-            job->snap_blocks = std::max<unsigned>(job->snap_blocks, (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows * (S.d / 4) + kBlock - 1) / kBlock, 2048)));
-        }
-    }
-    for (int k = 0; k < n_shards; ++k) job->aux_host.push_back(make_shard_aux(shards[k]));
-    // ---- touch mode: all shards of the job or none; masks and closed-form tables are library-owned
-    for (int k = 0; k < n_shards; ++k) job->touch = job->touch || shards[k].touch_mode != 0;
-    job->ahead = shards[0].touch_mode == 2;
-    job->index = shards[0].touch_mode == 3;
-    for (int k = 0; k < n_shards; ++k) job->all_file_tags = job->all_file_tags && shards[k].file_tags != nullptr;
-    if (job->touch) {
-        for (int k = 0; k < n_shards; ++k) {
-            const ure_shard_t &S = shards[k];
-            const char *why = !S.touch_mode ? "every shard of a job must ask for it" :
-                              (S.touch_mode < 1 || S.touch_mode > 3) ? "touch_mode is 0, 1, 2 or 3" :
-                              S.touch_mode != shards[0].touch_mode ? "every shard of a job must ask for the same touch mode" :
-                              (S.touch_mode == 2 && job->aux_host[k].steps > kAheadMaxSteps) ? "touch_mode 2 takes at most 63 steps per epoch (the mask word's top bit is the start buffer)" :
-                              (S.touch_mode == 2 && (S.snapU || S.snapV)) ? "touch_mode 2 writes compact snapshots only (snap + row_slot)" :
-                              (S.touch_mode == 2 && S.snap && !S.row_slot) ? "touch_mode 2 needs row_slot with snap" :
-                              (S.touch_mode == 3 && job->aux_host[k].steps > kIdxMaxSteps) ? "touch_mode 3 takes at most 1008 steps per epoch (16 mask words of 63 steps)" :
-                              (S.touch_mode == 3 && (S.n_multi > kIdxHeavyMax || S.n_split < 0 || S.n_split > S.n_multi)) ? "touch_mode 3: 0 <= n_split <= n_multi <= 256" :
-                              (S.touch_mode == 3 && S.batch > 200000) ? "touch_mode 3 takes batches of at most 200,000 (the parts of a split row are numbered in 11 bits)" :
-                              !S.lazy_rows ? "it needs lazy_rows" :
-                              job->aux_host[k].steps > kTouchMaxSteps ? "more than 32000 steps per epoch (the step number shares the 16-bit batch tag with the buffer bit)" :
-                              (S.epochs != shards[0].epochs || S.lam != shards[0].lam || S.mu != shards[0].mu ||
-                               job->lr_host[k] != job->lr_host[0]) ? "the shards' optimizer schedules differ" : nullptr;
-            if (why) { delete job; return fail(-1, "ure_job_create: touch mode refused for shard %d: %s", k, why); }
-            job->max_units = std::max(job->max_units, S.n_units);
-            job->max_active4 = std::max<int64_t>(job->max_active4, (int64_t)S.n_active * (S.d / 4));
-            job->max_rows = std::max(job->max_rows, S.n_user + S.n_item);
-        }
-    }
-    hipError_t e = hipMalloc(&job->dev, sizeof(ure_shard_t) * n_shards);
-    if (e == hipSuccess) e = hipMemcpy(job->dev, job->host.data(), sizeof(ure_shard_t) * n_shards, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&job->dev_ab, sizeof(double) * 2 * n_shards);
-    if (job->touch && e == hipSuccess) {
-        // A_e^j for j = 0..64 (the length of a window) at every epoch's learning rate, in double: (w, m)' = A (w, m),
-        // m' = mu m + lam w, w' = w - lr m'
-        const int E = shards[0].epochs;
-        int tab_n = kTouchTab;                                      // touch_mode 3: a row may wait a whole epoch for its next step
-        if (job->index)
-            for (int k = 0; k < n_shards; ++k) tab_n = std::max(tab_n, job->aux_host[k].steps + 1);
-        for (int k = 0; k < n_shards; ++k) job->aux_host[k].ptab_stride = tab_n;
-        std::vector<float> tab((size_t)E * tab_n * 4);
-        const double lam = (double)shards[0].lam, mu = (double)shards[0].mu;
-        for (int ep = 0; ep < E; ++ep) {
-            const double lr = (double)job->lr_host[0][(size_t)ep];
-            const double a11 = 1.0 - lr * lam, a12 = -lr * mu, a21 = lam, a22 = mu;
-            double p11 = 1.0, p12 = 0.0, p21 = 0.0, p22 = 1.0;
-            for (int j = 0; j < tab_n; ++j) {
-                float *o = &tab[((size_t)ep * tab_n + j) * 4];
-                o[0] = (float)p11; o[1] = (float)p12; o[2] = (float)p21; o[3] = (float)p22;
-                const double q11 = a11 * p11 + a12 * p21, q12 = a11 * p12 + a12 * p22;
-                const double q21 = a21 * p11 + a22 * p21, q22 = a21 * p12 + a22 * p22;
-                p11 = q11; p12 = q12; p21 = q21; p22 = q22;
-            }
-        }
-        void *ptab = nullptr;
-        e = block_malloc(&ptab, tab.size() * sizeof(float));
-        if (e == hipSuccess) { job->touch_mem.push_back(ptab); e = hipMemcpy(ptab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice); }
-        // (epochs of at most 63 steps in every shard: idx_scatter_short_kernel sorts 1,024 slots at a time in LDS, and with a chunk of that size a
-        // wavefront per 1,024 slots instead of 4,096 -- the shards of such a job start their epochs at different ticks, 25 / 26 / 27 steps apart, and a
-        // single shard's 340 chunks of 4,096 left three quarters of the chip idle: 100 us per shard and epoch against 26 with all 32 at once)
-        bool index_short = true;
-        for (int k = 0; k < n_shards; ++k) index_short = index_short && job->aux_host[k].steps <= kIdxWin;
-        for (int k = 0; k < n_shards && e == hipSuccess && job->index; ++k) {
-            // touch_mode 3: the slot index of the current epoch (mf_index.h), one allocation per shard
-            const ure_shard_t &S = shards[k];
-            shard_aux &A = job->aux_host[k];
-            A.ptab = static_cast<const float4 *>(ptab);
-            const size_t n_all = (size_t)S.n_user + S.n_item, steps = (size_t)A.steps, slots = (size_t)S.n_slots;
-            A.idx_words = (int32_t)((steps + kIdxWin - 1) / kIdxWin);
-            A.idx_chunk = index_short ? kIdxStage : kIdxChunk;
-            A.idx_chunks = (int32_t)((slots + A.idx_chunk - 1) / A.idx_chunk);
-            A.idx_hw = S.n_multi + 2 * S.batch / kIdxPart + 2;
-            A.idx_light = (int32_t)std::min<int64_t>(2 * (int64_t)S.batch, S.n_active);
-            size_t at = 0;
-            auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-            const size_t o_grp = take(slots / 8 * 8), o_w = take((size_t)A.idx_words * n_all * 8), o_par = take(2 * n_all), o_first = take(n_all * 2 + (size_t)A.idx_words * n_all * 2);
-            const size_t o_hist = take((size_t)A.idx_chunks * (steps + 1) * 4), o_seg = take((size_t)kIdxSeg * (steps + 1) * 4), o_sb = take((steps + 2) * 4);
-            const size_t o_ss = take(slots * 16), o_rf = take((slots / 64 + 2) * 8), o_bc = take((slots / kIdxFlagBlock + 2) * 4);
-            const size_t o_it = take(((size_t)std::min<int64_t>(2 * (int64_t)S.N, S.n_slots) + 1) * 16), o_si = take((steps + 2) * 4), o_hc = take(steps * 4);
-            const size_t o_it2 = take(((size_t)std::min<int64_t>(2 * (int64_t)S.N, S.n_slots) + 1) * 16);
-            const size_t o_cum = take(steps * (kIdxHeavyMax + 1) * 4), o_pa = take((size_t)A.idx_hw * (S.d + 4) * 4);
-            const size_t o_map = take(steps * (size_t)A.idx_hw * 4), o_wg = take(steps * 4), o_sd = take(steps * 16);
-            void *mem = nullptr;
-            e = block_malloc(&mem, at);
-            if (e != hipSuccess) break;
-            job->touch_mem.push_back(mem);
-            char *b = static_cast<char *>(mem);
-            e = hipMemset(b + o_w, 0, (o_hist - o_w));                       // masks, end-of-epoch buffers, first steps
-            A.grp_row = reinterpret_cast<int32_t *>(b + o_grp);
-            A.W = reinterpret_cast<unsigned long long *>(b + o_w);
-            A.end_par[0] = reinterpret_cast<uint8_t *>(b + o_par);
-            A.end_par[1] = A.end_par[0] + n_all;
-            A.first_step = reinterpret_cast<uint16_t *>(b + o_first);
-            A.next_first = A.first_step + n_all;
-            A.hist = reinterpret_cast<uint32_t *>(b + o_hist);
-            A.seg = reinterpret_cast<uint32_t *>(b + o_seg);
-            A.step_begin = reinterpret_cast<uint32_t *>(b + o_sb);
-            A.sslot = reinterpret_cast<uint4 *>(b + o_ss);
-            A.runflag = reinterpret_cast<unsigned long long *>(b + o_rf);
-            A.blk_cnt = reinterpret_cast<uint32_t *>(b + o_bc);
-            A.items = reinterpret_cast<int4 *>(b + o_it);
-            A.items2 = reinterpret_cast<uint4 *>(b + o_it2);
-            A.step_item = reinterpret_cast<uint32_t *>(b + o_si);
-            A.heavy_cnt = reinterpret_cast<uint32_t *>(b + o_hc);
-            A.heavy_cum = reinterpret_cast<uint32_t *>(b + o_cum);
-            A.partial = reinterpret_cast<float *>(b + o_pa);
-            A.heavy_map = reinterpret_cast<uint32_t *>(b + o_map);
-            A.heavy_wg = reinterpret_cast<uint32_t *>(b + o_wg);
-            A.step_desc = reinterpret_cast<uint4 *>(b + o_sd);
-            job->index_split = job->index_split || S.n_split > 0;
-        }
-        for (int k = 0; k < n_shards && e == hipSuccess && !job->index; ++k) {
-            const size_t bytes = (size_t)(shards[k].n_user + shards[k].n_item) * sizeof(unsigned long long);
-            void *mk = nullptr;
-            e = block_malloc(&mk, 2 * bytes);
-            if (e != hipSuccess) break;
-            job->touch_mem.push_back(mk);
-            e = hipMemset(mk, 0, 2 * bytes);
-            job->aux_host[k].mask[0] = static_cast<unsigned long long *>(mk);
-            job->aux_host[k].mask[1] = static_cast<unsigned long long *>(mk) + (shards[k].n_user + shards[k].n_item);
-            job->aux_host[k].ptab = static_cast<const float4 *>(ptab);
-            // the masks once more in work order: per work unit (multi-pass rows) and per single-pass row of the schedule
-            const size_t n_um = (size_t)std::max(shards[k].n_units, 1), n_sm = (size_t)std::max(shards[k].n_active - shards[k].n_multi, 1);
-            void *wm = nullptr;
-            e = block_malloc(&wm, (2 * n_um + n_sm) * sizeof(unsigned long long));
-            if (e != hipSuccess) break;
-            job->touch_mem.push_back(wm);
-            e = hipMemset(wm, 0, (2 * n_um + n_sm) * sizeof(unsigned long long));
-            job->aux_host[k].unit_mask = static_cast<unsigned long long *>(wm);
-            job->aux_host[k].unit_own = static_cast<unsigned long long *>(wm) + n_um;
-            job->aux_host[k].sched_mask = static_cast<unsigned long long *>(wm) + 2 * n_um;
-            job->aux_host[k].n_um = (int32_t)n_um;
-            job->aux_host[k].n_sm = (int32_t)n_sm;
-            if (!job->ahead && job->aux_host[k].windows > 1 && shards[k].n_units > 0) {
-                // epochs of several windows: the steps of every scan pass of the multi-pass units (mf_touch.h: pass skipping)
-                void *pm = nullptr;
-                const size_t bytes = ((size_t)shards[k].n_slots / 8 + 1) * sizeof(unsigned long long);
-                e = block_malloc(&pm, bytes);
-                if (e != hipSuccess) break;
-                job->touch_mem.push_back(pm);
-                e = hipMemset(pm, 0, bytes);
-                if (e != hipSuccess) break;
-                job->aux_host[k].pass_mask = static_cast<unsigned long long *>(pm);
-            }
-            if (job->ahead) {
-                // touch_mode 2: the work-order masks once per epoch parity (the first set is the one above), and the owners' hand-over
-                void *wm2 = nullptr, *nf = nullptr;
-                e = block_malloc(&wm2, (2 * n_um + n_sm) * sizeof(unsigned long long));
-                if (e != hipSuccess) break;
-                job->touch_mem.push_back(wm2);
-                e = hipMemset(wm2, 0, (2 * n_um + n_sm) * sizeof(unsigned long long));
-                if (e != hipSuccess) break;
-                e = block_malloc(&nf, n_um + n_sm);
-                if (e != hipSuccess) break;
-                job->touch_mem.push_back(nf);
-                e = hipMemset(nf, 0xFF, n_um + n_sm);
-                job->aux_host[k].ahead_masks[0] = static_cast<unsigned long long *>(wm);
-                job->aux_host[k].ahead_masks[1] = static_cast<unsigned long long *>(wm2);
-                job->aux_host[k].unit_nf = static_cast<uint8_t *>(nf);
-                job->aux_host[k].sched_nf = static_cast<uint8_t *>(nf) + n_um;
-            }
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc(&job->dev_aux, sizeof(shard_aux) * n_shards);
-    if (e == hipSuccess) e = hipMemcpy(job->dev_aux, job->aux_host.data(), sizeof(shard_aux) * n_shards, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { const int rc = fail((int)e, "ure_job_create: %s", hipGetErrorString(e)); ure_job_destroy(reinterpret_cast<ure_job_t *>(job)); return rc; }
-    *out = reinterpret_cast<ure_job_t *>(job);
-    return 0;
-}
-
-int ure_job_destroy(ure_job_t *j)
-{
-    auto *job = reinterpret_cast<ure::ure_job *>(j);
-    if (!job) return 0;
-    if (job->dev) (void)hipFree(job->dev);
-    if (job->dev_ab) (void)hipFree(job->dev_ab);
-    if (job->dev_aux) (void)hipFree(job->dev_aux);
-    for (void *p : job->touch_mem) ure::block_free(p);          // (the three frees above have waited for the device)
-    delete job;
-    return 0;
-}
 
 int64_t ure_job_shard_steps(const ure_job_t *j, int s)
 {
     auto *job = reinterpret_cast<const ure::ure_job *>(j);
     if (!job || s < 0 || s >= (int)job->host.size()) return -1;
-    const ure_shard_t &S = job->host[s];
-    return (((int64_t)S.N + S.batch - 1) / S.batch) * S.epochs;
+    return (int64_t)job->aux_host[s].steps * job->host[s].epochs;
 }
 
 int64_t ure_job_ticks(const ure_job_t *j)
@@ -1049,59 +769,37 @@ static int train_ticks(ure::ure_job *job, int64_t tick0, int64_t tick1, hipStrea
         URE_HIP(hipEventRecord(e, st));
         return 0;
     };
+    // a group of launches between two events of `v` (ure_job_train_profiled adds up the pairs); false from it: with_width knows no such d
+    auto timed = [&](std::vector<hipEvent_t> *v, auto launches) -> int {
+        if (int rc = mark(v)) return rc;
+        if (!launches()) return fail(-1, "ure_job_train: unsupported d=%d", job->d);
+        return mark(v);
+    };
     for (int64_t t = tick0; t < tick1; ++t) {
+        int rc = 0;
         // batch tags: the step kernel prepares the next epoch's itself (riders); epoch 0, shards with
         // fewer than 3 steps per epoch and very large shards get standalone launches here
-        if (const int passes = tag_prep_needed(job, t)) {
-            if (int rc = mark(assign_ev)) return rc;
-            if (passes & 1) launch_tag_prep(job, t, st, 0);
-            if (passes & 2) launch_tag_prep(job, t, st, 1);
-            if (int rc = mark(assign_ev)) return rc;
-        }
-        if (job->ahead && touch_prep_needed(job, t)) {
-            if (int rc = mark(assign_ev)) return rc;
-            switch (job->d) {
-                case 4: launch_touch_ahead<1, 1>(job, t, st); break;
-                case 8: launch_touch_ahead<2, 1>(job, t, st); break;
-                case 16: launch_touch_ahead<4, 1>(job, t, st); break;
-                case 32: launch_touch_ahead<lanes_per_row(32), 32 / (4 * lanes_per_row(32))>(job, t, st); break;
-                case 64: launch_touch_ahead<8, 2>(job, t, st); break;
-                case 128: launch_touch_ahead<16, 2>(job, t, st); break;
-                default: launch_touch_ahead<32, 2>(job, t, st); break;
-            }
-            if (int rc = mark(assign_ev)) return rc;
-        } else if (index_epoch_start_needed(job, t)) {
-            if (int rc = mark(assign_ev)) return rc;
-            launch_index_epoch_start(job, t, st);
-            if (int rc = mark(assign_ev)) return rc;
-        } else if (touch_prep_needed(job, t)) {
-            if (int rc = mark(assign_ev)) return rc;
-            switch (lanes_per_row(job->d)) {
-                case 1: launch_touch_prep<1>(job, t, st); break;
-                case 2: launch_touch_prep<2>(job, t, st); break;
-                case 4: launch_touch_prep<4>(job, t, st); break;
-                case 8: launch_touch_prep<8>(job, t, st); break;
-                case 16: launch_touch_prep<16>(job, t, st); break;
-                default: launch_touch_prep<32>(job, t, st); break;
-            }
-            if (int rc = mark(assign_ev)) return rc;
-        }
-        if (int rc = mark(step_ev)) return rc;
-        switch (job->d) {
-            case 4: launch_step<1, 1>(job, t, st); break;
-            case 8: launch_step<2, 1>(job, t, st); break;
-            case 16: launch_step<4, 1>(job, t, st); break;
-            case 32: launch_step<lanes_per_row(32), 32 / (4 * lanes_per_row(32))>(job, t, st); break;
-            case 64: launch_step<8, 2>(job, t, st); break;
-            case 128: launch_step<16, 2>(job, t, st); break;
-            case 256: launch_step<32, 2>(job, t, st); break;
-            default: return fail(-1, "ure_job_train: unsupported d=%d", job->d);
-        }
-        if (int rc = mark(step_ev)) return rc;
+        if (const int passes = tag_prep_needed(job, t))
+            rc = timed(assign_ev, [&] {
+                if (passes & 1) launch_tag_prep(job, t, st, 0);
+                if (passes & 2) launch_tag_prep(job, t, st, 1);
+                return true;
+            });
+        if (rc) return rc;
+        if (job->ahead && touch_prep_needed(job, t))
+            rc = timed(assign_ev, [&] { return with_width(job->d, [&](auto lpr, auto v4) { launch_touch_ahead<decltype(lpr)::value, decltype(v4)::value>(job, t, st); }); });
+        else if (index_epoch_start_needed(job, t))
+            rc = timed(assign_ev, [&] { launch_index_epoch_start(job, t, st); return true; });
+        else if (touch_prep_needed(job, t))
+            rc = timed(assign_ev, [&] { return with_width(job->d, [&](auto lpr, auto) { launch_touch_prep<decltype(lpr)::value>(job, t, st); }); });
+        if (rc) return rc;
+        rc = timed(step_ev, [&] { return with_width(job->d, [&](auto lpr, auto v4) { launch_step<decltype(lpr)::value, decltype(v4)::value>(job, t, st); }); });
+        if (rc) return rc;
         if (job->snapshots) {
             bool epoch_end = false;
-            for (const ure_shard_t &S : job->host) {
-                const int64_t steps = ((int64_t)S.N + S.batch - 1) / S.batch;
+            for (size_t k = 0; k < job->host.size(); ++k) {
+                const ure_shard_t &S = job->host[k];
+                const int64_t steps = job->aux_host[k].steps;
                 const bool by_kernel = S.snapU || (S.snap && (S.touch_mode == 1 || S.touch_mode == 3 || !S.row_slot));      // otherwise the step kernel's owners wrote it
                 if (by_kernel && t + 1 <= steps * S.epochs && (t + 1) % steps == 0) { epoch_end = true; break; }
             }
@@ -1137,7 +835,7 @@ int ure_job_materialize(ure_job_t *j, int64_t ticks_done, void *stream)
     for (size_t k = 0; k < n; ++k) {
         const ure_shard_t &S = job->host[k];
         if (!S.lazy_rows) continue;
-        const int64_t steps = ((int64_t)S.N + S.batch - 1) / S.batch;
+        const int64_t steps = job->aux_host[k].steps;
         const int64_t T = std::min(ticks_done, steps * S.epochs);
         double a = 1.0, b = 0.0;
         const double lam = (double)S.lam, mu = (double)S.mu;

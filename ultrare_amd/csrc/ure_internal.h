@@ -78,6 +78,10 @@ struct ure_job {
 int tag_prep_needed(const ure_job *job, int64_t tick);                       // bit mask of the standalone passes needed (tag_prep.hip)
 void launch_tag_prep(const ure_job *job, int64_t tick, hipStream_t st, int pass);
 
+// block_cache.cpp: device memory the library owns, recycled from job to job (rounded up to 256 KiB; the caller fills it)
+hipError_t block_malloc(void **out, size_t bytes);
+void block_free(void *p);
+
 // Global-memory accessors.  A pointer that a kernel reads out of a descriptor in memory (struct
 // ure_shard) has no address space the compiler can see, so a plain dereference becomes a flat_*
 // instruction: it counts in vmcnt AND lgkmcnt, completes out of order and forces every wait to be
