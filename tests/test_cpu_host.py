@@ -1267,3 +1267,29 @@ def test_tag_chunks_and_shuffle_choice():
     assert rng.shuffle_method(180_000, 250, 'auto') == 'chain' and rng.shuffle_method(56_000, 800, 'auto') == 'chain'
     assert rng.shuffle_method((1 << 20) + 1, 800, 'reservations') == 'chain'
     assert rng.shuffle_method(56_000, 8, 'reservations') == 'reservations' and rng.shuffle_method(56_000, 800, 'chain') == 'chain'
+
+
+def test_perm_table_is_in_launch_order_and_tiled_by_its_chunks():
+    """rng.perm_table, the descriptor table of a call's device shuffles (struct ure_perm), against a plain triple loop over chunk, then
+    shard, then epoch: row (s, e) writes its tags at base + 2 * (off[s] + e * n_rows[s]) for the 64-element-aligned offsets of rng._pack,
+    and the chunks' row ranges tile the table."""
+    from ultrare_amd import rng
+    n_rows, epochs, batch, base, bounds = (5, 300, 4099), 5, 64, 1 << 20, [0, 2, 5]
+    seeds = [[(s + 1) * 1000003 + e * 17 + (1 << 61) for e in range(epochs)] for s in range(len(n_rows))]
+    seeds[1][3] = 2 ** 64 - 3                                           # (a sampler seed with the top bit set: the same bits as int64)
+    offs, total = rng._pack([epochs * n for n in n_rows])
+    assert offs == [0, 64, 1600] and total == 1600 + 20544 and all(o % 64 == 0 for o in offs + [total])
+    table, ranges = rng.perm_table(seeds, n_rows, batch, base, offs, bounds)
+    want = []
+    for c0, c1 in zip(bounds[:-1], bounds[1:]):
+        for s, n in enumerate(n_rows):
+            for e in range(c0, c1):
+                sd = seeds[s][e] - (1 << 64) if seeds[s][e] >= 1 << 63 else seeds[s][e]
+                want.append((sd, base + 2 * (offs[s] + e * n), n, batch))
+    assert table.dtype == rng.PERM_DTYPE and table.shape == (len(want),)
+    assert table.tolist() == want
+    assert ranges == [(0, 6), (6, 15)]
+    assert ranges[0][0] == 0 and ranges[-1][1] == len(table) and all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
+    # a batch size per shard gives the same table as one for all
+    per_shard, _ = rng.perm_table(seeds, n_rows, [batch] * len(n_rows), base, offs, bounds)
+    assert np.array_equal(per_shard, table)

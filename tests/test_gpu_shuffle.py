@@ -77,3 +77,32 @@ def test_shuffle_tags_beyond_2_to_20_rows(sizes):
     launch, one of them a word longer than a segment, one of a few rows."""
     n = max(sizes)
     _run([(x, 30000) for x in sizes], lambda n: 1, seed=3, range_log2=14 if n < 5_000_000 and len(sizes) == 1 else 0)
+
+
+@pytest.mark.parametrize('method', [None, 'reservations'])
+def test_deferred_device_tags_of_a_call_equal_the_hosts(method):
+    """rng.device_tags as bench.py drives it (defer=True, given bounds, given seeds): three shards in one allocation -- 5 rows (less than a
+    wavefront; 3 x 5 = 15 elements, so the next shard starts behind 64-element padding), 300 rows (inside one range) and 4099 (just past
+    4096) --, two chunks fired in order; every shard's tags equal rng.epoch_tags byte for byte."""
+    from ultrare_amd import rng
+    dev = torch.device('cuda:0')
+    sizes, epochs, batch = (5, 300, 4099), 3, 64
+    rs = np.random.RandomState(5)
+    seeds = [[int(x) for x in rs.randint(0, 2 ** 62, size=epochs)] for _ in sizes]
+    tasks = [rng._task_of(dict(start_state=None, n_user=0, n_item=0, k=0, epochs=epochs, with_total_test=True, n_rows=n, shuffle=True,
+                               device=dev, tags_batch=batch, seeds=sd), buffers=False) for n, sd in zip(sizes, seeds)]
+    fire = rng.device_tags(tasks, bounds=[0, 1, 3], defer=True, method=method)
+    assert callable(fire)
+    fire(0)
+    fire(1)
+    main = torch.cuda.current_stream(dev)
+    for t in tasks:
+        assert rng.Arrival.of(t.perms_value).wait(main, epochs - 1) == epochs
+    torch.cuda.synchronize()
+    rng.device_tags_check([t.perms_value for t in tasks])
+    for t, n, sd in zip(tasks, sizes, seeds):
+        got = t.perms_value.cpu()
+        assert got.shape == (epochs, n) and got.dtype == torch.int16
+        assert torch.equal(got, rng.epoch_tags(sd, n, batch)), n
+        assert len(t.perms_value._ure_methods) == 2
+        assert all(m == rng.shuffle_method(max(sizes), len(sizes), method) for m in t.perms_value._ure_methods)

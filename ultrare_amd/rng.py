@@ -505,12 +505,27 @@ def tags_batch_for(n, batch, honour_env=True):
     return int(batch) if 0 < -(-n // max(int(batch), 1)) <= 65535 and n < RANDPERM_HUGE_N else 0
 
 
+def _seed_words(seeds):
+    """The seeds as the int64 words the library reads (the sampler's seeds are uint64 values: the same bits)."""
+    return np.asarray(seeds, dtype=np.uint64).astype(np.int64)
+
+
+def _expand(seeds, n, tags_batch, dst, threads=0):
+    """The host's expansion of len(seeds) epochs of n rows into the memory at `dst`: their permutations (ure_host_randperm, int32 [epochs, n])
+    or, tags_batch = B > 0, those permutations' batch tags (ure_host_randperm_tags, int16) on `threads` library threads, without the GIL."""
+    from . import _native as nv
+    sd = _seed_words(seeds)
+    if tags_batch:
+        nv.check(nv.lib().ure_host_randperm_tags(sd.ctypes.data, len(sd), int(n), int(tags_batch), dst, int(threads or 0)), 'ure_host_randperm_tags')
+    else:
+        nv.check(nv.lib().ure_host_randperm(sd.ctypes.data, len(sd), int(n), dst, int(threads or 0)), 'ure_host_randperm')
+
+
 def epoch_perms(seeds, n, threads=0, pooled=False):
     """[len(seeds), n] int32 permutations, perms[t] == torch.randperm(n, generator seeded with
     seeds[t]).  Each epoch has its own generator, so the epochs are expanded concurrently by
     the library's host threads (ure_host_randperm, a restatement of ATen's MT19937
     Fisher-Yates loop checked against torch.randperm in tests/test_cpu_host.py)."""
-    from . import _native as nv
     out = POOL.take((len(seeds), n), torch.int32) if pooled else torch.empty(len(seeds), n, dtype=torch.int32)
     if len(seeds) == 0 or n == 0:
         return out
@@ -518,8 +533,7 @@ def epoch_perms(seeds, n, threads=0, pooled=False):
         for t, s in enumerate(seeds):
             out[t] = epoch_perm(s, n)
         return out
-    sd = np.asarray(seeds, dtype=np.uint64).astype(np.int64)
-    nv.check(nv.lib().ure_host_randperm(sd.ctypes.data, len(sd), n, out.data_ptr(), int(threads or 0)), 'ure_host_randperm')
+    _expand(seeds, n, 0, out.data_ptr(), threads)
     return out
 
 
@@ -529,14 +543,20 @@ _EXPANDER = None
 _UPLOAD_STREAMS = {}
 
 
+def _upload_stream(device):
+    """The side stream of the calling thread on `device`: a worker's uploads and device inits go on its own."""
+    key = (device, threading.get_ident())
+    st = _UPLOAD_STREAMS.get(key)
+    if st is None:
+        st = _UPLOAD_STREAMS[key] = torch.cuda.Stream(device)
+    return st
+
+
 def epoch_tags(seeds, n, batch, threads=0):
     """[len(seeds), n] int16 (uint16 bits): tags[t][perm_t[b]] = b // batch for perm_t = the permutation of epoch_perms -- the
     step of the epoch in which every interaction trains (ure_host_randperm_tags; struct ure_shard: file_tags)."""
-    from . import _native as nv
-    nv.lib()
-    sd = np.asarray(seeds, dtype=np.uint64).astype(np.int64)
-    out = torch.empty((len(sd), int(n)), dtype=torch.int16)
-    nv.check(nv.lib().ure_host_randperm_tags(sd.ctypes.data, len(sd), int(n), int(batch), out.data_ptr(), int(threads or 0)), 'ure_host_randperm_tags')
+    out = torch.empty((len(seeds), int(n)), dtype=torch.int16)
+    _expand(seeds, n, batch, out.data_ptr(), threads)
     return out
 
 
@@ -578,7 +598,6 @@ def epoch_perms_async(seeds, n, threads=0, pooled=False, device=None, tags_batch
     tags_batch = tags_batch_for(n, tags_batch, honour_env=False)
     word = torch.int16 if tags_batch else torch.int32
     out = POOL.take((len(seeds), n), word) if pooled else torch.empty(len(seeds), n, dtype=word)
-    sd = np.asarray(seeds, dtype=np.uint64).astype(np.int64)
 
     on_dev = ready = None
     if device is not None and torch.device(device).type == 'cuda':
@@ -590,23 +609,18 @@ def epoch_perms_async(seeds, n, threads=0, pooled=False, device=None, tags_batch
         ready.record(torch.cuda.current_stream(dev))
 
     def work():
-        if tags_batch:
-            nv.check(nv.lib().ure_host_randperm_tags(sd.ctypes.data, len(sd), n, tags_batch, out.data_ptr(), int(threads or 0)), 'ure_host_randperm_tags')
-        else:
-            nv.check(nv.lib().ure_host_randperm(sd.ctypes.data, len(sd), n, out.data_ptr(), int(threads or 0)), 'ure_host_randperm')
+        _expand(seeds, n, tags_batch, out.data_ptr(), threads)
         if on_dev is None:
             return out
         dev = on_dev.device
         with torch.cuda.device(dev):
-            st = _UPLOAD_STREAMS.get(dev)
-            if st is None:
-                st = _UPLOAD_STREAMS[dev] = torch.cuda.Stream(dev)
+            st = _upload_stream(dev)                    # (this executor has one thread: one stream per device)
             st.wait_event(ready)
             with torch.cuda.stream(st):
                 on_dev.copy_(out, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(st)
-        whole = Chunk(len(sd))
+        whole = Chunk(len(seeds))
         whole.put(ev)
         on_dev._ure_arrival = Arrival([whole], host=out, whole=True)
         return on_dev
@@ -638,53 +652,49 @@ class _DrawsTask:
                  buffers=True):
         from . import _native as nv
         nv.lib()
-        self.args = (start_state, n_user, n_item, k, epochs, with_total_test, n_rows, shuffle, int(threads or 0), want_perms)
+        self.start_state, self.n_user, self.n_item, self.k = start_state, n_user, n_item, k
+        self.epochs, self.with_total_test, self.n_rows, self.shuffle = epochs, with_total_test, n_rows, shuffle
+        self.threads, self.want_perms, self.chunk_epochs = int(threads or 0), want_perms, chunk_epochs
         self.device = torch.device(device) if device is not None and torch.device(device).type == 'cuda' else None
+        # tags_batch = B > 0: the permutations leave the host as BATCH TAGS (tags_batch_for; engine.TrainJob tells them from permutations
+        # by their dtype) -- half the bytes on PCIe, and no partition phases on the device.  Only on the chunked device path.
+        self.tags_batch = tags_batch_for(n_rows, tags_batch, honour_env=False) if self.device is not None else 0
         self.host = self.on_dev = self.ready = self.stream = self.arrival = None
         self.init_value = self.perms_value = None
         self.init_done, self.error = threading.Event(), None
         self.sharers = 1                            # inits of the same call running beside this one (start_inits)
         self.seeds = None                           # (a caller that knows them -- shard_streams(want_seeds=True) -- sets them: _task_of)
-        self._buffer_args = (chunk_epochs, tags_batch)
         if buffers:
             self.make_buffers()
 
-    def _buffer_plan(self):
-        """-> (word type, epochs, rows) of the buffers chunks() fills and uploads, or None (no permutations, or not on a device)."""
-        _, tags_batch = self._buffer_args
-        _, _, _, _, epochs, _, n_rows, shuffle, _, want_perms = self.args
-        # tags_batch = B > 0: the permutations leave the host as BATCH TAGS (tags_batch_for; engine.TrainJob tells them from permutations
-        # by their dtype) -- half the bytes on PCIe, and no partition phases on the device.  Only on the chunked device path.
-        self.tags_batch = tags_batch_for(n_rows, tags_batch, honour_env=False) if self.device is not None else 0
-        if not (want_perms and shuffle and n_rows > 0 and epochs > 0 and n_rows < RANDPERM_HUGE_N):
+    def _word(self):
+        """-> the word type of the [epochs, n_rows] buffers chunks() fills and uploads, or None (no permutations to expand)."""
+        if not (self.want_perms and self.shuffle and self.n_rows > 0 and self.epochs > 0 and self.n_rows < RANDPERM_HUGE_N):
             return None
-        return (torch.int16 if self.tags_batch else torch.int32), epochs, n_rows
+        return torch.int16 if self.tags_batch else torch.int32
 
     def _adopt(self, host, on_dev, ready, shared=None):
         """Take the buffers (views of a block all shards of a call share, or this shard's own)."""
-        chunk_epochs, _ = self._buffer_args
-        _, _, _, _, epochs, _, n_rows = self.args[:7]
         self.host, self.on_dev, self.ready = host, on_dev, ready
         if on_dev is None:
             return
         # chunks of at least chunk_epochs epochs and ~4 MB: every chunk costs its worker ~0.1 ms of Python (slices, a copy,
         # an event) under the GIL, and a request of 16 small shards had 112 of them competing with the calling thread
-        chunk_epochs = max(int(chunk_epochs), -(-(4 << 20) // ((2 if self.tags_batch else 4) * n_rows)))
-        self.arrival = on_dev._ure_arrival = Arrival([Chunk(min(epochs, c0 + chunk_epochs)) for c0 in range(0, epochs, chunk_epochs)], host, shared)
+        step = max(int(self.chunk_epochs), -(-(4 << 20) // ((2 if self.tags_batch else 4) * self.n_rows)))
+        self.arrival = on_dev._ure_arrival = Arrival([Chunk(min(self.epochs, c0 + step)) for c0 in range(0, self.epochs, step)], host, shared)
         if self.error is not None:                  # the init failed before the buffers were there: never leave a consumer waiting
             self.arrival.fail(self.error)
 
     def make_buffers(self):
         """The permutations' host and device buffers and events, on the CALLING thread (the pool and the allocator see the caller's
         current stream).  init() does not need them (start_inits), chunks() does."""
-        plan = self._buffer_plan()
-        if plan is None:
+        word = self._word()
+        if word is None:
             return
-        word, epochs, n_rows = plan
-        host = POOL.take((epochs, n_rows), word)
+        host = POOL.take((self.epochs, self.n_rows), word)
         on_dev = ready = None
         if self.device is not None:
-            on_dev = torch.empty((epochs, n_rows), dtype=word, device=self.device)
+            on_dev = torch.empty((self.epochs, self.n_rows), dtype=word, device=self.device)
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream(self.device))
         self._adopt(host, on_dev, ready)
@@ -696,82 +706,63 @@ class _DrawsTask:
         if self.arrival is not None:
             self.arrival.fail(exc)
 
-    def _upload_stream(self):
-        """The side stream of the calling worker thread."""
-        key = (self.device, threading.get_ident())
-        st = _UPLOAD_STREAMS.get(key)
-        if st is None:
-            st = _UPLOAD_STREAMS[key] = torch.cuda.Stream(self.device)
-        return st
-
     def seeds_first(self):
         """The per-epoch seeds WITHOUT the model init: they follow the four fills in the stream, whose lengths are known, so a generator
         moved past them (ure_host_mt_advance) draws them at once -- and the permutations, the bulk of a request's host work, are expanded
         beside the inits instead of behind them.  False: the tables are too small to skip (the seeds come with init())."""
         if self.seeds is not None:
             return True
-        start_state, n_user, n_item, k, epochs, with_total_test = self.args[:6]
-        draws = model_draws(n_user, n_item, k, 0, False)
+        draws = model_draws(self.n_user, self.n_item, self.k, 0, False)
         if draws is None:
             return False
         # (one native call: the state is copied, moved past the four fills and asked for the epochs' int64 draws -- as `random_()` makes them)
         from . import _native as nv
-        per = 4 if with_total_test else 3
-        vals = np.empty(max(epochs, 0) * per, dtype=np.int64)
-        nv.check(nv.lib().ure_host_draw_int64(start_state.data_ptr(), start_state.numel(), int(draws[0] + draws[1]), len(vals), vals.ctypes.data),
+        per = 4 if self.with_total_test else 3
+        vals = np.empty(max(self.epochs, 0) * per, dtype=np.int64)
+        nv.check(nv.lib().ure_host_draw_int64(self.start_state.data_ptr(), self.start_state.numel(), int(draws[0] + draws[1]), len(vals), vals.ctypes.data),
                  'ure_host_draw_int64')
         self.seeds = vals[1::per].tolist()
         return True
 
     def init(self):
-        start_state, n_user, n_item, k, epochs, with_total_test = self.args[:6]
+        """This shard's model init on the calling worker: the fills by mf_init, uploaded on the worker's side stream."""
         from .engine import mark
         mark('w: init start')
         g = torch.Generator()
-        g.set_state(start_state)
-        init = mf_init(n_user, n_item, k, generator=g, threads=fill_threads((n_user + n_item) * k, self.sharers))
-        seeds = epoch_seeds(epochs, with_total_test, generator=g)
-        if self.seeds is None:
-            self.seeds = seeds
+        g.set_state(self.start_state)
+        init = mf_init(self.n_user, self.n_item, self.k, generator=g, threads=fill_threads((self.n_user + self.n_item) * self.k, self.sharers))
         mark('w: init drawn')
+        ev = None
         if self.device is not None:
             # the init tables go up first, on a side stream of this worker
-            dev = self.device
-            with torch.cuda.device(dev):
-                st = self._upload_stream()
+            with torch.cuda.device(self.device):
+                st = _upload_stream(self.device)
                 with torch.cuda.stream(st):
-                    up = tuple(t.to(dev) for t in init)
-                    ev0 = torch.cuda.Event()
-                    ev0.record(st)
-            for t in up:
-                t._ure_event = ev0
-            init = up
-        self.init_value = init
-        self.init_done.set()
+                    init = tuple(t.to(self.device) for t in init)
+                    ev = torch.cuda.Event()
+                    ev.record(st)
+        _inits_done([self], [g.get_state()], [init], ev)
 
     def chunks(self):
         """Generator: every step expands (and uploads) one chunk of epochs; the permutations are complete when it ends."""
-        from . import _native as nv
-        _, _, _, _, epochs, _, n_rows, shuffle, threads, want_perms = self.args
-        if not want_perms:
+        epochs, n_rows, threads = self.epochs, self.n_rows, self.threads
+        if not self.want_perms:
             return
-        if not shuffle:
+        if not self.shuffle:
             self.perms_value = torch.arange(n_rows, dtype=torch.int32).repeat(epochs, 1)
             return
         if self.host is None:
             self.perms_value = epoch_perms(self.seeds, n_rows, threads)
             return
-        sd = np.asarray(self.seeds, dtype=np.uint64).astype(np.int64)
-        L = nv.lib()
         if self.on_dev is None:
-            nv.check(L.ure_host_randperm(sd.ctypes.data, len(sd), n_rows, self.host.data_ptr(), threads), 'ure_host_randperm')
+            _expand(self.seeds, n_rows, 0, self.host.data_ptr(), threads)
             self.perms_value = self.host
             return
         from .engine import mark
         dev, on_dev, host = self.device, self.on_dev, self.host
         with torch.cuda.device(dev):
-            st = self._upload_stream()
-        sd_ptr, host_ptr, row_bytes = sd.ctypes.data, host.data_ptr(), (2 if self.tags_batch else 4) * n_rows
+            st = _upload_stream(dev)
+        host_ptr, row_bytes = host.data_ptr(), (2 if self.tags_batch else 4) * n_rows
         self.perms_value = on_dev
         first = True
         c0 = 0
@@ -779,10 +770,7 @@ class _DrawsTask:
             c1 = chunk.end
             if _TEST_CHUNK_DELAY_S:
                 time.sleep(_TEST_CHUNK_DELAY_S)
-            if self.tags_batch:
-                nv.check(L.ure_host_randperm_tags(sd_ptr + 8 * c0, c1 - c0, n_rows, self.tags_batch, host_ptr + row_bytes * c0, threads), 'ure_host_randperm_tags')
-            else:
-                nv.check(L.ure_host_randperm(sd_ptr + 8 * c0, c1 - c0, n_rows, host_ptr + row_bytes * c0, threads), 'ure_host_randperm')
+            _expand(self.seeds[c0:c1], n_rows, self.tags_batch, host_ptr + row_bytes * c0, threads)
             with torch.cuda.device(dev), torch.cuda.stream(st):
                 if first:
                     st.wait_event(self.ready)
@@ -836,31 +824,36 @@ class _SharedBlock:
             POOL.give(self.block)
 
 
+def _pack(sizes):
+    """Buffers of `sizes` elements laid end to end in one allocation, each starting at a multiple of 64 elements
+    -> (their element offsets, the total)."""
+    offs, at = [], 0
+    for n in sizes:
+        offs.append(at)
+        at += (n + 63) // 64 * 64
+    return offs, at
+
+
 def make_buffers_together(tasks):
     """make_buffers for the shards of one call from ONE host block, ONE device allocation and one event (a buffer, an allocation and an
     event per shard were 16 x 0.1-0.2 ms of the calling thread at 16 shards, beside 16 busy init workers).  Shards that cannot share
     (no device, another word type) get their own."""
-    plans = [(t, t._buffer_plan()) for t in tasks]
-    share = [(t, p) for t, p in plans if p is not None and t.device is not None]
-    if len(share) < 2 or len({(p[0], str(t.device)) for t, p in share}) != 1:
+    share = [t for t in tasks if t._word() is not None and t.device is not None]
+    if len(share) < 2 or len({(t._word(), str(t.device)) for t in share}) != 1:
         share = []
     if share:
-        word, dev = share[0][1][0], share[0][0].device
-        al = lambda x: (x + 63) // 64 * 64
-        offs, at = [], 0
-        for _, (_, epochs, n_rows) in share:
-            offs.append(at)
-            at += al(epochs * n_rows)
-        host_all = POOL.take((at,), word)
-        dev_all = torch.empty(at, dtype=word, device=dev)
+        word, dev = share[0]._word(), share[0].device
+        offs, total = _pack([t.epochs * t.n_rows for t in share])
+        host_all = POOL.take((total,), word)
+        dev_all = torch.empty(total, dtype=word, device=dev)
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(dev))
         block = _SharedBlock(host_all, len(share))
-        for (t, (_, epochs, n_rows)), o in zip(share, offs):
-            t._adopt(host_all[o:o + epochs * n_rows].view(epochs, n_rows), dev_all[o:o + epochs * n_rows].view(epochs, n_rows), ready, block)
-    shared = {id(t) for t, _ in share}
-    for t, p in plans:
-        if id(t) not in shared:
+        for t, o in zip(share, offs):
+            shape, end = (t.epochs, t.n_rows), o + t.epochs * t.n_rows
+            t._adopt(host_all[o:end].view(shape), dev_all[o:end].view(shape), ready, block)
+    for t in tasks:
+        if t not in share:
             t.make_buffers()
 
 
@@ -910,6 +903,58 @@ def default_tag_bounds(epochs, n_shards, n_max):
     return bounds
 
 
+def _device_tags_possible(tasks):
+    """Whether every shard of a call can take its tags from the device: batch tags wanted, no more than 2^27 rows, ONE device, the same
+    epochs, and seeds that come without the init (_DrawsTask.seeds_first, which draws them here)."""
+    if not tasks or any(t._word() != torch.int16 or t.n_rows > DEVICE_TAGS_MAX_ROWS or t.device is None for t in tasks):
+        return False
+    if len({str(t.device) for t in tasks}) != 1 or not all(t.seeds_first() for t in tasks):
+        return False
+    return all(t.epochs == tasks[0].epochs for t in tasks)
+
+
+def perm_table(seeds, n_rows, tags_batch, base, offs, bounds):
+    """The descriptor table (struct ure_perm) of a call's device shuffles, host arithmetic only: seeds[s][e] = the seed of shard s's epoch e,
+    n_rows[s] its rows, tags_batch its batch size (one for all, or one per shard); shard s's [epochs, n_rows[s]] int16 tags start offs[s]
+    elements behind the address `base`; bounds = the chunks' epoch boundaries [0, ..., epochs].
+    -> (the table in LAUNCH order -- chunk, shard, epoch: a launch holds chunk c of all shards --, [(lo, hi)]: every chunk's rows of it)."""
+    seeds = _seed_words(seeds)
+    S, epochs = seeds.shape
+    assert bounds[0] == 0 and bounds[-1] == epochs and all(a < b for a, b in zip(bounds[:-1], bounds[1:]))
+    n_of = np.asarray(n_rows, dtype=np.int64)[:, None]
+    full = np.zeros((S, epochs), dtype=PERM_DTYPE)          # built shard by epoch and reordered once
+    full['seed'] = seeds
+    full['tags'] = int(base) + 2 * (np.asarray(offs, dtype=np.int64)[:, None] + np.arange(epochs, dtype=np.int64)[None, :] * n_of)
+    full['n'] = n_of
+    full['batch'] = np.asarray(tags_batch, dtype=np.int64).reshape(-1, 1)
+    table = np.concatenate([full[:, c0:c1].reshape(-1) for c0, c1 in zip(bounds[:-1], bounds[1:])])
+    ends = [S * c1 for c1 in bounds]
+    return table, list(zip(ends[:-1], ends[1:]))
+
+
+def _shuffle_scratch(launches, n_max, dev):
+    """The work memory of a call's shuffle launches, one block per method: the launches follow each other on one stream, so those of a
+    method share a block sized for the largest of them.  -> ({method: (block, words, permutations at a time)}, [the blocks' flag words,
+    zeroed: Arrival.check reads them])."""
+    from . import _native as nv
+    L = nv.lib()
+    at_a_time = {}
+    for _, lo, hi, how in launches:
+        at_a_time[how] = max(at_a_time.get(how, 0), hi - lo if how == 'chain' else min(DEVICE_TAGS_GROUPS, hi - lo))
+    scratch, flags = {}, []
+    for how, n_p in at_a_time.items():
+        if how == 'chain':
+            words, at = int(L.ure_device_shuffle_tags_scratch(n_max, n_p)), int(L.ure_device_shuffle_tags_flag(n_max, n_p))
+            n_flags = 1
+        else:
+            words, at = int(L.ure_device_randperm_tags_scratch(n_max, n_p)), 2 * ((n_max + 63) // 64 * 64) * n_p
+            n_flags = n_p                                    # a word per workgroup: 0xdead if it ever gave up (device_tags_check)
+        block = torch.empty(words, dtype=torch.int32, device=dev)
+        flags.append(block[at:at + n_flags].zero_())
+        scratch[how] = (block, words, n_p)
+    return scratch, flags
+
+
 def device_tags(tasks, bounds=None, defer=False, method=None):
     """The batch tags of a call's shards made on the DEVICE instead of by host threads: the seeds come by skip-ahead
     (_DrawsTask.seeds_first), every (shard, epoch) is one entry of ONE descriptor table, and the epochs go out in a few launches on a
@@ -920,108 +965,59 @@ def device_tags(tasks, bounds=None, defer=False, method=None):
     bounds: the chunks' epoch boundaries [0, ..., epochs] instead of default_tag_bounds.  defer: nothing is launched here; -> fire(c),
     which launches chunk c (in order) -- bench.py puts the shuffles of the epochs it times inside its clock."""
     from . import _native as nv
-    from .engine import upload_many
-    plans = [t._buffer_plan() for t in tasks]
-    if not tasks or any(p is None or p[0] != torch.int16 or p[2] > DEVICE_TAGS_MAX_ROWS or t.device is None for t, p in zip(tasks, plans)):
+    from .engine import mark, upload_many
+    if not _device_tags_possible(tasks):
         return False
-    if len({str(t.device) for t in tasks}) != 1 or not all(t.seeds_first() for t in tasks):
-        return False
-    dev = tasks[0].device
-    epochs = plans[0][1]
-    if any(p[1] != epochs for p in plans):
-        return False
-    al = lambda x: (x + 63) // 64 * 64
-    offs, at = [], 0
-    for _, e, n_rows in plans:
-        offs.append(at)
-        at += al(e * n_rows)
-    from .engine import mark
+    dev, epochs, n_rows = tasks[0].device, tasks[0].epochs, [t.n_rows for t in tasks]
+    n_max = max(n_rows)
+    offs, total = _pack([epochs * n for n in n_rows])
     mark('tags: start')
     main = torch.cuda.current_stream(dev)
-    dev_all = torch.empty(at, dtype=torch.int16, device=dev)
-    S = len(tasks)
-    n_max = max(p[2] for p in plans)
-    if bounds is None:
-        bounds = default_tag_bounds(epochs, S, n_max)
-    bounds = [int(b) for b in bounds]
-    assert bounds[0] == 0 and bounds[-1] == epochs and all(a < b for a, b in zip(bounds[:-1], bounds[1:]))
-    # the table in launch order -- (chunk, shard, epoch) --, built shard by epoch and reordered once
-    n_of = np.array([p[2] for p in plans], dtype=np.int64)
-    full = np.zeros((S, epochs), dtype=PERM_DTYPE)
-    full['seed'] = np.array([t.seeds for t in tasks], dtype=np.uint64).astype(np.int64)
-    full['tags'] = dev_all.data_ptr() + 2 * (np.array(offs, dtype=np.int64)[:, None] + np.arange(epochs, dtype=np.int64)[None, :] * n_of[:, None])
-    full['n'] = n_of[:, None]
-    full['batch'] = np.array([t.tags_batch for t in tasks], dtype=np.int64)[:, None]
-    table = np.concatenate([full[:, c0:c1].reshape(-1) for c0, c1 in zip(bounds[:-1], bounds[1:])])
-    launches, at_row = [], 0
-    for c, (c0, c1) in enumerate(zip(bounds[:-1], bounds[1:])):
-        n_p = S * (c1 - c0)
-        launches.append((c1, at_row, at_row + n_p, shuffle_method(n_max, n_p, method), 0))          # (one side stream: chunks alternating between two ran beside each other and took
-                                                                                        # longer each -- 12.8 against 9.2 ms of shuffle kernels per six requests, the 16-shard request 11.7 against 9.3 ms)
-        at_row += n_p
+    dev_all = torch.empty(total, dtype=torch.int16, device=dev)
+    bounds = [int(b) for b in (default_tag_bounds(epochs, len(tasks), n_max) if bounds is None else bounds)]
+    table, ranges = perm_table([t.seeds for t in tasks], n_rows, [t.tags_batch for t in tasks], dev_all.data_ptr(), offs, bounds)
+    launches = [(end, lo, hi, shuffle_method(n_max, hi - lo, method)) for end, (lo, hi) in zip(bounds[1:], ranges)]
     mark('tags: table')
-    L = nv.lib()
-    sides = _PERM_STREAMS.get(str(dev))
-    if sides is None:
-        sides = _PERM_STREAMS[str(dev)] = (torch.cuda.Stream(dev),)      # (stream priorities change nothing here: measured, profiles/r05/NOTES.md)
-    # scratch per (side stream, method): the launches of a stream follow each other, so they share it
-    scratch, flags, keep = {}, [], [dev_all]
-    for _, lo, hi, how, side in launches:
-        if how == 'chain':
-            want = (int(L.ure_device_shuffle_tags_scratch(n_max, hi - lo)), hi - lo)
-        else:
-            groups = min(DEVICE_TAGS_GROUPS, hi - lo)
-            want = (int(L.ure_device_randperm_tags_scratch(n_max, groups)), groups)
-        have = scratch.get((side, how))
-        if have is None or want[1] > have[1]:
-            scratch[(side, how)] = want
-    n_al = al(n_max)
-    for (side, how), (words, n_p) in list(scratch.items()):
-        block = torch.empty(words, dtype=torch.int32, device=dev)
-        if how == 'chain':
-            flag_at = int(L.ure_device_shuffle_tags_flag(n_max, n_p))
-            f = block[flag_at:flag_at + 1]
-        else:
-            f = block[2 * n_al * n_p:2 * n_al * n_p + n_p]           # a word per workgroup: 0xdead if it ever gave up (device_tags_check)
-        f.zero_()
-        flags.append(f)
-        keep.append(block)
-        scratch[(side, how)] = (block, words, n_p)
+    # ONE side stream per device: chunks alternating between two ran beside each other and took longer each -- 12.8 against 9.2 ms of shuffle
+    # kernels per six requests, the 16-shard request 11.7 against 9.3 ms.  (Stream priorities change nothing here: measured, profiles/r05/NOTES.md)
+    side = _PERM_STREAMS.get(str(dev))
+    if side is None:
+        side = _PERM_STREAMS[str(dev)] = torch.cuda.Stream(dev)
+    scratch, flags = _shuffle_scratch(launches, n_max, dev)
     mark('tags: scratch')
     table_dev = upload_many([table.view(np.uint8)], dev)[0]
-    keep.append(table_dev)
-    # (the blocks are made on the caller's stream and worked on by the side streams: the allocator must not hand them to anybody
-    # else before the side streams are through with them, whatever becomes of the request -- ADVICE r4)
+    # (the blocks are made on the caller's stream and worked on by the side stream: the allocator must not hand them to anybody
+    # else before the side stream is through with them, whatever becomes of the request -- ADVICE r4)
+    keep = [dev_all] + [block for block, _, _ in scratch.values()] + [table_dev]
     for block in keep:
-        for side in sides:
-            block.record_stream(side)
+        block.record_stream(side)
     ready = torch.cuda.Event()
     ready.record(main)
-    for side in sides:
-        side.wait_event(ready)
-    chunks = [Chunk(c1) for c1, *_ in launches]         # (the same for every shard: a launch holds chunk c of all of them)
+    side.wait_event(ready)
+    chunks = [Chunk(end) for end, *_ in launches]       # (the same for every shard: a launch holds chunk c of all of them)
+    L = nv.lib()
 
     def fire(c):
-        c1, lo, hi, how, side = launches[c]
-        block, words, n_p = scratch[(side, how)]
+        _, lo, hi, how = launches[c]
+        block, words, n_p = scratch[how]
         ptr = table_dev.data_ptr() + lo * PERM_DTYPE.itemsize
         if how == 'chain':
-            nv.check(L.ure_device_shuffle_tags(ptr, hi - lo, n_max, block.data_ptr(), words, 0, sides[side].cuda_stream), 'ure_device_shuffle_tags')
+            nv.check(L.ure_device_shuffle_tags(ptr, hi - lo, n_max, block.data_ptr(), words, 0, side.cuda_stream), 'ure_device_shuffle_tags')
         else:
-            nv.check(L.ure_device_randperm_tags(ptr, hi - lo, n_max, block.data_ptr(), words, n_p, sides[side].cuda_stream), 'ure_device_randperm_tags')
+            nv.check(L.ure_device_randperm_tags(ptr, hi - lo, n_max, block.data_ptr(), words, n_p, side.cuda_stream), 'ure_device_randperm_tags')
         ev = torch.cuda.Event()
-        ev.record(sides[side])
+        ev.record(side)
         chunks[c].put(ev)
     mark('tags: uploaded')
     if not defer:
         for c in range(len(launches)):
             fire(c)
     mark('tags: launched')
-    for t, (_, e, n_rows), o in zip(tasks, plans, offs):
-        on_dev = dev_all[o:o + e * n_rows].view(e, n_rows)
+    for t, n, o in zip(tasks, n_rows, offs):
+        on_dev = dev_all[o:o + epochs * n].view(epochs, n)
         t.host, t.on_dev, t.ready = None, on_dev, ready
         t.arrival = on_dev._ure_arrival = Arrival(chunks, flags=flags, keep=keep)      # (keep: alive as long as the tags are)
-        on_dev._ure_methods = [how for *_, how, _ in launches]                         # (bench.py reads it: each chunk's shuffle)
+        on_dev._ure_methods = [how for *_, how in launches]                            # (bench.py reads it: each chunk's shuffle)
         t.perms_value = on_dev
     return fire if defer else True
 
@@ -1044,11 +1040,29 @@ def _task_of(sp, buffers=True):
     return t
 
 
-def _guarded_init(t):
+def _inits_done(tasks, states, tables, event=None):
+    """The end of every init route: states[i] = task i's generator state behind its fills, where the epochs' seeds follow in the stream
+    (drawn here unless the task has them: seeds_first, _task_of); tables[i] = its (U0, V0), tagged with `event` -- the end of their upload or
+    of the kernels that make them on a side stream, which consumers wait for -- when there is one."""
+    for t, st, (U0, V0) in zip(tasks, states, tables):
+        if t.seeds is None:
+            g = torch.Generator()
+            g.set_state(st)
+            t.seeds = epoch_seeds(t.epochs, t.with_total_test, generator=g)
+        if event is not None:
+            U0._ure_event = V0._ure_event = event
+        t.init_value = (U0, V0)
+    for t in tasks:
+        t.init_done.set()
+
+
+def _guarded_inits(tasks, route, *args):
+    """route(*args) makes the inits of `tasks`; whatever it raises fails every one of them (never leave a consumer waiting)."""
     try:
-        t.init()
+        route(*args)
     except BaseException as e:
-        t.fail(e)
+        for t in tasks:
+            t.fail(e)
         raise
 
 
@@ -1066,24 +1080,30 @@ def _submit_inits(tasks):
     call for all shards' fills and one upload (_batch_init), else a worker per shard."""
     pool = worker_pool()
     if tasks and _device_init_possible(tasks):
-        pool.submit(_device_init, tasks)
+        pool.submit(_guarded_inits, tasks, _device_init, tasks)
     elif len(tasks) > 1 and _batch_init_possible(tasks):
-        pool.submit(_batch_init, tasks)
+        pool.submit(_guarded_inits, tasks, _batch_init, tasks)
     else:
         for t in tasks:
             t.sharers = len(tasks)
-            pool.submit(_guarded_init, t)
+            pool.submit(_guarded_inits, [t], t.init)
 
 
 def _device_init_wanted(n_normals, device):
     return device is not None and torch.device(device).type == 'cuda' and n_normals >= DEVICE_INIT_MIN_NORMALS and device_fill_ok(device)
 
 
+def _same_tables(tasks):
+    """Whether the shards of a call can share one init: the same table sizes and seed draws, skippable fills, one device."""
+    a = tasks[0]
+    same = all((t.n_user, t.n_item, t.k, t.epochs, t.with_total_test, t.device) == (a.n_user, a.n_item, a.k, a.epochs, a.with_total_test, a.device)
+               for t in tasks)
+    return same and model_draws(a.n_user, a.n_item, a.k, 0, False) is not None
+
+
 def _device_init_possible(tasks):
-    a = tasks[0].args
-    if tasks[0].device is None or not all(t.args[1:4] == a[1:4] and t.args[4:6] == a[4:6] and t.device == tasks[0].device for t in tasks):
-        return False
-    return model_draws(a[1], a[2], a[3], 0, False) is not None and _device_init_wanted(len(tasks) * (a[1] + a[2]) * a[3], tasks[0].device)
+    a = tasks[0]
+    return a.device is not None and _same_tables(tasks) and _device_init_wanted(len(tasks) * (a.n_user + a.n_item) * a.k, a.device)
 
 
 def _device_init(tasks):
@@ -1091,39 +1111,23 @@ def _device_init(tasks):
     shard: csrc/mt_jump.cpp), the kernels run on this worker's side stream, every task gets its views and the event consumers wait for.
     No host normals, no upload -- 909 M values and 3.6 GB at BASELINE.json configs[3]."""
     from .engine import mark
-    try:
-        mark('w: init start')
-        _, n_user, n_item, k, epochs, with_total_test = tasks[0].args[:6]
-        draws = model_draws(n_user, n_item, k, 0, False)
-        dev = tasks[0].device
-        states = [t.args[0].clone() for t in tasks]
-        with torch.cuda.device(dev):
-            up = tasks[0]._upload_stream()
-            out = mf_init_device(states, n_user * k, n_item * k, draws[0], dev, stream=up)
-            ev = torch.cuda.Event()
-            ev.record(up)
-        for t, st, (U0, V0) in zip(tasks, states, out):
-            if t.seeds is None:                          # (the epochs' seeds follow the fills in the stream)
-                g = torch.Generator()
-                g.set_state(st)
-                t.seeds = epoch_seeds(epochs, with_total_test, generator=g)
-            U0, V0 = U0.view(n_user, k), V0.view(n_item, k)
-            U0._ure_event = V0._ure_event = ev
-            t.init_value = (U0, V0)
-        mark('w: init queued on the device')
-        for t in tasks:
-            t.init_done.set()
-    except BaseException as e:
-        for t in tasks:
-            t.fail(e)
-        raise
+    mark('w: init start')
+    a = tasks[0]
+    draws = model_draws(a.n_user, a.n_item, a.k, 0, False)
+    states = [t.start_state.clone() for t in tasks]
+    with torch.cuda.device(a.device):
+        up = _upload_stream(a.device)
+        out = mf_init_device(states, a.n_user * a.k, a.n_item * a.k, draws[0], a.device, stream=up)
+        ev = torch.cuda.Event()
+        ev.record(up)
+    _inits_done(tasks, states, [(U0.view(a.n_user, a.k), V0.view(a.n_item, a.k)) for U0, V0 in out], ev)
+    mark('w: init queued on the device')
 
 
 def _batch_init_possible(tasks):
-    a = tasks[0].args
-    return (native_fill_ok() and all(t.args[1:4] == a[1:4] and t.args[4:6] == a[4:6] and t.device == tasks[0].device for t in tasks)
-            and model_draws(a[1], a[2], a[3], 0, False) is not None
-            and len(tasks) * (a[1] + a[2]) * a[3] * 4 <= (256 << 20))          # (one pinned block for all of them: small tables only)
+    a = tasks[0]
+    return (native_fill_ok() and _same_tables(tasks)
+            and len(tasks) * (a.n_user + a.n_item) * a.k * 4 <= (256 << 20))          # (one pinned block for all of them: small tables only)
 
 
 def _batch_init(tasks):
@@ -1132,51 +1136,34 @@ def _batch_init(tasks):
     configs[4] -- kept each other and the calling thread waiting for the interpreter lock: the layouts' worker started 2 ms late.)"""
     from . import _native as nv
     from .engine import mark
-    try:
-        mark('w: init start')
-        _, n_user, n_item, k, epochs, with_total_test = tasks[0].args[:6]
-        S, nu, nv_ = len(tasks), n_user * k, n_item * k
-        draws = model_draws(n_user, n_item, k, 0, False)
-        block = POOL.take((S, nu + nv_), torch.float32)
-        states = [t.args[0].clone() for t in tasks]
-        st_a = (ctypes.c_void_p * S)(*[x.data_ptr() for x in states])
-        base, row = block.data_ptr(), 4 * (nu + nv_)
-        u_a = (ctypes.c_void_p * S)(*[base + s * row for s in range(S)])
-        v_a = (ctypes.c_void_p * S)(*[base + s * row + 4 * nu for s in range(S)])
-        skip = (ctypes.c_int64 * S)(*([int(draws[0])] * S))
-        nv.check(nv.lib().ure_host_mf_init_batch(S, st_a, states[0].numel(), skip, u_a, nu, v_a, nv_, host_cpus()), 'ure_host_mf_init_batch')
-        _count(skipped_draws=S * draws[0], normals=S * (n_user + n_item) * k)
-        per = 4 if with_total_test else 3
-        for t, st in zip(tasks, states):
-            if t.seeds is None:                          # (the epochs' seeds follow the fills in the stream)
-                g = torch.Generator()
-                g.set_state(st)
-                t.seeds = epoch_seeds(epochs, with_total_test, generator=g)
-        mark('w: init drawn')
-        dev = tasks[0].device
-        if dev is not None:
-            with torch.cuda.device(dev):
-                up = tasks[0]._upload_stream()
-                with torch.cuda.stream(up):
-                    on_dev = block.to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(up)
-            POOL.give(block, ev)
-            for s, t in enumerate(tasks):
-                U0, V0 = on_dev[s, :nu].view(n_user, k), on_dev[s, nu:].view(n_item, k)
-                U0._ure_event = V0._ure_event = ev
-                t.init_value = (U0, V0)
-        else:
-            host = block.clone()
-            POOL.give(block)
-            for s, t in enumerate(tasks):
-                t.init_value = (host[s, :nu].view(n_user, k), host[s, nu:].view(n_item, k))
-        for t in tasks:
-            t.init_done.set()
-    except BaseException as e:
-        for t in tasks:
-            t.fail(e)
-        raise
+    mark('w: init start')
+    a = tasks[0]
+    n_user, n_item, k, dev = a.n_user, a.n_item, a.k, a.device
+    S, nu, nv_ = len(tasks), n_user * k, n_item * k
+    draws = model_draws(n_user, n_item, k, 0, False)
+    block = POOL.take((S, nu + nv_), torch.float32)
+    states = [t.start_state.clone() for t in tasks]
+    st_a = (ctypes.c_void_p * S)(*[x.data_ptr() for x in states])
+    base, row = block.data_ptr(), 4 * (nu + nv_)
+    u_a = (ctypes.c_void_p * S)(*[base + s * row for s in range(S)])
+    v_a = (ctypes.c_void_p * S)(*[base + s * row + 4 * nu for s in range(S)])
+    skip = (ctypes.c_int64 * S)(*([int(draws[0])] * S))
+    nv.check(nv.lib().ure_host_mf_init_batch(S, st_a, states[0].numel(), skip, u_a, nu, v_a, nv_, host_cpus()), 'ure_host_mf_init_batch')
+    _count(skipped_draws=S * draws[0], normals=S * (n_user + n_item) * k)
+    mark('w: init drawn')
+    ev = None
+    if dev is not None:
+        with torch.cuda.device(dev):
+            up = _upload_stream(dev)
+            with torch.cuda.stream(up):
+                tables = block.to(dev, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(up)
+        POOL.give(block, ev)
+    else:
+        tables = block.clone()
+        POOL.give(block)
+    _inits_done(tasks, states, [(tables[s, :nu].view(n_user, k), tables[s, nu:].view(n_item, k)) for s in range(S)], ev)
 
 
 def draws_batch_async(specs, n_workers=0, tasks=None):
@@ -1189,7 +1176,7 @@ def draws_batch_async(specs, n_workers=0, tasks=None):
     started = tasks is not None                      # (start_inits: the inits are running already)
     if started:
         for t, sp in zip(tasks, specs):
-            t.args = t.args[:8] + (int(sp.get('threads', 0) or 0),) + t.args[9:]
+            t.threads = int(sp.get('threads', 0) or 0)
     else:
         tasks = [_task_of(sp, buffers=False) for sp in specs]
     on_device = device_tags_wanted() and device_tags(tasks)
