@@ -626,6 +626,33 @@ int ure_ridge_rows(const float *F, int64_t n_fixed, int d, int k, const int64_t 
                    void *stream);
 
 /* ---------------------------------------------------------------------------
+ * OT grouping on the sparse rating matrix (csrc/csr_group.hip; new symbols, the ABI number is unchanged): the cost and
+ * the centroid update of 'rating-ot' read the ratings as CSR / CSC and never form the n_user x n_item array.  Not parity:
+ * the reference's own branch raises (utils.py:637 on a csr_matrix); the arithmetic is stated in numpy in
+ * ultrare_amd/sparse_group.py and the kernels are held to it bit for bit.
+ * ------------------------------------------------------------------------- */
+/* row_off [n + 1] int64, col [nnz] int32 (ascending inside a row, no repeats), val [nnz] fp32: a device CSR of n rows over
+ * n_item columns.  Ct (device, [n_item][ldc] fp32, ldc >= k): the k centroids TRANSPOSED, the k values of an item contiguous.
+ * cc[c] = |C_c|^2 in float64: lane l of 256 adds Ct[j][c]^2 for j = l, l + 256, ... in ascending j from +0.0, then the 256
+ * lane sums are added in ascending l (a first small launch writes the k values into scratch).  For row i and centroid c, over
+ * the row's stored entries in ascending column, sequentially in float64 from +0.0: dot = sum x_ij Ct[j][c], xx = sum x_ij^2;
+ * dist[c][i] = (float)max((xx - 2 dot) + cc[c], 0.0), dist (device) [k][n] fp32 as ure_ot_cost lays it out.  An empty row
+ * gives (float)cc[c].  1 <= k <= 256, 1 <= n, n_item < 2^31; a column index outside [0, n_item) is read as the nearest
+ * valid one (callers check their matrices).  scratch (device): ure_csr_cost_scratch(k) = 8 k bytes (-1 for k outside
+ * 1 .. 256).  No floating-point atomics and no sum split across lanes: an entry's bytes depend on its own row and the
+ * centroids alone, on any stream, whatever other rows share the call.  Nothing synchronises. */
+int64_t ure_csr_cost_scratch(int k);
+int ure_csr_cost(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, const float *Ct, int ldc, int k,
+                 float *dist, void *scratch, int64_t scratch_bytes, void *stream);
+/* col_off [n_item + 1] int64, row [nnz] int32 (ascending inside a column), val [nnz] fp32: the CSC of the same matrix;
+ * label (device, int32 [n]) in [0, k).  counts[c] (device, int32 [k]) = members of cluster c.  S[c][j] = the sequential
+ * float64 sum from +0.0, in ascending user id, of the entries of column j whose user has label c; Ct[j][c] = (float)(S[c][j] /
+ * (double)counts[c]), and 0 for a cluster without members (counts says so; callers raise).  Ct [n_item][ldc]: columns
+ * k .. ldc - 1 are not written.  Limits and guarantees as ure_csr_cost; a label outside [0, k) joins no cluster. */
+int ure_csr_centroids(const int64_t *col_off, const int32_t *row, const float *val, const int32_t *label, int64_t n, int64_t n_item, int k,
+                      float *Ct, int ldc, int32_t *counts, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Comparison clusterers (utils.py:354-418: k-means / balanced k-means on the user embedding;
  * never called on the reference's CLI path, kept for the OT-vs-k-means comparison of its notebook)
  * ------------------------------------------------------------------------- */

@@ -141,6 +141,9 @@ _PROTOTYPES = {
     'ure_ridge_rows_scratch': (_i64, [_i64, ctypes.c_int]),
     'ure_ridge_rows': (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _vp, ctypes.c_double, ctypes.c_double,
                                       _vp, _vp, _vp, _i64, _vp]),
+    'ure_csr_cost_scratch': (_i64, [ctypes.c_int]),
+    'ure_csr_cost': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _i64, _vp]),
+    'ure_csr_centroids': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

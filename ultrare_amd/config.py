@@ -154,7 +154,7 @@ class Instance(object):
         else:
             val_mat = readSparseMat(self.param.train_dir, self.param.n_user, self.param.n_item) \
                 if group_type.startswith('rating') else None
-            user_mat = self._full_user_mat()
+            user_mat = None if group_type.startswith('rating') else self._full_user_mat()       # the ratings need no finished full-MF run
             rank, dist = dist_rank()
             grouper = Group(val_mat, self.param.dataset, user_mat)
             kw = dict(verbose=False, data_dir=os.path.dirname(os.path.dirname(self.param.train_dir)))

@@ -1530,3 +1530,93 @@ def ridge_rows(F, d, k, segs, l2, l2_n=0.0, stream=None, order='longest'):
         err.X, err.failed, err.segment = X, failed, first
         raise err
     return X
+
+
+# ---------------------------------------------------------------------------
+# OT grouping on the sparse rating matrix (csrc/csr_group.hip; the contract is sparse_group.py)
+# ---------------------------------------------------------------------------
+class CsrSet:
+    """The canonical CSR and CSC of a SciPy sparse matrix (sparse_group.canonical_csr) resident on the device, uploaded once
+    per clustering call: the cost kernel walks the rows, the centroid kernel the columns.  n rows (users), n_item columns."""
+
+    def __init__(self, sp_mat, device=None):
+        from .sparse_group import canonical_csr
+        self.csr, self.csc = canonical_csr(sp_mat)                # (raises ValueError before any device work)
+        self.n, self.n_item = self.csr.shape
+        self.nnz = self.csr.nnz
+        self.device = device or _device()
+        # (a kernel argument must not be NULL: an empty matrix keeps one unused entry)
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        # (plain copies: the pinned staging pool of upload_many is for small descriptors, these are 12 bytes per rating, twice)
+        (self.row_off, self.col, self.val, self.col_off, self.row, self.cval) = [
+            torch.from_numpy(a).to(self.device)
+            for a in (self.csr.off, pad(self.csr.idx), pad(self.csr.val), self.csc.off, pad(self.csc.idx), pad(self.csc.val))]
+
+
+def _csr_same_device(S, t, what):
+    if t.device != S.row_off.device:
+        raise ValueError(f'{what} is on {t.device} but the CsrSet was uploaded to {S.row_off.device}')
+
+
+def _csr_held_for(stream, *tensors):
+    """Tensors allocated here for a launch on a stream that is not torch's current one: the caching allocator may hand a block out
+    again only after that stream's work."""
+    if stream is not None:
+        for t in tensors:
+            t.record_stream(stream)
+
+
+def _csr_k(k):
+    from .sparse_group import MAX_K
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K:
+        raise ValueError(f'k must be an integer in 1 .. {MAX_K}, not {k!r}')
+    return int(k)
+
+
+def csr_cost(S, Ct, k, stream=None):
+    """ure_csr_cost: dist [k, n] float32 on the device (ure_ot_cost's layout) of the rows of S (a CsrSet) against the k
+    centroids held transposed in the device tensor Ct [n_item, ldc] float32, ldc >= k.  Nothing synchronises."""
+    k = _csr_k(k)
+    if not (torch.is_tensor(Ct) and Ct.is_cuda):
+        raise nv.NativeError('csr_cost runs on the HIP device only (no CPU fallback)')
+    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and Ct.shape[0] == S.n_item and Ct.shape[1] >= k):
+        raise ValueError(f'Ct must be a contiguous float32 [{S.n_item}, >= {k}] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
+    _csr_same_device(S, Ct, 'Ct')
+    L, dev = nv.lib(), Ct.device
+    nbytes = int(L.ure_csr_cost_scratch(k))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(k, S.n, dtype=torch.float32, device=dev)
+    nv.check(L.ure_csr_cost(nv.ptr(S.row_off), nv.ptr(S.col), nv.ptr(S.val), S.n, S.n_item, nv.ptr(Ct), int(Ct.shape[1]), k, nv.ptr(dist),
+                            nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_csr_cost')
+    _csr_held_for(stream, scratch, dist)
+    return dist
+
+
+def csr_centroids(S, label, k, ldc=None, stream=None):
+    """ure_csr_centroids: (Ct [n_item, ldc] float32, counts [k] int32) on the device, the means of the users of every cluster
+    of label (n values in [0, k): a host array, or a device int32 tensor whose range is read back once), transposed as
+    csr_cost reads them.  ldc (default k) >= k; the padding columns are zero.  A cluster without members gives zeros and
+    counts 0.  Nothing synchronises after the launch."""
+    k = _csr_k(k)
+    ldc = k if ldc is None else int(ldc)
+    if ldc < k:
+        raise ValueError(f'ldc = {ldc} < k = {k}')
+    if torch.is_tensor(label):
+        if not label.is_cuda:
+            raise nv.NativeError('csr_centroids runs on the HIP device only (no CPU fallback)')
+        if label.dtype != torch.int32 or label.shape != (S.n,) or int(label.min()) < 0 or int(label.max()) >= k:
+            raise ValueError(f'label must be n = {S.n} int32 values in [0, {k})')
+        _csr_same_device(S, label, 'label')
+        lab_d = label.contiguous()
+    else:
+        lab = np.ascontiguousarray(label)
+        if lab.shape != (S.n,) or lab.min() < 0 or lab.max() >= k:
+            raise ValueError(f'label must be n = {S.n} values in [0, {k})')
+        lab_d = to_device_async(lab.astype(np.int32), S.device)
+    dev = lab_d.device
+    Ct = (torch.empty if ldc == k else torch.zeros)(S.n_item, ldc, dtype=torch.float32, device=dev)
+    counts = torch.empty(k, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_csr_centroids(nv.ptr(S.col_off), nv.ptr(S.row), nv.ptr(S.cval), nv.ptr(lab_d), S.n, S.n_item, k, nv.ptr(Ct), ldc,
+                                        nv.ptr(counts), nv.stream_handle(stream)), 'ure_csr_centroids')
+    _csr_held_for(stream, lab_d, Ct, counts)
+    return Ct, counts

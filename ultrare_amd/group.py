@@ -15,15 +15,16 @@ from .method.utils import _dense_f32, atomic_save, kmeans, kmedoids, lpa, ot_clu
 
 DATA_DIR = abspath(os.environ.get('ULTRARE_DATA_DIR', join(os.getcwd(), 'data')))
 SAVE_DIR = abspath(os.environ.get('ULTRARE_SAVE_DIR', join(os.getcwd(), 'result')))
+DENSE_MAX_ITEMS = 256          # ure_ot_cost's widest row: up to here 'rating-ot' keeps the dense route it always had
 
 
 class Group(object):
     def __init__(self, rating, dataset, user_mat=None):
-        self.rating = rating  # csr_matrix (only used by the 'rating-ot' variant)
+        self.rating = rating  # csr_matrix (only used by the 'rating-*' variants)
         self.dataset = dataset
         self.user_mat = user_mat
         self.n_user = self.rating.shape[0] if rating is not None else (len(user_mat) if user_mat is not None else 0)
-        self.n_item = self.rating.shape[1] if rating is not None else 0
+        self.n_item = self.rating.shape[1] if rating is not None and len(self.rating.shape) > 1 else 0
 
     def grouping(self, dataset='ml1m', n_group=2, var='emb-ot', verbose=True, data_dir=None, *, reg=1e-3):
         """reg: the entropic regulariser of the 'sinkhorn' clusterer (absolute, in squared-distance units; ignored by the others
@@ -43,7 +44,15 @@ class Group(object):
         assert cluster_var in ['ot', 'sinkhorn', 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa', 'blpa'], \
             "cluster_var must be 'ot' (published path), 'sinkhorn', 'kmeans', 'bkmeans', 'kmedoids', 'bkmedoids', 'lpa' or 'blpa'"
         if trans_var == 'rating':
-            embedding = np.asarray(self.rating.todense(), dtype=np.float32)
+            if len(self.rating.shape) != 2:
+                raise ValueError(f'the rating matrix must be 2-D, not of shape {tuple(self.rating.shape)}')
+            if cluster_var in ('ot', 'sinkhorn') and self.n_item > DENSE_MAX_ITEMS:
+                # the CSR goes straight through: ot_cluster runs the cost and the centroid update on the sparse matrix
+                # (csrc/csr_group.hip) and n_user x n_item is never formed; bad input is refused before any device work
+                from .sparse_group import check_cluster_args
+                embedding = check_cluster_args(self.rating, n_group)
+            else:
+                embedding = np.asarray(self.rating.todense(), dtype=np.float32)
         elif trans_var == 'emb':
             embedding = self.user_mat
         else:

@@ -464,11 +464,16 @@ def ot_cluster(X, k, max_iters=10, timing=None, solver='exact', reg=1e-3, num_it
     the reference.  Returns (inertia, label[int64]).  timing (a list, optional): every round's parts in milliseconds (_ot_round).
     solver='exact' (the default, the reference's arithmetic: exact EMD) or 'sinkhorn': every round's transport is
     entropic OT solved on the device (_ot_cluster_sinkhorn), an opt-in that is not bit-parity with the reference; reg,
-    num_iter_max and stop_thr are its settings and are ignored by the exact solver."""
+    num_iter_max and stop_thr are its settings and are ignored by the exact solver.
+    X may be a SciPy sparse matrix (the ratings): the same rounds then run through the CSR cost and centroid kernels
+    (_ot_cluster_csr) and the n x d array is never formed; dense inputs take the dense kernels as before.  timing is served
+    there for both solvers."""
     if solver not in ('exact', 'sinkhorn'):
         raise ValueError(f"solver must be 'exact' or 'sinkhorn', not {solver!r}")
     if solver == 'sinkhorn':
         engine.check_sinkhorn_args(reg, num_iter_max, stop_thr)
+    if _is_sparse(X):
+        return _ot_cluster_csr(X, k, max_iters, solver, reg, num_iter_max, stop_thr, timing)
     X = np.ascontiguousarray(X, dtype=np.float32)
     n, d = X.shape
     if k < 1 or k > n:
@@ -530,6 +535,82 @@ def _ot_cluster_sinkhorn(X, centroid, k, max_iters, reg, num_iter_max, stop_thr)
         nv.check(L.ure_ot_centroids_members(nv.ptr(Xd), nv.ptr(order), nv.ptr(off), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
                  'ure_ot_centroids_members')
         new_centroid = cent_d.cpu().numpy()
+        if np.allclose(centroid, new_centroid):
+            break
+        centroid = new_centroid
+    print(f'{inertia:.3f}', end=' ')
+    return inertia, label.astype(np.int64)
+
+
+def _is_sparse(X):
+    """A SciPy sparse matrix, or the (csr, csc) pair sparse_group.canonical_csr made of one."""
+    import sys
+    from ..sparse_group import Compressed
+    if isinstance(X, tuple):
+        return len(X) == 2 and all(isinstance(h, Compressed) for h in X)
+    sp = sys.modules.get('scipy.sparse')           # (a sparse matrix cannot exist before scipy.sparse was imported)
+    return sp is not None and sp.issparse(X)
+
+
+def _ot_cluster_csr(X, k, max_iters, solver, reg, num_iter_max, stop_thr, timing=None):
+    """ot_cluster's rounds on a SciPy sparse matrix (the ratings, n_user x n_item), never densified: ure_csr_cost ->
+    the exact LP on the host (warm-started by ure_ot_potentials, as _ot_round) or ure_ot_sinkhorn on the device matrix ->
+    the labels to the device -> ure_csr_centroids, then utils.py's allclose stop on the [k, n_item] centroids.  The
+    arithmetic of the two kernels is this project's (sparse_group.py): the reference's own branch raises.  Every refusal
+    (shape, non-finite values, k) comes before any device work.  timing (a list): the round's parts on the host's clock with a
+    synchronisation between them, appended as a dict of milliseconds, as _ot_round does."""
+    from ..sparse_group import check_cluster_args, dense_rows
+    halves = check_cluster_args(X, k)
+    n = halves[0].shape[0]
+    if solver == 'sinkhorn' and k > engine.SINKHORN_MAX_K:
+        raise ValueError(f'the sinkhorn solver takes at most {engine.SINKHORN_MAX_K} clusters, not {k}')
+    centroid = dense_rows(halves[0], np.random.choice(n, size=k, replace=False))
+    L, st = nv.lib(), nv.stream_handle()
+    S = engine.CsrSet(halves)
+    Ct = torch.from_numpy(np.ascontiguousarray(centroid.T)).to(S.device)
+    pi = np.zeros(k, dtype=np.float64)
+    stats = []
+    if solver == 'sinkhorn':
+        ot_cluster.sinkhorn_stats = stats
+    for rnd in range(max_iters):
+        marks = []
+
+        def tick(name):
+            if timing is not None:
+                torch.cuda.synchronize()
+                marks.append((name, time.perf_counter()))
+        tick('start')
+        dist_d = engine.csr_cost(S, Ct, k)
+        tick('cost_kernel')
+        if solver == 'sinkhorn':
+            r = engine.ot_sinkhorn(dist_d, reg, num_iter_max, stop_thr, want_u=False, want_cost_min=True)
+            stats.append((r['iters'], r['err']))
+            label = r['label'].cpu().numpy()
+            inertia = r['cost_min'].cpu().numpy().sum()              # == np.min(dist, axis=0).sum(): the same float32 values and order
+            tick('device_sinkhorn')
+        else:
+            nv.check(L.ure_ot_potentials(nv.ptr(dist_d), n, k, ot_warm_iters(n), pi.ctypes.data, None, st), 'ure_ot_potentials')
+            tick('device_potentials')
+            dist = dist_d.cpu().numpy()
+            tick('cost_to_host')
+            label, _, _, _ = nv.ot_assign_warm(dist, pi, want_plan=False)
+            inertia = np.min(dist, axis=0).sum()
+            tick('host_solver')
+        sizes = np.bincount(label, minlength=k)
+        if (sizes == 0).any():
+            empty = np.flatnonzero(sizes == 0).tolist()
+            if solver == 'sinkhorn':
+                raise ValueError(f'ot_cluster(solver=\'sinkhorn\'): round {rnd}: cluster(s) {empty} received no '
+                                 f'point, so their centroid (utils.py:648) is undefined; reg = {reg:g} against costs up to '
+                                 f'{float(dist_d.max()):.4g}: a larger reg balances the groups')
+            raise ValueError(f'ot_cluster(solver=\'exact\'): round {rnd}: cluster(s) {empty} received no point, so their centroid '
+                             f'(utils.py:648) is undefined; the exact plan gives every cluster n / k = {n / k:g} points, so '
+                             f'k = {k} is too large for n = {n}')
+        Ct, _ = engine.csr_centroids(S, label, k)
+        new_centroid = np.ascontiguousarray(Ct.cpu().numpy().T)
+        tick('centroids')
+        if timing is not None:
+            timing.append({b[0] + '_ms': round((b[1] - a[1]) * 1e3, 4) for a, b in zip(marks[:-1], marks[1:])})
         if np.allclose(centroid, new_centroid):
             break
         centroid = new_centroid

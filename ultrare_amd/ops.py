@@ -25,6 +25,11 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         (new)             (pred, sse partials) with fitted weight rows
     torch.ops.ultrare.ridge_rows(F, off, idx, val, k, l2, l2_n)
                                                         (new)             the ridge solution of every CSR segment against F
+    torch.ops.ultrare.csr_cost(row_off, col, val, Ct, k)
+                                                        (new)             [k, n] squared distances of CSR rows to the
+                                                                          centroids held transposed in Ct [n_item, ldc]
+    torch.ops.ultrare.csr_centroids(col_off, row, val, label, k)
+                                                        (new)             (Ct [n_item, k], counts [k]) from the CSC
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -208,3 +213,57 @@ def ridge_rows(F: torch.Tensor, off: torch.Tensor, idx: torch.Tensor, val: torch
 @ridge_rows.register_fake
 def _(F, off, idx, val, k, l2, l2_n):
     return F.new_empty(off.numel() - 1, F.shape[1])
+
+
+def _csr_half(off, idx, val):
+    if not (off.dtype == torch.int64 and idx.dtype == torch.int32 and val.dtype == torch.float32):
+        raise ValueError('a CSR half is (int64 offsets, int32 indices, float32 values)')
+    if off.dim() != 1 or off.numel() < 2 or idx.numel() != val.numel() or idx.numel() < 1:
+        raise ValueError('offsets must hold n + 1 values and indices as many entries as values (at least one)')
+    return off.contiguous(), idx.contiguous(), val.contiguous()
+
+
+@torch.library.custom_op('ultrare::csr_cost', mutates_args=())
+def csr_cost(row_off: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Ct: torch.Tensor, k: int) -> torch.Tensor:
+    _dev(row_off, col, val, Ct)
+    row_off, col, val = _csr_half(row_off, col, val)
+    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and 1 <= k <= Ct.shape[1]):
+        raise ValueError(f'Ct must be a contiguous float32 [n_item, >= k] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
+    if int(col.max()) >= Ct.shape[0] or int(col.min()) < 0:
+        raise ValueError(f'column indices outside the {Ct.shape[0]} rows of Ct')
+    L, n = nv.lib(), row_off.numel() - 1
+    nbytes = int(L.ure_csr_cost_scratch(k))
+    if nbytes < 0:
+        raise ValueError(f'k = {k} outside 1 .. 256')
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=Ct.device)
+    dist = torch.empty(k, n, dtype=torch.float32, device=Ct.device)
+    nv.check(L.ure_csr_cost(nv.ptr(row_off), nv.ptr(col), nv.ptr(val), n, int(Ct.shape[0]), nv.ptr(Ct), int(Ct.shape[1]), k, nv.ptr(dist),
+                            nv.ptr(scratch), nbytes, nv.stream_handle()), 'ure_csr_cost')
+    return dist
+
+
+@csr_cost.register_fake
+def _(row_off, col, val, Ct, k):
+    return Ct.new_empty(k, row_off.numel() - 1)
+
+
+@torch.library.custom_op('ultrare::csr_centroids', mutates_args=())
+def csr_centroids(col_off: torch.Tensor, row: torch.Tensor, val: torch.Tensor, label: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(col_off, row, val, label)
+    col_off, row, val = _csr_half(col_off, row, val)
+    label = label.to(torch.int32).contiguous()
+    n, n_item = label.numel(), col_off.numel() - 1
+    if int(row.max()) >= n or int(row.min()) < 0:
+        raise ValueError(f'row indices outside the {n} labels')
+    if int(label.min()) < 0 or int(label.max()) >= k:
+        raise ValueError(f'label must hold values in [0, {k})')
+    Ct = torch.empty(n_item, k, dtype=torch.float32, device=val.device)
+    counts = torch.empty(k, dtype=torch.int32, device=val.device)
+    nv.check(nv.lib().ure_csr_centroids(nv.ptr(col_off), nv.ptr(row), nv.ptr(val), nv.ptr(label), n, n_item, k, nv.ptr(Ct), k, nv.ptr(counts),
+                                        nv.stream_handle()), 'ure_csr_centroids')
+    return Ct, counts
+
+
+@csr_centroids.register_fake
+def _(col_off, row, val, label, k):
+    return val.new_empty(col_off.numel() - 1, k), val.new_empty(k, dtype=torch.int32)

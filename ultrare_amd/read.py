@@ -226,8 +226,14 @@ def loadData(data, batch=30000, n_worker=24, shuffle=True):
 
 
 def readSparseMat(dir, n_user, n_item, max_rating=5):
-    """read.py:136-145 (float16 CSR of ratings; consumed only by 'rating-ot')."""
+    """read.py:136-145 (float16 CSR of ratings; consumed only by the 'rating-*' groupings).  The values are rounded to
+    float16, the reference's dtype; a SciPy that refuses float16 sparse matrices holds the rounded values as float32."""
     from scipy.sparse import coo_matrix
     row, col, raw = _read_csv(dir)
     val = raw / max_rating
-    return coo_matrix((val, (row, col)), shape=(n_user, n_item), dtype=np.float16).tocsr()
+    try:
+        return coo_matrix((val, (row, col)), shape=(n_user, n_item), dtype=np.float16).tocsr()
+    except (ValueError, TypeError):
+        mat = coo_matrix((val.astype(np.float16).astype(np.float32), (row, col)), shape=(n_user, n_item)).tocsr()
+        mat.data = mat.data.astype(np.float16).astype(np.float32)      # (a pair rated twice was summed: float16 holds the sum too)
+        return mat
