@@ -126,7 +126,7 @@ void ure_oracle_merge_rows(float *dst, const float *src, const int64_t *rows, in
         memcpy(dst + (size_t)rows[t] * d, src + (size_t)rows[t] * d, (size_t)d * sizeof(float));
 }
 
-/* numpy's float32 pairwise sum of n contiguous values, n < 128 (PW_BLOCKSIZE):
+/* numpy's float32 pairwise sum of n contiguous values; up to 128 (PW_BLOCKSIZE) one block:
  * eight running accumulators over blocks of 8, combined as
  * ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), leftovers added sequentially; for n < 8 a
  * plain left-to-right loop.  SURVEY section 7 ("Exact OT on GPU") checked this bit
@@ -170,18 +170,37 @@ void ure_oracle_ot_cost(const float *X, const float *C, int64_t n, int32_t k, in
 
 /* new_centroid[c] = X[label==c].mean(axis=0)  (utils.py:648): numpy reduces over
  * axis 0 of the gathered [cnt,d] block row by row (sequential fp32 adds in
- * ascending row id), then divides by the fp32 count.  bit-exact. */
+ * ascending row id) from the initial value +0.0 (mean() passes `where`, which
+ * starts add.reduce at the identity), then divides by the fp32 count.  For d = 1
+ * the block is one contiguous run and numpy sums it like a vector: pairwise sums
+ * of buffers of 8192 values, added in order.  bit-exact. */
 void ure_oracle_centroids(const float *X, const int64_t *label, int64_t n, int32_t k, int32_t d, float *C /* [k][d] */)
 {
     int64_t *cnt = (int64_t *)calloc((size_t)k, sizeof(int64_t));
     memset(C, 0, (size_t)k * d * sizeof(float));
-    for (int64_t i = 0; i < n; ++i) {
-        float *c = C + (size_t)label[i] * d;
-        const float *x = X + (size_t)i * d;
-        if (cnt[label[i]]++ == 0)
-            memcpy(c, x, (size_t)d * sizeof(float));
-        else
+    if (d == 1) {
+        float *buf = (float *)malloc(8192 * sizeof(float));
+        for (int32_t c = 0; c < k; ++c) {
+            int32_t fill = 0;
+            for (int64_t i = 0; i <= n; ++i) {
+                if (i < n && label[i] == c) {
+                    buf[fill++] = X[i];
+                    ++cnt[c];
+                }
+                if (fill == 8192 || (i == n && fill > 0)) {
+                    C[c] += np_pairwise_f32(buf, fill);
+                    fill = 0;
+                }
+            }
+        }
+        free(buf);
+    } else {
+        for (int64_t i = 0; i < n; ++i) {
+            float *c = C + (size_t)label[i] * d;
+            const float *x = X + (size_t)i * d;
+            ++cnt[label[i]];
             for (int32_t j = 0; j < d; ++j) c[j] += x[j];
+        }
     }
     for (int32_t c = 0; c < k; ++c)
         for (int32_t j = 0; j < d; ++j) C[(size_t)c * d + j] /= (float)cnt[c];

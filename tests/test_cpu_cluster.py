@@ -183,3 +183,68 @@ class _Host:
 
     def numpy(self):
         return self.a
+
+
+# ---- the shapes of the GPU bit tests can tell numpy's summation rules apart (on the numpy installed here) -------------------
+def _np_leaf(a):
+    """numpy's pairwise_sum of at most 128 float32 values: below 8 one after the other from 0, else eight accumulators."""
+    if len(a) < 8:
+        res = np.float32(0)
+        for v in a:
+            res = res + v
+        return res
+    r = a[:8].copy()
+    full = len(a) - len(a) % 8
+    for i in range(8, full, 8):
+        r = r + a[i:i + 8]
+    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    for v in a[full:]:
+        res = res + v
+    return res
+
+
+def _np_pairwise(a):
+    """One pairwise sum over the whole run: halves (the first a multiple of 8) down to leaves of at most 128."""
+    if len(a) <= 128:
+        return _np_leaf(a)
+    h = len(a) // 2
+    h -= h % 8
+    return _np_pairwise(a[:h]) + _np_pairwise(a[h:])
+
+
+def _one_split(a):
+    """The rule ure_ot_cost had before: a row longer than 128 split once, both halves taken as leaves."""
+    if len(a) <= 128:
+        return _np_leaf(a)
+    h = len(a) // 2
+    h -= h % 8
+    return _np_leaf(a[:h]) + _np_leaf(a[h:])
+
+
+@pytest.mark.parametrize('n', [8193, 8261, 16391, 20000])
+def test_numpy_row_sums_past_8192_are_not_one_pairwise_sum(n):
+    """np.sum(A, axis=1) of float32 rows longer than 8192 adds the pairwise sums of buffers of 8192 values in order; a single
+    pairwise sum over the row gives other bits somewhere in a few rows, so tests/test_gpu_cluster.py's row-sum shapes would
+    catch a kernel that ignored the buffers."""
+    A = np.abs(np.random.default_rng(n).standard_normal((6, n))).astype(np.float32)
+    got = np.sum(A, axis=1)
+    buffered = np.array([sum((_np_pairwise(row[i:i + 8192]) for i in range(0, n, 8192)), np.float32(0)) for row in A])
+    single = np.array([_np_pairwise(row) for row in A])
+    assert buffered.dtype == np.float32 and single.dtype == np.float32
+    assert np.array_equal(got.view(np.uint32), buffered.view(np.uint32))
+    assert (got.view(np.uint32) != single.view(np.uint32)).any()
+
+
+@pytest.mark.parametrize('d,differs', [(248, False), (249, True), (255, True), (256, False)])
+def test_numpy_cost_rows_of_249_to_255_split_twice(d, differs):
+    """utils.py:637's row sums follow numpy's full rule; for d = 249 .. 255 the second half (129 .. 135 terms) is split again,
+    so the one-split rule gives other bits there and the same bits at 248 and 256."""
+    rs = np.random.RandomState(d)
+    X = rs.standard_normal((300, d)).astype(np.float32)
+    C = rs.standard_normal((4, d)).astype(np.float32)
+    T = (X - C[:, np.newaxis]) ** 2
+    got = T.sum(axis=2)
+    full = np.array([[_np_pairwise(row) for row in block] for block in T])
+    once = np.array([[_one_split(row) for row in block] for block in T])
+    assert np.array_equal(got.view(np.uint32), full.view(np.uint32))
+    assert (got.view(np.uint32) != once.view(np.uint32)).any() == differs

@@ -182,6 +182,95 @@ def test_streamed_equals_given_on_own_distances(n, d, n_nb, metric):
     assert np.all(np.abs(W - ref_w) <= 1e-6 * np.abs(ref_w) + n * np.finfo(np.float32).tiny)
 
 
+# ---- row sums past one numpy buffer ---------------------------------------------------------------------------------
+# np.sum(A, axis=1) sums a row in buffers of 8192 values; above that the kernel switches to the last buffer's leaf table and
+# adds the buffer sums in order.  8193: a last buffer of one value; 8261: of 69 (one leaf, a tail of 5); 16391: two full
+# buffers and 7 values (a leaf below one group of 8); 20000: two full buffers and 3616 values (a tree of its own).
+ROWSUM_NS = [8193, 8261, 16391, 20000]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize('n', ROWSUM_NS)
+@pytest.mark.parametrize('metric', METRICS)
+def test_rowsum_beyond_one_buffer_equals_numpy(n, metric):
+    """256 rows of D -- the first 64, the last 70 (the ragged tile) and 122 random ones -- fetched as columns (D is symmetric bit
+    for bit: test_streamed_equals_given_on_own_distances) and summed by numpy against the streamed row sums."""
+    from ultrare_amd import engine
+    X = _data(n, 3, n)
+    Xd = torch.from_numpy(X).cuda()
+    R = engine.pair_rowsum(Xd, metric).cpu().numpy()
+    rows = np.concatenate([np.arange(64), np.arange(n - 70, n), np.random.default_rng(n).choice(np.arange(64, n - 70), 122, replace=False)])
+    Dt = np.ascontiguousarray(engine.pair_cols(Xd, rows, metric).cpu().numpy().T)
+    assert Dt.shape == (256, n) and Dt.flags['C_CONTIGUOUS']
+    want = np.sum(Dt, axis=1)
+    print(f'n={n} {metric}: {int((_bits(R[rows]) != _bits(want)).sum())} of 256 row sums differ from numpy')
+    assert np.array_equal(_bits(R[rows]), _bits(want))
+
+
+def test_rowsum_beyond_one_buffer_given_source():
+    """Once, the whole 8261 x 8261 array (273 MB): the given source takes the same walk as the streamed one, and numpy agrees
+    on every row."""
+    from ultrare_amd import engine
+    n = 8261
+    Xd = torch.from_numpy(_data(n, 3, n)).cuda()
+    G = engine.pair_cols(Xd, np.arange(n), 'euclidean')
+    R = engine.pair_rowsum(Xd, 'euclidean').cpu().numpy()
+    assert np.array_equal(_bits(engine.pair_rowsum(G).cpu().numpy()), _bits(R))
+    assert np.array_equal(_bits(np.sum(G.cpu().numpy(), axis=1)), _bits(R))
+
+
+# ---- exp-sums at the limit of k ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('k', [77, 128])
+@pytest.mark.parametrize('metric', METRICS)
+def test_label_expsum_at_the_group_limit(k, metric):
+    """k = 77 is the first whose dynamic LDS (the tile + k x 64 doubles) passes 64 KiB, 128 is the limit; some groups have
+    no member."""
+    from ultrare_amd import engine
+    n, d = 300, 10
+    X = _data(n, d, n * 7 + d)
+    Xd = torch.from_numpy(X).cuda()
+    label = np.random.default_rng(k).integers(0, k, size=n)
+    label[label % 5 == 3] = 0                                  # every fifth group stays empty
+    label[label == k - 1] = 1                                  # and the last one
+    empty = np.setdiff1d(np.arange(k), label)
+    assert len(empty) >= k // 5 and k - 1 in empty and len(np.unique(label)) > k // 2
+    G = engine.pair_cols(Xd, np.arange(n), metric)
+    Gh = G.cpu().numpy()
+    W = engine.pair_label_expsum(Xd, label, k, metric).cpu().numpy()
+    assert W.shape == (n, k) and W.dtype == np.float64
+    assert np.array_equal(W.view(np.uint64), engine.pair_label_expsum(G, label, k).cpu().numpy().view(np.uint64))
+    ref_w = _w64(Gh, label, k)
+    assert np.all(np.abs(W - ref_w) <= 1e-6 * np.abs(ref_w) + n * np.finfo(np.float32).tiny)
+    assert not W[:, empty].any() and W[:, np.unique(label)].all()
+
+
+# ---- kNN at the split limit -----------------------------------------------------------------------------------------------
+def test_knn_at_the_split_limit_and_given_with_query():
+    """n = 4090 is 64 column tiles, the last one ragged: splits = 64 gives every tile a workgroup of its own (fewer columns
+    than n_nb = 128 in each), splits = 1000 is clamped to 64.  Both sources, 70 query rows with repeats: every call returns
+    the bytes of splits = 1, which are the lexsort of the device's own distances."""
+    from ultrare_amd import engine
+    n, d, n_nb = 4090, 10, 128
+    Xd = torch.from_numpy(_data(n, d, n * 7 + d)).cuda()
+    query = np.random.default_rng(3).integers(0, n, size=64)
+    query = np.concatenate([query, query[:5], [n - 1]])
+    assert len(query) == 70 and len(np.unique(query)) < 70
+    Dq = np.ascontiguousarray(engine.pair_cols(Xd, query, 'euclidean').cpu().numpy().T)        # rows `query` of D (symmetric)
+    G = engine.pair_cols(Xd, np.arange(n), 'euclidean')
+    assert np.array_equal(_bits(G[torch.from_numpy(query).cuda()].cpu().numpy()), _bits(Dq))
+    dist, idx = engine.pair_knn(Xd, n_nb, 'euclidean', query=query, splits=1)
+    for src, met in ((Xd, 'euclidean'), (G, None)):
+        for splits in (1, 64, 1000):
+            d2, i2 = engine.pair_knn(src, n_nb, met, query=query, splits=splits)
+            assert torch.equal(d2.view(torch.int32), dist.view(torch.int32)) and torch.equal(i2, idx), (met, splits)
+    order = np.lexsort((np.broadcast_to(np.arange(n), Dq.shape), Dq), axis=1)[:, :n_nb]
+    np.testing.assert_array_equal(idx.cpu().numpy(), order)
+    assert np.array_equal(_bits(dist.cpu().numpy()), _bits(np.take_along_axis(Dq, order, axis=1)))
+
+
 # ---- Group.grouping ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('var', ['emb-bkmedoids', 'emb-blpa'])
 def test_group_grouping_new_clusterers(gold, var, tmp_path):

@@ -295,9 +295,19 @@ def test_ot_rounds_k16_fractional_case(ot_ml1m):
             assert np.array_equal(cent_d.cpu().numpy(), cents[r + 1])
 
 
-@pytest.mark.parametrize('n,k,d', [(1000, 3, 8), (777, 5, 20), (5000, 7, 64), (4099, 32, 128), (300, 4, 200), (257, 2, 256), (63, 2, 4)])
+OT_COST_SHAPES = [(1000, 3, 8), (777, 5, 20), (5000, 7, 64), (4099, 32, 128), (300, 4, 200), (257, 2, 256), (63, 2, 4),
+                  # below, at and above one group of 8 accumulators
+                  (70, 3, 1), (70, 3, 7), (70, 3, 9),
+                  # the first widths numpy splits in two, and the last ones whose second half is one block (at most 128 terms)
+                  (70, 3, 129), (70, 3, 136), (130, 5, 241), (130, 5, 248),
+                  # 249 .. 255: the second half has 129 .. 135 terms and numpy splits it again.  254 is the widest row of the tiled
+                  # kernel (its LDS tile is 64 KiB - 256 bytes), 255 the first of the untiled one
+                  (130, 5, 249), (130, 5, 250), (65, 2, 254), (65, 2, 255)]
+
+
+@pytest.mark.parametrize('n,k,d', OT_COST_SHAPES)
 def test_ot_cost_kernel_bit_equal_numpy_order(n, k, d):
-    """ure_ot_cost (64-row LDS tiles, lane = row, wave = centroid; the untiled kernel for d = 256) against
+    """ure_ot_cost (64-row LDS tiles, lane = row, wave = centroid; the untiled kernel for d = 255 and 256) against
     utils.py:637 evaluated by numpy: every bit of every distance, ragged last tile included."""
     from ultrare_amd import _native as nv
     rs = np.random.RandomState(n + d)
@@ -307,8 +317,91 @@ def test_ot_cost_kernel_bit_equal_numpy_order(n, k, d):
     Xd, Cd = torch.from_numpy(X).cuda(), torch.from_numpy(C).cuda()
     dist_d = torch.empty(k, n, dtype=torch.float32, device='cuda')
     nv.check(nv.lib().ure_ot_cost(nv.ptr(Xd), nv.ptr(Cd), n, k, d, nv.ptr(dist_d), nv.stream_handle()), 'ure_ot_cost')
-    assert np.array_equal(dist_d.cpu().numpy(), want)
+    got = dist_d.cpu().numpy()
+    print(f'n={n} k={k} d={d}: {int((got != want).sum())} of {want.size} distances differ from numpy')
+    assert np.array_equal(got, want)
     assert np.array_equal(O.ot_cost(X, C), want)
+
+
+# ---- ure_ot_centroids_members: the kernel ot_cluster uses, at the sizes around its 32-member look-ahead ----------------
+MEMBER_SIZES = [1, 31, 32, 33, 63, 64, 65, 97, 1000]
+
+
+def _member_lists(label, k):
+    """order / off as utils._ot_round builds them: a stable argsort of the labels, the cumulative bincount."""
+    order = np.argsort(label.astype(np.uint8), kind='stable').astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(np.bincount(label, minlength=k))]).astype(np.int64)
+    return order, off
+
+
+def _device_centroids(X, label, k):
+    """(centroids, counts) of ure_ot_centroids_members and of ure_ot_centroids on the same labels."""
+    from ultrare_amd import _native as nv
+    n, d = X.shape
+    L, st = nv.lib(), nv.stream_handle()
+    Xd = torch.from_numpy(X).cuda()
+    order, off = _member_lists(label, k)
+    order_d, off_d = torch.from_numpy(order).cuda(), torch.from_numpy(off).cuda()
+    lab_d = torch.from_numpy(label.astype(np.int32)).cuda()
+    out = []
+    for members in (True, False):
+        cent_d = torch.full((k, d), 7.0, dtype=torch.float32, device='cuda')
+        counts_d = torch.full((k,), -1, dtype=torch.int32, device='cuda')
+        if members:
+            nv.check(L.ure_ot_centroids_members(nv.ptr(Xd), nv.ptr(order_d), nv.ptr(off_d), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
+                     'ure_ot_centroids_members')
+        else:
+            nv.check(L.ure_ot_centroids(nv.ptr(Xd), nv.ptr(lab_d), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st), 'ure_ot_centroids')
+        out.append((cent_d.cpu().numpy(), counts_d.cpu().numpy()))
+    return out
+
+
+def _member_case(d, sizes):
+    rs = np.random.RandomState(1000 + d)
+    n, k = int(np.sum(sizes)), len(sizes)
+    label = rs.permutation(np.repeat(np.arange(k), sizes))
+    X = rs.standard_normal((n, d)).astype(np.float32)
+    return X, label, k
+
+
+@pytest.mark.parametrize('d', [1, 5, 64])
+def test_ot_centroids_members_bit_equal_numpy_mean(d):
+    """Clusters of exactly 1, 31 .. 33, 63 .. 65, 97 and 1000 members (one below, at and one above one and two rounds of the
+    32-member look-ahead, three rounds and a tail, a long run), labels shuffled over the ids: every bit of
+    X[label == c].mean(axis=0), from the member lists and from the labels.  The only member of the cluster of one is a row
+    of -0.0: numpy's mean starts its sum at +0.0, so that centroid is +0.0 -- a kernel that copies its first term keeps the
+    sign.  At d = 1 numpy sums the members pairwise (one contiguous run), not one after the other."""
+    X, label, k = _member_case(d, MEMBER_SIZES)
+    X[np.flatnonzero(label == 0)[0]] = -0.0
+    assert np.bincount(label).tolist() == MEMBER_SIZES
+    want = np.array([X[label == c].mean(axis=0) for c in range(k)])
+    assert want.dtype == np.float32 and not np.signbit(want[0]).any()
+    (got, counts), (got_l, counts_l) = _device_centroids(X, label, k)
+    for name, g in (('members', got), ('labels', got_l)):
+        diff = g.view(np.uint32) != want.view(np.uint32)
+        print(f'd={d} {name}: {int(diff.sum())} of {want.size} values differ from numpy, clusters {np.flatnonzero(diff.any(axis=1)).tolist()}')
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(got.view(np.uint32), got_l.view(np.uint32))
+    assert counts.tolist() == MEMBER_SIZES == counts_l.tolist()
+    assert np.array_equal(O.centroids(X, label, k).view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize('d', [1, 5, 64])
+def test_ot_centroids_members_with_an_empty_cluster(d):
+    """The Sinkhorn path can leave a cluster without members: count 0 and a row of NaN, as numpy's mean of no rows; the
+    other rows keep every bit."""
+    sizes = MEMBER_SIZES[:4] + [0] + MEMBER_SIZES[4:]
+    X, label, k = _member_case(d, sizes)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')                     # numpy: "Mean of empty slice"
+        want = np.array([X[label == c].mean(axis=0) for c in range(k)])
+    assert np.isnan(want[4]).all()
+    full = [c for c in range(k) if c != 4]
+    (got, counts), (got_l, counts_l) = _device_centroids(X, label, k)
+    assert counts.tolist() == sizes == counts_l.tolist() and counts[4] == 0
+    for g in (got, got_l):
+        assert np.isnan(g[4]).all()
+        assert np.array_equal(g[full].view(np.uint32), want[full].view(np.uint32))
 
 
 def test_ot_potentials_balance_the_loads(ot_ml1m):

@@ -64,13 +64,28 @@ def check_against_contract(X, F, k, off, idx, val, l2, l2_n, rows=None, widened=
 
 
 # ---- 1. accuracy against the contract ---------------------------------------------------------------------------------------
+# (k, d): every width the kernel is instantiated for -- 4 (one float4 per row, 1 x 1 register blocks), 8, 16, 32, 64 (the only
+# width whose packed triangle, 2080 doubles, is larger than its tile of 32 rows) and 128 -- with k below, at and between the
+# widths as pad_dim gives them, then k <= d / 2: a narrow system in a wide table, which pad_dim never produces but
+# engine.ridge_rows accepts
+KD = [pytest.param(k, d, id=str(k)) for k, d in [(5, 8), (16, 16), (32, 32), (100, 128), (128, 128)]] + \
+     [pytest.param(k, d, id=f'{k}-{d}') for k, d in [(1, 4), (2, 4), (3, 4), (4, 4), (33, 64), (48, 64), (64, 64),
+                                                     (3, 16), (20, 64), (40, 128)]]
+
+
+def tile_rows(d):
+    """Rows of one LDS tile of csrc/mf_ridge.hip (RrShape<D>::T)."""
+    return 64 if d <= 32 else 2048 // d
+
+
 @pytest.mark.parametrize('l2_n', [0.0, 0.05])
 @pytest.mark.parametrize('l2', [0.5, 1e-2])
-@pytest.mark.parametrize('k', [5, 16, 32, 100, 128])
-def test_rows_match_the_float64_contract(k, l2, l2_n):
+@pytest.mark.parametrize('k,d', KD)
+def test_rows_match_the_float64_contract(k, d, l2, l2_n):
     from ultrare_amd import engine
-    d = engine.pad_dim(k)
-    lens = [0, 1, 2, k - 1, k, k + 1, 2 * k, 500, 3000] * 2 + [0]
+    assert d == engine.pad_dim(d) and (d == engine.pad_dim(k) or 2 * k <= d)
+    T = tile_rows(d)
+    lens = [0, 1, 2, k - 1, k, k + 1, 2 * k, 500, 3000] * 2 + [0] + [T - 1, T, T + 1, 2 * T, 2 * T + 1]
     F = normal_table(400, d, seed=k)                        # the padding columns are NOT zero: they must not enter
     seg, idx, val = segments_of(lens, 400, seed=k + 1)
     segs = engine.SegmentSet(seg, idx, val, len(lens))
@@ -78,14 +93,14 @@ def test_rows_match_the_float64_contract(k, l2, l2_n):
     assert X.shape == (len(lens), d) and X.dtype == np.float32
     assert not X[:, k:].any()                               # padding columns are exactly zero
     off = np.concatenate([[0], np.cumsum(lens)])
-    check_against_contract(X, F, k, off, idx, val, l2, l2_n, what=f'k={k} l2={l2} l2_n={l2_n}')
+    check_against_contract(X, F, k, off, idx, val, l2, l2_n, what=f'k={k} d={d} l2={l2} l2_n={l2_n}')
 
 
 # ---- 2. determinism -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('k', [5, 32, 128])
+@pytest.mark.parametrize('k', [5, 32, 128, 64, 3])
 def test_bytes_do_not_depend_on_stream_order_or_company(k):
     from ultrare_amd import engine
-    d = engine.pad_dim(k)
+    d = engine.pad_dim(k)                                   # 8, 32, 128, 64, 4
     rs = np.random.RandomState(k)
     lens = rs.choice([0, 1, 3, k, 2 * k + 1, 77, 700], 150)
     F = torch.from_numpy(normal_table(300, d, seed=2)).cuda()

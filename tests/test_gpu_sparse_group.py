@@ -13,7 +13,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAIN = os.path.join(ROOT, 'tests', 'golden', 'toy', '0_train.csv')
 N_USER, N_ITEM = 1508, 2071
-KS = [1, 5, 64, 65, 256]          # lane groups of 1 and 8, a full wavefront, one past it (two chunks), the limit
+# every lane-group width of csr_group.hip's group_width -- 1, 2 (the only width without the unrolled full-tile branch), 4, 8,
+# 16, 32 (the usual shard count) and 64 -- with k at, just below and just above a width, then two chunks of 64 (65, 128),
+# one past them (129) and the limit
+KS = [1, 2, 3, 4, 5, 9, 16, 17, 32, 33, 64, 65, 128, 129, 256]
 
 
 def bits(a):

@@ -11,7 +11,7 @@
 // fp32 evaluation ORDER rather than the fastest one: the squared differences of a row
 // are summed with numpy's 8-accumulator pairwise rule, and a centroid is the
 // sequential fp32 sum of its member rows in ascending row id divided once by the
-// count.  This is byte-for-byte work bounded by HBM reads of X (n*d*4 bytes per
+// count (for d = 1 numpy's buffered pairwise sum of the members: see the centroid kernels).  This is byte-for-byte work bounded by HBM reads of X (n*d*4 bytes per
 // centroid pass); it is deliberately NOT reshaped into an MFMA GEMM
 // (|x|^2 - 2 x.c + |c|^2 rounds differently and would break label parity).
 #include "ure_internal.h"
@@ -55,15 +55,29 @@ __device__ __forceinline__ float np_block_sum(const float *__restrict__ x, const
     return res;
 }
 
-// numpy splits runs longer than 128 in two (first half rounded down to a multiple of 8) -- for n <= 256 (ure_ot_cost's limit) that is at most one split, so
-// no recursion.  Inlined into its caller, the loads keep their address spaces: as a called, recursive function (rounds 1-4) it read ot_cost_tiled_kernel's
-// LDS tile and the centroid through flat pointers, and the kernel spent its time there.
+// numpy splits runs longer than 128 in two (first half rounded down to a multiple of 8), and each half again while it is longer than 128.  For n <= 256
+// (ure_ot_cost's limit) the first half has at most 128 terms; the second has n - n2 <= 135 and exceeds 128 exactly for n = 249 .. 255 (n2 = 120), where
+// numpy splits it once more into 64 and 65 .. 71 terms.  That is two splits at the most, written out: no recursion.  Inlined into its caller, the loads
+// keep their address spaces: as a called, recursive function (rounds 1-4) it read ot_cost_tiled_kernel's LDS tile and the centroid through flat
+// pointers, and the kernel spent its time there.
 __device__ __forceinline__ float np_pairwise_le256(const float *__restrict__ x, const float *__restrict__ c, int n)
 {
-    if (n <= 128) return np_block_sum(x, c, n);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return __fadd_rn(np_block_sum(x, c, n2), np_block_sum(x + n2, c + n2, n - n2));
+    int n2 = n;
+    if (n > 128) {
+        n2 = n / 2;
+        n2 -= n2 % 8;
+    }
+    const float first = np_block_sum(x, c, n2);
+    if (n2 == n) return first;
+    const int m = n - n2;
+    int m2 = m;
+    if (m > 128) {
+        m2 = m / 2;
+        m2 -= m2 % 8;
+    }
+    float second = np_block_sum(x + n2, c + n2, m2);
+    if (m2 < m) second = __fadd_rn(second, np_block_sum(x + n2 + m2, c + n2 + m2, m - m2));
+    return __fadd_rn(first, second);
 }
 
 __global__ __launch_bounds__(kBlock) void ot_cost_kernel(const float *__restrict__ X, const float *__restrict__ C, int64_t n,
@@ -257,6 +271,67 @@ __global__ void ot_pot_update_kernel(int64_t n, int k, pot_state *__restrict__ s
     }
 }
 
+// ---- centroids: numpy's order of X[label == c].mean(axis=0) ------------------------------------------------------------
+// mean() is add.reduce from the initial value +0.0 (numpy passes `where`, which starts the reduction at the identity), divided once by the float32
+// count.  For d >= 2 the member rows are added one after the other in ascending id, column by column.  For d = 1 the gathered [m, 1] block is one
+// contiguous run and numpy sums it as np.sum sums a vector: pairwise_sum over buffers of 8192 values, the buffer sums added in order.  Starting at
+// +0.0 shows only when every member so far is -0.0: the mean is then +0.0, as numpy's.
+constexpr int kNpBuf = 8192;
+constexpr int kNpDepth = 16;                // pending halves of one buffer's pairwise tree (its depth is 7)
+
+// numpy's pairwise_sum of the next m <= kNpBuf values of a stream (next() hands them out in order): m < 8 sequential from 0; m <= 128 a leaf of
+// eight accumulators; above, the halves h = m / 2 - (m / 2) % 8 and m - h the same way.  Walked depth first with an explicit stack: a leaf is
+// summed when it is met and then added to the finished left halves it closes.
+template <typename Next>
+__device__ __forceinline__ float np_pairwise_stream(Next &next, int m)
+{
+    int len[kNpDepth], closes[kNpDepth];
+    float part[kNpDepth];
+    int sp = 0, vp = 0;
+    len[0] = m;
+    closes[0] = 0;
+    sp = 1;
+    while (sp > 0) {
+        const int l = len[--sp], cl = closes[sp];
+        if (l > 128) {
+            int h = l / 2;
+            h -= h % 8;
+            len[sp] = l - h;                                // the right half, after the left
+            closes[sp++] = cl + 1;
+            len[sp] = h;
+            closes[sp++] = 0;
+            continue;
+        }
+        float res = 0.f;
+        if (l < 8) {
+            for (int i = 0; i < l; ++i) res = __fadd_rn(res, next());
+        } else {
+            float r[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = next();
+            int i = 8;
+            for (; i < l - (l % 8); i += 8) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], next());
+            }
+            res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])), __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
+            for (; i < l; ++i) res = __fadd_rn(res, next());
+        }
+        for (int u = 0; u < cl; ++u) res = __fadd_rn(part[--vp], res);
+        part[vp++] = res;
+    }
+    return part[0];
+}
+
+// np.sum's order over a stream of m values: the buffers' pairwise sums added in order, from +0.0.
+template <typename Next>
+__device__ __forceinline__ float np_sum_stream(Next &next, int64_t m)
+{
+    float sum = 0.f;
+    for (int64_t left = m; left > 0; left -= kNpBuf) sum = __fadd_rn(sum, np_pairwise_stream(next, (int)min<int64_t>(left, kNpBuf)));
+    return sum;
+}
+
 // One thread per (cluster, column): ascending walk over the points.
 __global__ __launch_bounds__(kBlock) void ot_centroid_kernel(const float *__restrict__ X, const int32_t *__restrict__ label,
                                                              int64_t n, int k, int d, float *__restrict__ C,
@@ -267,11 +342,20 @@ __global__ __launch_bounds__(kBlock) void ot_centroid_kernel(const float *__rest
     const int c = t / d, j = t % d;
     float sum = 0.f;
     int cnt = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (label[i] == c) {
-            const float x = X[i * d + j];
-            sum = cnt == 0 ? x : __fadd_rn(sum, x);
-            ++cnt;
+    if (d == 1) {                                           // one contiguous run: np.sum's order (the members are counted first)
+        for (int64_t i = 0; i < n; ++i) cnt += label[i] == c ? 1 : 0;
+        int64_t i = 0;
+        auto next = [&]() {
+            while (i < n - 1 && label[i] != c) ++i;         // (called cnt times: there is a member left)
+            return X[i++];
+        };
+        sum = np_sum_stream(next, cnt);
+    } else {
+        for (int64_t i = 0; i < n; ++i) {
+            if (label[i] == c) {
+                sum = __fadd_rn(sum, X[i * d + j]);
+                ++cnt;
+            }
         }
     }
     C[t] = __fdiv_rn(sum, (float)cnt);
@@ -280,7 +364,7 @@ __global__ __launch_bounds__(kBlock) void ot_centroid_kernel(const float *__rest
 
 // The same means from member lists: order[off[c] .. off[c+1]) = the points of cluster c in ascending id (a stable
 // counting sort of the labels, made on the host where the labels come from).  A thread still adds its column of its
-// cluster's rows one after the other in ascending id -- numpy's order -- but walks ~n / k rows instead of testing all n
+// cluster's rows one after the other in ascending id, from +0.0 -- numpy's order -- but walks ~n / k rows instead of testing all n
 // labels (n = 162,000, k = 32, d = 128: 11.9 -> 6.6 ms; with the loads of 32 members in flight, round 5: below).
 __global__ __launch_bounds__(kBlock) void ot_centroid_members_kernel(const float *__restrict__ X, const int32_t *__restrict__ order,
                                                                      const int64_t *__restrict__ off, int k, int d, float *__restrict__ C,
@@ -291,6 +375,13 @@ __global__ __launch_bounds__(kBlock) void ot_centroid_members_kernel(const float
     const int c = t / d, j = t % d;
     const int64_t b = off[c], e = off[c + 1];
     float sum = 0.f;
+    if (d == 1) {                                           // one contiguous run: np.sum's order
+        int64_t q = b;
+        auto next = [&]() { return X[(size_t)order[q++]]; };
+        C[t] = __fdiv_rn(np_sum_stream(next, e - b), (float)(e - b));
+        if (counts) counts[c] = (int32_t)(e - b);
+        return;
+    }
     // the ADDS stay one after the other in ascending id; the loads need not: 32 member ids, then their 32 values, are requested together (one id, then
     // its value, then the add was two dependent memory levels per member: 6.6 ms for the 5,063 members of a cluster at n = 162,000, k = 32, d = 128)
     constexpr int kAhead = 32;
@@ -302,14 +393,13 @@ __global__ __launch_bounds__(kBlock) void ot_centroid_members_kernel(const float
         for (int u = 0; u < kAhead; ++u) id[u] = order[q + u];
 #pragma unroll
         for (int u = 0; u < kAhead; ++u) x[u] = X[(size_t)id[u] * d + j];
-        float s0 = q == b ? x[0] : __fadd_rn(sum, x[0]);
+        float s0 = __fadd_rn(sum, x[0]);
 #pragma unroll
         for (int u = 1; u < kAhead; ++u) s0 = __fadd_rn(s0, x[u]);
         sum = s0;
     }
     for (; q < e; ++q) {
-        const float x = X[(size_t)order[q] * d + j];
-        sum = q == b ? x : __fadd_rn(sum, x);
+        sum = __fadd_rn(sum, X[(size_t)order[q] * d + j]);
     }
     C[t] = __fdiv_rn(sum, (float)(e - b));
     if (j == 0 && counts) counts[c] = (int32_t)(e - b);
