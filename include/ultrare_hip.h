@@ -359,7 +359,8 @@ int ure_score(const float *const *U_tables, const float *const *V_tables, int n_
               float *pred, double *sse, void *stream);
 
 /* utils.py:165-184 for users whose entries are contiguous: user t owns entries
- * [off[t], off[t+1]).  For each user: top-10 by prediction and by rating (ties:
+ * [off[t], off[t+1]).  For each user: top-10 by prediction and by rating (values
+ * ordered as numpy orders float32: -inf < finite < +inf < NaN, -0.0 == +0.0; ties:
  * higher position first = stable argsort reversed), hits[t] = #(rating[top_pred]
  * >= 4/5), ndcg[t] = the reference's positional NDCG@10 (utils.py:190-210).
  * `log2_tab` [10] (device, float64) = log2(2..10) followed by the ideal DCG computeDCG(ones(10)),

@@ -42,6 +42,13 @@ def lib():
         L.ure_oracle_score.restype = None
         L.ure_oracle_score.argtypes = [ctypes.POINTER(_f32p), ctypes.POINTER(_f32p), ctypes.c_int32, _i32p, _i32p,
                                        ctypes.c_int64, ctypes.c_int32, _f32p]
+        L.ure_oracle_score_contract.restype = None
+        L.ure_oracle_score_contract.argtypes = [ctypes.POINTER(_f32p), ctypes.POINTER(_f32p), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32, _i32p, _i32p, ctypes.c_int64, ctypes.c_int32, _f32p]
+        L.ure_oracle_score_partials.restype = None
+        L.ure_oracle_score_partials.argtypes = [_f32p, _f32p, _i32p, _i32p, ctypes.c_int64, ctypes.c_int32, _f32p]
+        L.ure_oracle_score_sse.restype = None
+        L.ure_oracle_score_sse.argtypes = [_f32p, _f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
         L.ure_oracle_ot_cost.restype = None
         L.ure_oracle_ot_cost.argtypes = [_f32p, _f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _f32p]
         L.ure_oracle_centroids.restype = None
@@ -181,6 +188,85 @@ def score(models, uid, iid):
     return pred
 
 
+SCORE_PARTIALS = 2048          # URE_SCORE_PARTIALS (include/ultrare_hip.h): the cap on ure_score's workgroups = the length of sse
+
+
+def score_contract(models, uid, iid, n_total=None, first=True, last=True, running=None):
+    """The ure_score contract, bit for bit: per model and group of four columns a product and three fmaf, the d/4
+    partials as a balanced tree of adjacent pairs, the models in list order into one float32 accumulator that starts at 0
+    (first) or at `running`, with `last` one division by float32(n_total) (default: len(models))."""
+    S = len(models)
+    keep = [np.ascontiguousarray(m[0]) for m in models] + [np.ascontiguousarray(m[1]) for m in models]
+    Us = (_f32p * S)(*[_p(a, _f32p) for a in keep[:S]])
+    Vs = (_f32p * S)(*[_p(a, _f32p) for a in keep[S:]])
+    d = keep[0].shape[1]
+    assert d in (4, 8, 16, 32, 64, 128, 256) and all(a.shape[1] == d for a in keep)
+    pred = np.zeros(len(uid), dtype=np.float32) if first else np.array(running, dtype=np.float32)
+    assert len(pred) == len(uid)
+    lib().ure_oracle_score_contract(Us, Vs, S, S if n_total is None else n_total, int(first), int(last), _p(uid, _i32p), _p(iid, _i32p),
+                                    len(uid), d, _p(pred, _f32p))
+    return pred
+
+
+def score_partials(U, V, uid, iid):
+    """One model's d/4 partials per pair [n, d/4] (product + three fmaf per group of four columns): the leaves of the contract's tree."""
+    U, V = np.ascontiguousarray(U), np.ascontiguousarray(V)
+    part = np.empty((len(uid), U.shape[1] // 4), dtype=np.float32)
+    lib().ure_oracle_score_partials(_p(U, _f32p), _p(V, _f32p), _p(uid, _i32p), _p(iid, _i32p), len(uid), U.shape[1], _p(part, _f32p))
+    return part
+
+
+def score_sse_partials(pred, rating, d):
+    """The SCORE_PARTIALS doubles ure_score writes to sse for table width d (layout and order: DESIGN.md), bit for bit."""
+    sse = np.empty(SCORE_PARTIALS, dtype=np.float64)
+    lib().ure_oracle_score_sse(_p(pred, _f32p), _p(rating, _f32p), len(pred), d, SCORE_PARTIALS, _p(sse, ctypes.POINTER(ctypes.c_double)))
+    return sse
+
+
+def sum_vectors(vectors):
+    """ure_sum_vectors: the vectors added in list order into a float32 accumulator that starts at 0."""
+    acc = np.zeros(len(vectors[0]), dtype=np.float32)
+    for v in vectors:
+        acc = acc + np.asarray(v, dtype=np.float32)
+    return acc
+
+
+def tree_1024(x):
+    """The fixed order of ure_eval_reduce / ure_eval_subset over one array (float64 or int64): accumulator t of 1024 adds
+    x[t], x[t + 1024], ... in turn from zero, then the tree  for o = 512 ... 1: s[:o] += s[o:2o]."""
+    x = np.asarray(x)
+    acc = np.zeros(1024, dtype=x.dtype)
+    for b0 in range(0, len(x), 1024):
+        row = x[b0:b0 + 1024]
+        acc[:len(row)] = acc[:len(row)] + row
+    o = 512
+    while o:
+        acc[:o] = acc[:o] + acc[o:2 * o]
+        o //= 2
+    return acc[0]
+
+
+def eval_reduce(hits, ndcg, sse, n_rows):
+    """ure_eval_reduce's three numbers (rmse, mean NDCG, mean HR) in its order of operations."""
+    n_users = len(hits)
+    ts, tn, th = tree_1024(np.asarray(sse, np.float64)), tree_1024(np.asarray(ndcg, np.float64)), int(tree_1024(np.asarray(hits, np.int64)))
+    return np.array([np.sqrt(ts / np.float64(n_rows)),
+                     tn / np.float64(n_users) if n_users else 0.0,
+                     (np.float64(th) / 10.0) / np.float64(n_users) if n_users else 0.0])
+
+
+def eval_subset(sub_users, sub_pairs, pred, rating, hits, ndcg):
+    """ure_eval_subset's three numbers: the squared errors of the subset's pairs in float32, widened, and the per-user metrics of
+    its users, each in the order of tree_1024."""
+    e = (pred[sub_pairs] - rating[sub_pairs]).astype(np.float32)
+    ts = tree_1024((e * e).astype(np.float64))
+    tn, th = tree_1024(np.asarray(ndcg, np.float64)[sub_users]), int(tree_1024(np.asarray(hits, np.int64)[sub_users]))
+    n_sub, n_pairs = len(sub_users), len(sub_pairs)
+    return np.array([np.sqrt(ts / np.float64(n_pairs)) if n_pairs else 0.0,
+                     tn / np.float64(n_sub) if n_sub else 0.0,
+                     (np.float64(th) / 10.0) / np.float64(n_sub) if n_sub else 0.0])
+
+
 _LOG2 = np.log2(np.arange(2, 11))
 
 
@@ -198,23 +284,16 @@ def ndcg_at_k(r, top_k=10):
     return dcg(r) / dcg(np.ones(top_k))
 
 
-def eval_from_pred(uid, r, pred, batch, top_k=10):
-    """utils.py:127-187 given the ensemble prediction: RMSE over batch-wise fp32
-    losses, per-user HR@k and the reference's positional NDCG@k, users in
-    first-appearance order, argsort forced stable (SURVEY 7 'NDCG tie-breaking')."""
-    n = len(uid)
-    loss = 0.0
-    for b0 in range(0, n, batch):
-        e = pred[b0:b0 + batch] - r[b0:b0 + batch]
-        loss += float(np.float32((e * e).astype(np.float64).sum()))
-    rmse = float(np.sqrt(loss / n))
+def eval_users_from_pred(uid, r, pred, top_k=10):
+    """utils.py:156-184 per user: -> (users in first-appearance order, hits = the number of the user's top_k predictions whose
+    rating is at least 4/5, NDCG@k), argsort forced stable (SURVEY 7 'NDCG tie-breaking')."""
     _, first = np.unique(uid, return_index=True)
     users = uid[np.sort(first)]
     order = np.argsort(uid, kind='stable')
     su = uid[order]
     starts = np.searchsorted(su, users, side='left')
     ends = np.searchsorted(su, users, side='right')
-    ndcg, hr = [], []
+    ndcg, hits = [], []
     for s, e in zip(starts, ends):
         idx = order[s:e]
         ur = r[idx].astype(np.float64)
@@ -222,10 +301,25 @@ def eval_from_pred(uid, r, pred, batch, top_k=10):
         top_r = np.argsort(ur, kind='stable')[::-1][:top_k]
         top_p = np.argsort(up, kind='stable')[::-1][:top_k]
         rel = ur[top_p]
-        hr.append(sum(rel >= (4 / 5)) / top_k)
+        hits.append(sum(rel >= (4 / 5)))
         common = np.isin(top_r, top_p)
         rel = rel * (rel >= (4 / 5))
         ndcg.append(ndcg_at_k(rel * common, top_k))
+    return users, hits, ndcg
+
+
+def eval_from_pred(uid, r, pred, batch, top_k=10):
+    """utils.py:127-187 given the ensemble prediction: RMSE over batch-wise fp32
+    losses, per-user HR@k and the reference's positional NDCG@k, users in
+    first-appearance order."""
+    n = len(uid)
+    loss = 0.0
+    for b0 in range(0, n, batch):
+        e = pred[b0:b0 + batch] - r[b0:b0 + batch]
+        loss += float(np.float32((e * e).astype(np.float64).sum()))
+    rmse = float(np.sqrt(loss / n))
+    _, hits, ndcg = eval_users_from_pred(uid, r, pred, top_k)
+    hr = [h / top_k for h in hits]
     return rmse, float(np.mean(ndcg)), float(np.mean(hr))
 
 

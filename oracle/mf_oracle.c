@@ -206,3 +206,85 @@ void ure_oracle_centroids(const float *X, const int64_t *label, int64_t n, int32
         for (int32_t j = 0; j < d; ++j) C[(size_t)c * d + j] /= (float)cnt[c];
     free(cnt);
 }
+
+/* ---- The ure_score contract (DESIGN.md "The ure_score contract"; csrc/score_dot.h, csrc/mf_eval.hip score_kernel).  bit-exact. ----
+ * One model's score of a pair: column group j = columns 4j .. 4j+3 gives p_j = a0*b0, then three fmaf (one rounding each);
+ * the d/4 partials are added as a balanced tree of adjacent pairs ((p0+p1)+(p2+p3))+... -- what the xor butterfly over the
+ * lanes of a group computes on every lane.  d a power of two, 4 <= d <= 256. */
+static void contract_partials(const float *u, const float *v, int32_t d, float *part)
+{
+    for (int32_t j = 0; j < d / 4; ++j) {
+        const float *a = u + 4 * j, *b = v + 4 * j;
+        float p = a[0] * b[0];
+        p = fmaf(a[1], b[1], p);
+        p = fmaf(a[2], b[2], p);
+        p = fmaf(a[3], b[3], p);
+        part[j] = p;
+    }
+}
+
+static float contract_dot(const float *u, const float *v, int32_t d)
+{
+    float part[64];
+    const int32_t m = d / 4;
+    contract_partials(u, v, d, part);
+    for (int32_t w = 1; w < m; w <<= 1)
+        for (int32_t j = 0; j < m; j += 2 * w) part[j] += part[j + w];
+    return part[0];
+}
+
+/* part[j][c] = the partial of column group c of one model for pair j: what the tests build other summation orders from. */
+void ure_oracle_score_partials(const float *U, const float *V, const int32_t *uid, const int32_t *iid, int64_t n, int32_t d,
+                               float *part /* [n][d/4] */)
+{
+    for (int64_t j = 0; j < n; ++j)
+        contract_partials(U + (size_t)uid[j] * d, V + (size_t)iid[j] * d, d, part + (size_t)j * (d / 4));
+}
+
+/* pred[j] = (first ? 0 : pred[j]) + score_0 + score_1 + ... in list order, one float32 accumulator; with `last` one
+ * division by (float)n_models_total. */
+void ure_oracle_score_contract(const float *const *Us, const float *const *Vs, int32_t n_models, int32_t n_models_total,
+                               int32_t first, int32_t last, const int32_t *uid, const int32_t *iid, int64_t n, int32_t d,
+                               float *pred)
+{
+    for (int64_t j = 0; j < n; ++j) {
+        float acc = first ? 0.0f : pred[j];
+        for (int32_t m = 0; m < n_models; ++m)
+            acc += contract_dot(Us[m] + (size_t)uid[j] * d, Vs[m] + (size_t)iid[j] * d, d);
+        if (last) acc = acc / (float)n_models_total;
+        pred[j] = acc;
+    }
+}
+
+/* The squared-error partials ure_score leaves in sse[0 .. n_partials): G = 64 / (d/4) pairs per wavefront,
+ * blocks = min(ceil(ceil(n/G)/4), n_partials) workgroups of four waves.  Accumulator (workgroup b, wave w, group g) takes the
+ * pairs (b*4 + w)*G + g + k*blocks*4*G, k = 0, 1, ... in turn with sq = fmaf(e, e, sq), e = pred - rating in float32; a wave's
+ * G accumulators are added as an xor butterfly in float32, a workgroup's four waves in double, in order; slots past `blocks`
+ * are 0. */
+void ure_oracle_score_sse(const float *pred, const float *rating, int64_t n, int32_t d, int32_t n_partials, double *sse)
+{
+    const int32_t G = 64 / (d / 4);
+    const int64_t waves = (n + G - 1) / G;
+    int64_t blocks = (waves + 3) / 4;
+    if (blocks > n_partials) blocks = n_partials;
+    const int64_t n_acc = blocks * 4 * G;
+    for (int32_t b = 0; b < n_partials; ++b) sse[b] = 0.0;
+    for (int64_t b = 0; b < blocks; ++b) {
+        double t = 0.0;
+        for (int32_t w = 0; w < 4; ++w) {
+            float acc[64];
+            for (int32_t g = 0; g < G; ++g) {
+                float sq = 0.0f;
+                for (int64_t j = (b * 4 + w) * G + g; j < n; j += n_acc) {
+                    const float e = pred[j] - rating[j];
+                    sq = fmaf(e, e, sq);
+                }
+                acc[g] = sq;
+            }
+            for (int32_t o = 1; o < G; o <<= 1)
+                for (int32_t g = 0; g < G; g += 2 * o) acc[g] += acc[g + o];
+            t += (double)acc[0];
+        }
+        sse[b] = t;
+    }
+}

@@ -246,36 +246,47 @@ __global__ __launch_bounds__(kBlock) void series_combine_kernel(const float *own
 
 // (value, position) keys ordered lexicographically; "better" = later in a stable
 // ascending argsort, i.e. earlier in its reverse (utils.py:169-170).
-__device__ __forceinline__ bool key_gt(float v, int i, float bv, int bi) { return v > bv || (v == bv && i > bi); }
+__device__ __forceinline__ bool key_gt(int v, int i, int bv, int bi) { return v > bv || (v == bv && i > bi); }
 
-// A model that diverged (the reference's summed-loss SGD does on heavy users, e.g. two of the 16 shards of
-// BASELINE.json configs[4] on the synthetic set) predicts NaN.  np.argsort places NaN after every number, so its
-// reverse ranks NaN first: NaN is ordered as +inf here, which keeps the keys totally ordered -- without it no entry
-// has rank k for some k and the selection returns position -1.
-__device__ __forceinline__ float nan_last(float v) { return v != v ? __builtin_inff() : v; }
+// The values are ranked through an ordered integer key, the order np.argsort gives float32: -inf < finite < +inf < NaN,
+// -0.0 == +0.0, every NaN (either sign, any payload) the same key.  A model that diverged (the reference's summed-loss SGD
+// does on heavy users, e.g. two of the 16 shards of BASELINE.json configs[4] on the synthetic set) predicts +inf before it
+// predicts NaN; np.argsort places NaN after every number, +inf included, so its reverse ranks NaN first, then +inf.  (NaN
+// ordered AS +inf -- the earlier rule -- tied the two and let the position decide.)  The keys are totally ordered, so
+// every rank has exactly one entry; without that the selection returns position -1.
+//   b >= 0: the bits themselves (+0 = 0 ... +inf = 0x7F800000);  b < 0: 0x80000000 - b = minus the magnitude (-0.0 -> 0,
+//   -inf -> -0x7F800000).  kKeyNone is below every key: the padding of lanes past a segment, "greater than nothing" under the
+//   strict count even when the segment holds a real -inf.
+constexpr int kKeyNone = INT_MIN;
+__device__ __forceinline__ int rank_key(float v)
+{
+    const int b = __builtin_bit_cast(int, v);
+    const int k = b < 0 ? (int)(0x80000000u - (unsigned)b) : b;
+    return v != v ? INT_MAX : k;
+}
 
 // The best (value, position) key of the wave, on every lane: four DPP exchanges inside each row of 16 lanes, then the four row
 // winners through scalar registers.  (As six __shfl_xor steps -- twelve dependent ds_bpermute -- a selection round took ~0.8 us
 // and the ten rounds of the 199 users with more than 64 test entries were the tail of every eval launch: 8 us for one member, r3.)
 template <int CTRL>
-__device__ __forceinline__ void argmax_step(float &v, int &i)
+__device__ __forceinline__ void argmax_step(int &v, int &i)
 {
-    const float ov = dpp_f<CTRL>(v);
+    const int ov = dpp_i<CTRL>(v);
     const int oi = dpp_i<CTRL>(i);
     if (key_gt(ov, oi, v, i)) { v = ov; i = oi; }
 }
-__device__ __forceinline__ void wave_argmax(float &v, int &i)
+__device__ __forceinline__ void wave_argmax(int &v, int &i)
 {
     argmax_step<kDppQuadXor1>(v, i);
     argmax_step<kDppQuadXor2>(v, i);
     argmax_step<kDppHalfMirror>(v, i);
     argmax_step<kDppRowMirror>(v, i);
-    const int vi = __builtin_bit_cast(int, v);
-    float bv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 0));
+    const int vi = v;
+    int bv = __builtin_amdgcn_readlane(vi, 0);
     int bi = __builtin_amdgcn_readlane(i, 0);
 #pragma unroll
     for (int r = 1; r < 4; ++r) {
-        const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 16 * r));
+        const int ov = __builtin_amdgcn_readlane(vi, 16 * r);
         const int oi = __builtin_amdgcn_readlane(i, 16 * r);
         if (key_gt(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
@@ -287,19 +298,19 @@ __device__ __forceinline__ void wave_argmax(float &v, int &i)
 template <int K>
 __device__ __forceinline__ void top_k_positions(const float *__restrict__ val, int cnt, int lane, int (&top)[K])
 {
-    float pv = FLT_MAX;   // previous pick: everything is "less" than it on the first round
+    int pv = INT_MAX;     // previous pick: everything is "less" than it on the first round
     int pi = INT_MAX;
     bool pinf = true;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        float bv = -FLT_MAX;
+        int bv = kKeyNone;
         int bi = -1;
         for (int t = lane; t < cnt; t += kWave) {
-            const float v = nan_last(val[t]);
+            const int v = rank_key(val[t]);
             const bool below_prev = pinf || v < pv || (v == pv && t < pi);
             if (below_prev && (bi < 0 || key_gt(v, t, bv, bi))) { bv = v; bi = t; }
         }
-        // lanes without a candidate carry (−FLT_MAX, −1), which loses to any real key
+        // lanes without a candidate carry (kKeyNone, −1), which loses to any real key
         wave_argmax(bv, bi);
         top[k] = bi;
         pv = bv; pi = bi; pinf = false;
@@ -313,17 +324,17 @@ __device__ __forceinline__ void top_k_positions(const float *__restrict__ val, i
 // and are exact unless two of the ten best keys are EQUAL, which shows as two entries with one rank; only then (the wave
 // decides as one) the ranks are counted again with the position as the tie-break.  Ratings tie all the time: FAST off.
 template <int K, bool FAST = false>
-__device__ __forceinline__ void top_k_in_registers(float val, int cnt, int lane, int (&top)[K])
+__device__ __forceinline__ void top_k_in_registers(int val, int cnt, int lane, int (&top)[K])
 {
     // entry t is broadcast through a scalar register (v_readlane: t is wave-uniform) -- a ds_bpermute per entry, as __shfl
     // compiles to, sends all 64 lanes through the LDS crossbar for it (eval_users: 125 -> 7x us per series call, r3)
-    const int vi = __builtin_bit_cast(int, val);
+    const int vi = val;
     // the lanes that hold an entry, as a mask: a ballot of (lane < cnt && rank == k) compiles to a select and a second compare
     const unsigned long long valid = __builtin_amdgcn_ballot_w64(lane < cnt);
     int rank = 0;
     bool exact = !FAST;
     if (FAST) {
-        for (int t = 0; t < cnt; ++t) rank += __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, t)) > val ? 1 : 0;
+        for (int t = 0; t < cnt; ++t) rank += __builtin_amdgcn_readlane(vi, t) > val ? 1 : 0;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const unsigned long long m = __builtin_amdgcn_ballot_w64(rank == k) & valid;
@@ -334,7 +345,7 @@ __device__ __forceinline__ void top_k_in_registers(float val, int cnt, int lane,
     if (exact) {
         rank = 0;
         for (int t = 0; t < cnt; ++t) {
-            const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, t));
+            const int ov = __builtin_amdgcn_readlane(vi, t);
             rank += key_gt(ov, t, val, lane) ? 1 : 0;
         }
 #pragma unroll
@@ -349,14 +360,14 @@ __device__ __forceinline__ void top_k_in_registers(float val, int cnt, int lane,
 // round takes the best not-yet-taken key of the wave (no memory access per round).
 constexpr int kRegItems = 8;
 template <int K, int R>
-__device__ __forceinline__ void top_k_multi(const float (&val)[R], int cnt, int lane, int (&top)[K])
+__device__ __forceinline__ void top_k_multi(const int (&val)[R], int cnt, int lane, int (&top)[K])
 {
     unsigned taken = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) taken |= (lane + r * kWave >= cnt ? 1u : 0u) << r;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        float bv = -FLT_MAX;
+        int bv = kKeyNone;
         int bi = -1;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -372,18 +383,18 @@ __device__ __forceinline__ void top_k_multi(const float (&val)[R], int cnt, int 
 // One rotation of a 16-lane row by N lanes (DPP row_ror): a VALU move, no LDS crossbar.  The entry's position travels with
 // its value, so nothing here depends on the direction of the rotation.
 template <int N>
-__device__ __forceinline__ void quarter_rank_steps(const int vi, const int s, const int cnt, const float val, int &rank)
+__device__ __forceinline__ void quarter_rank_steps(const int vi, const int s, const int cnt, const int val, int &rank)
 {
-    const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x120 + N, 0xF, 0xF, false));
+    const int ov = __builtin_amdgcn_update_dpp(0, vi, 0x120 + N, 0xF, 0xF, false);
     const int ot = __builtin_amdgcn_update_dpp(0, s, 0x120 + N, 0xF, 0xF, false);
     rank += (ot < cnt && key_gt(ov, ot, val, s)) ? 1 : 0;
     if constexpr (N < 15) quarter_rank_steps<N + 1>(vi, s, cnt, val, rank);
 }
-// The strict comparison alone (lanes past the segment carry -inf, which is greater than nothing): no position travels.
+// The strict comparison alone (lanes past the segment carry kKeyNone, which is greater than nothing): no position travels.
 template <int N>
-__device__ __forceinline__ void quarter_rank_steps_strict(const int vi, const float val, int &rank)
+__device__ __forceinline__ void quarter_rank_steps_strict(const int vi, const int val, int &rank)
 {
-    rank += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x120 + N, 0xF, 0xF, false)) > val ? 1 : 0;
+    rank += __builtin_amdgcn_update_dpp(0, vi, 0x120 + N, 0xF, 0xF, false) > val ? 1 : 0;
     if constexpr (N < 15) quarter_rank_steps_strict<N + 1>(vi, val, rank);
 }
 
@@ -391,14 +402,14 @@ __device__ __forceinline__ void quarter_rank_steps_strict(const int vi, const fl
 // the in-register selection of top_k_in_registers at width 16, four users per wavefront.  FAST as there: the wave falls
 // back to the exact count when any of its four users has equal keys among its ten best.
 template <int K, bool FAST = false>
-__device__ __forceinline__ void top_k_quarter(float val, int cnt, int lane, int (&top)[K])
+__device__ __forceinline__ void top_k_quarter(int val, int cnt, int lane, int (&top)[K])
 {
     const int g16 = lane & ~15, s = lane & 15;
     int rank = 0;
     bool exact = !FAST;
     if (FAST) {
-        const float padded = s < cnt ? val : -__builtin_inff();
-        quarter_rank_steps_strict<1>(__builtin_bit_cast(int, padded), padded, rank);
+        const int padded = s < cnt ? val : kKeyNone;
+        quarter_rank_steps_strict<1>(padded, padded, rank);
         bool tie = false;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -411,7 +422,7 @@ __device__ __forceinline__ void top_k_quarter(float val, int cnt, int lane, int 
     }
     if (exact) {
         rank = 0;
-        quarter_rank_steps<1>(__builtin_bit_cast(int, val), s, cnt, val, rank);      // all 15 other lanes of the row, one rotation each
+        quarter_rank_steps<1>(val, s, cnt, val, rank);      // all 15 other lanes of the row, one rotation each
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const unsigned long long m = __ballot(s < cnt && rank == k);
@@ -499,12 +510,11 @@ __device__ __forceinline__ void user_metrics(const float *__restrict__ rating, i
 template <bool IS_PRED, int R>
 __device__ __forceinline__ void multi_items(const float *__restrict__ val, int beg, int cnt, int lane, int (&top)[10])
 {
-    float v[R];
+    int v[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int t = lane + r * kWave;
-        v[r] = t < cnt ? val[beg + t] : 0.f;
-        if (IS_PRED) v[r] = nan_last(v[r]);
+        v[r] = t < cnt ? rank_key(val[beg + t]) : kKeyNone;
     }
     top_k_multi<10, R>(v, cnt, lane, top);
 }
@@ -516,8 +526,7 @@ __device__ __forceinline__ void rank_wide(const float *__restrict__ val, int beg
     constexpr int K = 10;
     if (cnt <= kWave) {
         // the common case (the items fit one per lane): ten ballots after `cnt` broadcasts, no memory access per round
-        float v = lane < cnt ? val[beg + lane] : 0.f;
-        if (IS_PRED) v = nan_last(v);
+        const int v = lane < cnt ? rank_key(val[beg + lane]) : kKeyNone;
         top_k_in_registers<K, IS_PRED>(v, cnt, lane, top);
     } else if (cnt <= kWave * 2) {
         // heavier users: a few entries per lane (2, or up to 8), loaded once; ten arg-max rounds in registers
@@ -592,11 +601,11 @@ __global__ __launch_bounds__(kBlock) void eval_users_kernel(const int32_t *__res
     const float own_rating = s < cnt ? rating[beg + s] : 0.f;
     int trj = -1;
     if (top_rating && have && s < K) trj = top_rating[(size_t)user * 10 + s];
-    const float pv = s < cnt ? nan_last(pred[beg + s]) : 0.f;
+    const int pv = s < cnt ? rank_key(pred[beg + s]) : kKeyNone;
     top_k_quarter<K, true>(pv, cnt, lane, tp);
     if (!top_rating) {
         int tr[K];
-        top_k_quarter<K>(own_rating, cnt, lane, tr);
+        top_k_quarter<K>(rank_key(own_rating), cnt, lane, tr);
 #pragma unroll
         for (int k = 0; k < K; ++k) trj = s == k ? tr[k] : trj;
     }
@@ -627,18 +636,18 @@ __device__ __forceinline__ unsigned row_sum_u32(unsigned v)
 // over its own 16-lane row by DPP rotations and over the half's other row through one cross-row move followed by the same rotations
 // (a wavefront each -- `cnt` scalar broadcasts for one user -- was what such users cost before: a fifth of a 10 % hold-out of ml-1m).
 template <int N>
-__device__ __forceinline__ void half_other_steps_strict(const int ovi, const float val, int &rank)
+__device__ __forceinline__ void half_other_steps_strict(const int ovi, const int val, int &rank)
 {
     const int r = N == 0 ? ovi : __builtin_amdgcn_update_dpp(0, ovi, 0x120 + (N == 0 ? 1 : N), 0xF, 0xF, false);
-    rank += __builtin_bit_cast(float, r) > val ? 1 : 0;
+    rank += r > val ? 1 : 0;
     if constexpr (N < 15) half_other_steps_strict<N + 1>(ovi, val, rank);
 }
 template <int N>
-__device__ __forceinline__ void half_other_steps(const int ovi, const int os, const int cnt, const float val, const int s, int &rank)
+__device__ __forceinline__ void half_other_steps(const int ovi, const int os, const int cnt, const int val, const int s, int &rank)
 {
     const int rv = N == 0 ? ovi : __builtin_amdgcn_update_dpp(0, ovi, 0x120 + (N == 0 ? 1 : N), 0xF, 0xF, false);
     const int rs = N == 0 ? os : __builtin_amdgcn_update_dpp(0, os, 0x120 + (N == 0 ? 1 : N), 0xF, 0xF, false);
-    rank += (rs < cnt && key_gt(__builtin_bit_cast(float, rv), rs, val, s)) ? 1 : 0;
+    rank += (rs < cnt && key_gt(rv, rs, val, s)) ? 1 : 0;
     if constexpr (N < 15) half_other_steps<N + 1>(ovi, os, cnt, val, s, rank);
 }
 // sum over the 32 lanes of a half wave (every lane ends with the total)
@@ -699,9 +708,9 @@ __global__ __launch_bounds__(kBlock) void eval_rank_kernel(const int32_t *__rest
         const bool have = user < n_wide + n_half;
         const int s = lane & 31;
         const int beg = have ? off[user] : 0, cnt = have ? off[user + 1] - beg : 0;       // cnt <= 32 by the caller's ordering
-        const float pv = s < cnt ? nan_last(pred[beg + s]) : -__builtin_inff();
+        const int pv = s < cnt ? rank_key(pred[beg + s]) : kKeyNone;
         const int n_top = cnt < K ? cnt : K;
-        const int pvi = __builtin_bit_cast(int, pv);
+        const int pvi = pv;
         const int ovi = __shfl_xor(pvi, 16, kWave);                                        // the entry at the same place of the half's other row
         int rank = 0;
         quarter_rank_steps_strict<1>(pvi, pv, rank);
@@ -730,10 +739,10 @@ __global__ __launch_bounds__(kBlock) void eval_rank_kernel(const int32_t *__rest
     const bool have = user < n_users;
     const int s = lane & 15;
     const int beg = have ? off[user] : 0, cnt = have ? off[user + 1] - beg : 0;       // cnt <= 16 by the caller's ordering
-    const float pv = s < cnt ? nan_last(pred[beg + s]) : -__builtin_inff();           // lanes past the segment: greater than nothing
+    const int pv = s < cnt ? rank_key(pred[beg + s]) : kKeyNone;                      // lanes past the segment: greater than nothing
     const int n_top = cnt < K ? cnt : K;
     int rank = 0;
-    quarter_rank_steps_strict<1>(__builtin_bit_cast(int, pv), pv, rank);
+    quarter_rank_steps_strict<1>(pv, pv, rank);
     // positions 0-4 in w0, 5-9 in w1 (4 bits each); chk = (lanes with one of the first n_top ranks) << 16 | the sum of those ranks
     bool in_top = s < cnt && rank < n_top;
     unsigned w0 = row_sum_u32(in_top && rank < 5 ? (unsigned)s << (4 * rank) : 0u);
@@ -744,7 +753,7 @@ __global__ __launch_bounds__(kBlock) void eval_rank_kernel(const int32_t *__rest
     const bool tie = chk != ((unsigned)n_top << 16) + (unsigned)(n_top * (n_top - 1) / 2);
     if (__builtin_amdgcn_ballot_w64(tie) != 0) {
         rank = 0;
-        quarter_rank_steps<1>(__builtin_bit_cast(int, pv), s, cnt, pv, rank);
+        quarter_rank_steps<1>(pv, s, cnt, pv, rank);
         in_top = s < cnt && rank < n_top;
         w0 = row_sum_u32(in_top && rank < 5 ? (unsigned)s << (4 * rank) : 0u);
         w1 = row_sum_u32(in_top && rank >= 5 ? (unsigned)s << (4 * (rank - 5)) : 0u);
