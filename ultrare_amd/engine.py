@@ -16,6 +16,7 @@ HBM layout of one shard:
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -388,6 +389,54 @@ def _closed_form_scalars(lr_host, steps, lam, mu):
     return np.asarray(out, dtype=np.float32)
 
 
+def touch_plan(steps_max, d, batch, live_bytes, lazy_rows, snapshots, touch, final_only, epoch_reads, env=None):
+    """The step kernel of a job: -> touch_mode 0 (the default kernel), 1, 2 or 3.  steps_max = optimizer steps per epoch of the job's
+    longest shard, d = the padded table width, live_bytes = the job's live rows (w, m, second buffer), snapshots / touch /
+    final_only / epoch_reads = TrainJob's arguments as given; env = the environment switches (None: os.environ, read now)."""
+    env = os.environ if env is None else env
+    use_index = env.get('URE_TOUCH_INDEX', '1')
+    # touch mode (csrc/mf_touch.h): a step visits only the rows it trains, the others are advanced in closed form when
+    # they are next trained.  Pays when the tables do not fit the caches (configs[3]); URE_TOUCH=0/1 overrides the rule.
+    by_rule = False
+    if touch is None:
+        use_touch = env.get('URE_TOUCH', 'auto')
+        by_rule = use_touch == 'auto' and live_bytes > TOUCH_MIN_TABLE_BYTES and bool(final_only or epoch_reads)
+        touch = (use_touch == '1') or by_rule
+    if not (bool(touch) and lazy_rows and steps_max <= TOUCH_MAX_STEPS):
+        return 0
+    # touch_mode 2 (csrc/mf_touch.h, "masks one epoch ahead"): no dense pass at the epoch starts; for callers that read the tables
+    # only after the last epoch (final_only) and epochs of at most 63 steps.  URE_TOUCH_AHEAD=0 keeps mode 1.
+    # Short epochs (<= 63 steps) of NARROW rows: sorting the epoch's slots by step (touch_mode 3) costs ~3 ms per epoch whatever the row width, and saves the
+    # scan of every trained row's slots in every step -- most of the traffic at 64-byte rows.  BASELINE.json configs[3]'s shape (32 shards, 27 steps per
+    # epoch), epoch time in touch_mode 2 -> 3: d = 16 6.32 -> 4.95 ms, d = 32 6.25 -> 5.87, d = 64 8.36 -> 8.02, d = 128 12.18 -> 13.17
+    # (profiles/r04/exp_short_epochs_index.txt).  Under the auto rule touch_mode 3 is taken up to d = 64.
+    force_index = touch == 'index' or use_index == '2' or (by_rule and d <= INDEX_SHORT_EPOCH_MAX_D and use_index != '0')
+    if final_only and steps_max <= TOUCH_AHEAD_MAX_STEPS and snapshots in (False, None, 'compact') and env.get('URE_TOUCH_AHEAD', '1') != '0' and not force_index:
+        return 2
+    # touch_mode 3 (csrc/mf_index.h): epochs of more than 63 steps -- the epoch's slots are sorted by step at its start and a step
+    # launches over exactly the rows it trains (64-step windows look at every work unit in every step).  URE_TOUCH_INDEX=0 keeps windows.
+    if steps_max <= INDEX_MAX_STEPS and batch <= 200000 and (force_index or (steps_max > TOUCH_AHEAD_MAX_STEPS and use_index != '0')):
+        return 3
+    return 1
+
+
+def shard_regions(n_user, n_item, n_active, d, epochs, lazy_rows, snapshots, at=0, snap_at=0):
+    """Where one shard's tables live in a job's two device pools: -> (pool, snap, end, snap_end), pool and snap dicts name -> (first float,
+    floats, view shape); the shard starts at `at` / `snap_at` (multiples of 64), the next one at end / snap_end.  The float pool: U and V
+    (both buffers), mU, mV, sse and -- lazy_rows -- the start tables U0, V0, each rounded up to 64 floats.  The snapshot pool: snapU and
+    straight after it snapV ('full') or snap ('compact': the n_active rows), the shard's snapshots as a whole rounded up to 64 floats."""
+    al = lambda x: (x + 63) // 64 * 64
+    pool, snap, E = {}, {}, epochs
+    for name, shape in (('U', (2, n_user, d)), ('V', (2, n_item, d)), ('mU', (n_user, d)), ('mV', (n_item, d)), ('sse', (E, n_user)),
+                        ('U0', (n_user if lazy_rows else 0, d)), ('V0', (n_item if lazy_rows else 0, d))):
+        pool[name] = (at, math.prod(shape), shape)
+        at += al(math.prod(shape))
+    for name, shape in {'full': (('snapU', (E, n_user, d)), ('snapV', (E, n_item, d))), 'compact': (('snap', (E, n_active, d)),)}.get(snapshots, ()):
+        snap[name] = (snap_at, math.prod(shape), shape)
+        snap_at += math.prod(shape)
+    return pool, snap, at, al(snap_at)
+
+
 class _States:
     """TrainJob.state: per shard the views of the job's device memory ({'U', 'V', 'mU', 'mV', 'perm', 'sse', 'snap' ...}), made when first asked for."""
 
@@ -431,183 +480,154 @@ class TrainJob:
         epoch), True / False, or 'index' (touch_mode 3 whatever the epoch length)."""
         assert len(shards) == len(inits) == len(perms) and len(shards) > 0
         self.shards, self.k, self.d = shards, int(k), pad_dim(int(k))
-        self.batch, self.epochs = int(batch), int(epochs)
-        dev = shards[0].device
-        self.device = dev
+        self.batch, self.epochs, self.device = int(batch), int(epochs), shards[0].device
         # StepLR(step_size=50, gamma): lr of epoch t (scratch.py:69,79-80)
-        lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
-        self._lr_host = lr_host
+        self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
+        self._lam, self._mu = float(lam), float(momentum)
         # rows a shard never touches only decay: advance them in closed form when the tables are read
         # (URE_LAZY_ROWS=0 streams them every step, exactly as the reference's dense optimizer does)
         self.lazy_rows = LAZY_ROWS if lazy_rows is None else bool(lazy_rows)
         self._fresh = 0          # ticks for which the lazily advanced rows are up to date
-        # touch mode (csrc/mf_touch.h): a step visits only the rows it trains, the others are advanced in closed form when
-        # they are next trained.  Pays when the tables do not fit the caches (configs[3]); URE_TOUCH=0/1 overrides the rule.
-        steps_all = [(sh.N + self.batch - 1) // self.batch for sh in shards]
-        by_rule = False
-        if touch is None:
-            env = os.environ.get('URE_TOUCH', 'auto')
-            live = sum(sh.n_active for sh in shards) * self.d * 12
-            by_rule = env == 'auto' and live > TOUCH_MIN_TABLE_BYTES and (final_only or epoch_reads)
-            touch = (env == '1') or by_rule
-        self.touch = bool(touch) and self.lazy_rows and max(steps_all) <= TOUCH_MAX_STEPS
-        # touch_mode 2 (csrc/mf_touch.h, "masks one epoch ahead"): no dense pass at the epoch starts; for callers that read the tables
-        # only after the last epoch (final_only) and epochs of at most 63 steps.  URE_TOUCH_AHEAD=0 keeps mode 1.
-        # Short epochs (<= 63 steps) of NARROW rows: sorting the epoch's slots by step (touch_mode 3) costs ~3 ms per epoch whatever the row width, and saves the
-        # scan of every trained row's slots in every step -- most of the traffic at 64-byte rows.  BASELINE.json configs[3]'s shape (32 shards, 27 steps per
-        # epoch), epoch time in touch_mode 2 -> 3: d = 16 6.32 -> 4.95 ms, d = 32 6.25 -> 5.87, d = 64 8.36 -> 8.02, d = 128 12.18 -> 13.17
-        # (profiles/r04/exp_short_epochs_index.txt).  Under the auto rule touch_mode 3 is taken up to d = 64.
-        force_index = touch == 'index' or os.environ.get('URE_TOUCH_INDEX', '1') == '2' or (by_rule and self.d <= INDEX_SHORT_EPOCH_MAX_D and
-                                                                                             os.environ.get('URE_TOUCH_INDEX', '1') != '0')
-        self.ahead = (self.touch and bool(final_only) and max(steps_all) <= TOUCH_AHEAD_MAX_STEPS and snapshots in (False, None, 'compact')
-                      and os.environ.get('URE_TOUCH_AHEAD', '1') != '0' and not force_index)
-        # touch_mode 3 (csrc/mf_index.h): epochs of more than 63 steps -- the epoch's slots are sorted by step at its start and a step
-        # launches over exactly the rows it trains (64-step windows look at every work unit in every step).  URE_TOUCH_INDEX=0 keeps windows.
-        self.index = (self.touch and not self.ahead and max(steps_all) <= INDEX_MAX_STEPS and self.batch <= 200000 and
-                      (force_index or (max(steps_all) > TOUCH_AHEAD_MAX_STEPS and os.environ.get('URE_TOUCH_INDEX', '1') != '0')))
+        self._steps = [(sh.N + self.batch - 1) // self.batch for sh in shards]          # optimizer steps per epoch
+        self.touch_mode = touch_plan(max(self._steps), self.d, self.batch, sum(sh.n_active for sh in shards) * self.d * 12, self.lazy_rows,
+                                     snapshots, touch, final_only, epoch_reads)
+        self.touch, self.ahead, self.index = self.touch_mode > 0, self.touch_mode == 2, self.touch_mode == 3
         # end-of-epoch snapshots: 'compact' keeps the n_active rows with interactions only (every other row is a_e * w0 and is
         # rebuilt where it is read: ure_eval_series_compact; needs lazy_rows), True / 'full' keeps complete tables
         self.snapshots = ('compact' if self.lazy_rows else 'full') if snapshots == 'compact' else ('full' if snapshots else False)
-        steps_of = [(sh.N + self.batch - 1) // self.batch for sh in shards]
-        small = [lr_host] + ([closed_form_scalars(lr_host, st_, float(np.float32(lam)), float(np.float32(momentum))) for st_ in steps_of] if self.snapshots else [])
-        small = upload_many(small, dev)                  # the learning rates and every shard's closed-form scalars: one copy
-        self.lr = small[0]
+        small = [self._lr_host] + ([closed_form_scalars(self._lr_host, st_, float(np.float32(lam)), float(np.float32(momentum))) for st_ in self._steps]
+                                   if self.snapshots else [])
+        self._small = upload_many(small, self.device)          # the learning rates and every shard's closed-form scalars: one copy
+        self.lr = self._small[0]
         self._arrivals = []      # the rng.Arrival of every order that has one: run() waits for their chunks, check_tags() reads their flags
         self.wait_marks = None   # a list: run() adds an event pair around each wait of its stream for a chunk (bench.py)
-        descs = (nv.UreShard * len(shards))()
-        from . import rng
+        self._descs = (nv.UreShard * len(shards))()
         mark('job: start')
-        cur = torch.cuda.current_stream(dev) if torch.device(dev).type == 'cuda' else None
-        seen = set()
+        cur = torch.cuda.current_stream(self.device) if torch.device(self.device).type == 'cuda' else None
+        seen = set()             # the events this stream already waits for
         for sh in shards:
             if sh.ready is not None and id(sh.ready) not in seen:
                 seen.add(id(sh.ready))
                 cur.wait_event(sh.ready)
-        # every float table of every shard from ONE zero-filled allocation (a request of 16 shards made ~130 small allocations
-        # and fills here: 8-12 ms of host time beside 16 busy worker threads), the snapshots from another.  The descriptors are
-        # filled from ADDRESSES (base + offset); the views of the tables are made when somebody asks for them (self.state), which a
-        # request does after its launches are queued.
-        al = lambda x: (x + 63) // 64 * 64
-        d = self.d
-        sizes = [(2 * sh.n_user * d, 2 * sh.n_item * d, sh.n_user * d, sh.n_item * d, self.epochs * sh.n_user,
-                  sh.n_user * d if self.lazy_rows else 0, sh.n_item * d if self.lazy_rows else 0) for sh in shards]
-        pool = torch.zeros(sum(al(x) for sz in sizes for x in sz), dtype=torch.float32, device=dev)
-        snap_rows = [(sh.n_active if self.snapshots == 'compact' else sh.n_user + sh.n_item) if self.snapshots else 0 for sh in shards]
-        snap_pool = torch.empty(sum(al(self.epochs * r * d) for r in snap_rows), dtype=torch.float32, device=dev) if self.snapshots else None
-        self._pool, self._snap_pool, self._small = pool, snap_pool, small
-        base, snap_base = pool.data_ptr(), (snap_pool.data_ptr() if snap_pool is not None else 0)
-        at = snap_at = 0
+        self._allocate_pools()
         mark('job: pools')
-        self._offs, self._snap_offs, self._perms, self._init_src = [], [], [], []
-        copies = []                                   # (src, rows, dst, dst2) of the start tables: one launch below
-        for s, (sh, (U0, V0), perm) in enumerate(zip(shards, inits, perms)):
-            srcs = []
-            for t, n_rows in ((U0, sh.n_user), (V0, sh.n_item)):
-                ev = getattr(t, '_ure_event', None)
-                if ev is not None and id(ev) not in seen:               # uploaded on a side stream (rng.shard_draws_async)
-                    seen.add(id(ev))
-                    cur.wait_event(ev)
-                if ev is not None:
-                    t.record_stream(cur)
-                t = torch.as_tensor(t, dtype=torch.float32)
-                assert t.shape == (n_rows, self.k)
-                if t.device != torch.device(dev) or not t.is_contiguous():
-                    t = t.to(dev, non_blocking=True).contiguous()
-                srcs.append(t)
-            self._init_src.append(srcs)                                 # (alive until the copy below has run: released by close())
-            off = []
-            for x in sizes[s]:
-                off.append(at)
-                at += al(x)
-            self._offs.append(off)
-            pU, pV, pmU, pmV, psse, pU0, pV0 = (base + 4 * o for o in off)
-            arrival = rng.Arrival.of(perm)                  # (before a conversion could make another tensor)
-            if arrival is not None:
-                self._arrivals.append(arrival)
-                if arrival.whole:                           # uploaded on a side stream in one piece (rng.epoch_perms_async)
-                    arrival.wait(cur, self.epochs)
-            perm = torch.as_tensor(perm)
-            assert perm.shape == (self.epochs, sh.N), f'perm of shard {s} must be [epochs, N]'
-            # int16: not permutations but the batch tags the host made of them (rng.epoch_tags; struct ure_shard: file_tags)
-            as_tags = perm.dtype == torch.int16
-            perm = perm.to(device=dev, dtype=torch.int16 if as_tags else torch.int32).contiguous()
-            self._perms.append(perm)
-            D = descs[s]
-            for name in ('ent_oid', 'ent_r', 'ent_tag', 'ent_src', 'file_tag', 'inv_stage', 'inv_off', 'sched'):
-                setattr(D, name, sh.ptr(name))
-            if self.index:
-                # no work units: the step's items come from the epoch's index.  Rows by weight class (slots per step on average)
-                nnz, st_s = sh._sched_head[:min(sh.n_active, INDEX_HEAVY_MAX), 3], steps_all[s]
-                D.n_multi = int(np.count_nonzero(nnz >= INDEX_HEAVY_SLOTS * st_s))
-                D.n_split = min(D.n_multi, int(np.count_nonzero(nnz >= INDEX_SPLIT_SLOTS * st_s)))
-                units, n_units = sh.ptr('sched'), 0
-            elif self.touch:
-                # epochs of several windows (more than 64 steps): a row of up to TOUCH_ROW_PASSES scan passes stays ONE work item -- its
-                # lane group skips the passes without a slot of the step (csrc/mf_touch.h: pass masks) -- instead of one unit per pass
-                long_epochs = max(steps_all) > 64
-                units, n_units, n_multi = sh.units(self.d, touch=True, min_passes=TOUCH_ROW_PASSES if long_epochs else 1,
-                                                   unit_passes=TOUCH_UNIT_PASSES if long_epochs else 1)
-                D.n_multi = n_multi
-                units = nv.ptr(units)
-            else:
-                units = sh.units(self.d)
-                n_units = units.shape[0]
-                units = nv.ptr(units)
-            D.units, D.n_units, D.n_active, D.n_slots = units, n_units, sh.n_active, sh.n_slots
-            D.U[0], D.U[1] = pU, pU + 4 * sh.n_user * d
-            D.V[0], D.V[1] = pV, pV + 4 * sh.n_item * d
-            D.mU, D.mV = pmU, pmV
-            D.perm, D.lr, D.sse = (None if as_tags else nv.ptr(perm)), nv.ptr(self.lr), psse
-            D.file_tags = nv.ptr(perm) if as_tags else None
-            D.N, D.n_user, D.n_item, D.d = sh.N, sh.n_user, sh.n_item, self.d
-            D.batch, D.epochs = self.batch, self.epochs
-            D.lam, D.mu = float(lam), float(momentum)
-            D.touch_mode = (3 if self.index else 2 if self.ahead else 1) if self.touch else 0
-            self._snap_offs.append(snap_at)
-            if self.snapshots:
-                D.snap_a = small[1 + s].data_ptr()
-                if self.snapshots == 'compact':
-                    D.snap, D.row_slot = snap_base + 4 * snap_at, sh.ptr('_row_slot')
-                else:
-                    D.snapU, D.snapV = snap_base + 4 * snap_at, snap_base + 4 * (snap_at + self.epochs * sh.n_user * d)
-                snap_at += al(self.epochs * snap_rows[s] * d)
-            if self.lazy_rows:
-                D.U0, D.V0, D.lr_host, D.lazy_rows = pU0, pV0, lr_host.ctypes.data, 1
-            copies += [(srcs[0].data_ptr(), sh.n_user, pU, pU0 if self.lazy_rows else 0), (srcs[1].data_ptr(), sh.n_item, pV, pV0 if self.lazy_rows else 0)]
-        # the start tables into buffer 0 (and the closed form's copy), every shard's in one launch
-        n_c = len(copies)
-        src_a, dst_a, dst2_a = (ctypes.c_void_p * n_c)(*[c[0] for c in copies]), (ctypes.c_void_p * n_c)(*[c[2] for c in copies]), \
-            (ctypes.c_void_p * n_c)(*[c[3] or None for c in copies])
-        rows_a = (ctypes.c_int64 * n_c)(*[c[1] for c in copies])
-        nv.check(nv.lib().ure_copy_rows_batch(n_c, src_a, dst_a, dst2_a if self.lazy_rows else None, rows_a, self.k, d, nv.stream_handle()), 'ure_copy_rows_batch')
-        self._init_src = None             # (allocator: their memory is reused only after the streams they were recorded on have passed this point)
+        self._perms, self._init_src = [], []
+        for s in range(len(shards)):
+            self._init_src.append(self._adopt_start_tables(s, inits[s], cur, seen))       # (alive until the copy below has run)
+            self._perms.append(self._adopt_order(s, perms[s], cur))
+            self._fill_descriptor(s)
+        self._copy_start_tables()
         self.state = _States(len(shards), self._state_of)
-        self._descs = descs
-        self._job = ctypes.c_void_p()
         mark('job: tables allocated, descriptors filled')
-        nv.check(nv.lib().ure_job_create(descs, len(shards), ctypes.byref(self._job)), 'ure_job_create')
+        self._job = ctypes.c_void_p()
+        nv.check(nv.lib().ure_job_create(self._descs, len(shards), ctypes.byref(self._job)), 'ure_job_create')
         mark('job: ure_job_create')
-        self.ticks = int(nv.lib().ure_job_ticks(self._job))
+        self.ticks, self.done = int(nv.lib().ure_job_ticks(self._job)), 0
         self.shard_steps = [int(nv.lib().ure_job_shard_steps(self._job, s)) for s in range(len(shards))]
-        self.done = 0
+
+    def _allocate_pools(self):
+        """Every float table of every shard from ONE zero-filled allocation (a request of 16 shards made ~130 small allocations
+        and fills here: 8-12 ms of host time beside 16 busy worker threads), the snapshots from another.  The descriptors are
+        filled from ADDRESSES (_addr); the views of the tables are made when somebody asks for them (self.state), which a
+        request does after its launches are queued."""
+        self._regions, at, snap_at = [], 0, 0                        # per shard: (regions in _pool, regions in _snap_pool)
+        for sh in self.shards:
+            pool, snap, at, snap_at = shard_regions(sh.n_user, sh.n_item, sh.n_active, self.d, self.epochs, self.lazy_rows, self.snapshots, at, snap_at)
+            self._regions.append((pool, snap))
+        self._pool = torch.zeros(at, dtype=torch.float32, device=self.device)
+        self._snap_pool = torch.empty(snap_at, dtype=torch.float32, device=self.device) if self.snapshots else None
+
+    def _addr(self, s, name):
+        """Device address of shard s's region `name` (shard_regions)."""
+        pool, snap = self._regions[s]
+        return self._pool.data_ptr() + 4 * pool[name][0] if name in pool else self._snap_pool.data_ptr() + 4 * snap[name][0]
+
+    def _adopt_start_tables(self, s, init, cur, seen):
+        """The start tables (U0, V0) of shard s as contiguous device tensors, safe to read on the stream `cur`."""
+        sh, srcs = self.shards[s], []
+        for t, n_rows in zip(init, (sh.n_user, sh.n_item)):
+            ev = getattr(t, '_ure_event', None)
+            if ev is not None and id(ev) not in seen:               # uploaded on a side stream (rng.shard_draws_async)
+                seen.add(id(ev))
+                cur.wait_event(ev)
+            if ev is not None:
+                t.record_stream(cur)
+            t = torch.as_tensor(t, dtype=torch.float32)
+            assert t.shape == (n_rows, self.k)
+            if t.device != torch.device(self.device) or not t.is_contiguous():
+                t = t.to(self.device, non_blocking=True).contiguous()
+            srcs.append(t)
+        return srcs
+
+    def _adopt_order(self, s, perm, cur):
+        """The epoch order of shard s on the device: int32 permutations [epochs, N], or -- int16 -- the batch tags made of them (rng.epoch_tags)."""
+        from . import rng
+        arrival = rng.Arrival.of(perm)                  # (before a conversion could make another tensor)
+        if arrival is not None:
+            self._arrivals.append(arrival)
+            if arrival.whole:                           # uploaded on a side stream in one piece (rng.epoch_perms_async)
+                arrival.wait(cur, self.epochs)
+        perm = torch.as_tensor(perm)
+        assert perm.shape == (self.epochs, self.shards[s].N), f'perm of shard {s} must be [epochs, N]'
+        return perm.to(device=self.device, dtype=torch.int16 if perm.dtype == torch.int16 else torch.int32).contiguous()
+
+    def _work_units(self, s):
+        """The work of shard s's step kernel: -> (units_ptr, n_units, n_multi, n_split)."""
+        sh = self.shards[s]
+        if self.index:
+            # no work units: the step's items come from the epoch's index.  Rows by weight class (slots per step on average)
+            nnz, st_s = sh._sched_head[:min(sh.n_active, INDEX_HEAVY_MAX), 3], self._steps[s]
+            n_multi = int(np.count_nonzero(nnz >= INDEX_HEAVY_SLOTS * st_s))
+            return sh.ptr('sched'), 0, n_multi, min(n_multi, int(np.count_nonzero(nnz >= INDEX_SPLIT_SLOTS * st_s)))
+        if self.touch:
+            # epochs of several windows (more than 64 steps): a row of up to TOUCH_ROW_PASSES scan passes stays ONE work item -- its
+            # lane group skips the passes without a slot of the step (csrc/mf_touch.h: pass masks) -- instead of one unit per pass
+            long_epochs = max(self._steps) > 64
+            units, n_units, n_multi = sh.units(self.d, touch=True, min_passes=TOUCH_ROW_PASSES if long_epochs else 1,
+                                               unit_passes=TOUCH_UNIT_PASSES if long_epochs else 1)
+            return nv.ptr(units), n_units, n_multi, 0
+        units = sh.units(self.d)
+        return nv.ptr(units), units.shape[0], 0, 0
+
+    def _fill_descriptor(self, s):
+        """struct ure_shard of shard s (include/ultrare_hip.h) from the layout's and the pools' addresses."""
+        sh, D, d, perm = self.shards[s], self._descs[s], self.d, self._perms[s]
+        for name in ('ent_oid', 'ent_r', 'ent_tag', 'ent_src', 'file_tag', 'inv_stage', 'inv_off', 'sched'):
+            setattr(D, name, sh.ptr(name))
+        D.units, D.n_units, D.n_multi, D.n_split = self._work_units(s)
+        D.U[0], D.U[1] = self._addr(s, 'U'), self._addr(s, 'U') + 4 * sh.n_user * d
+        D.V[0], D.V[1] = self._addr(s, 'V'), self._addr(s, 'V') + 4 * sh.n_item * d
+        D.mU, D.mV, D.sse, D.lr = self._addr(s, 'mU'), self._addr(s, 'mV'), self._addr(s, 'sse'), nv.ptr(self.lr)
+        D.perm, D.file_tags = (None, nv.ptr(perm)) if perm.dtype == torch.int16 else (nv.ptr(perm), None)
+        D.N, D.n_user, D.n_item, D.d, D.n_active, D.n_slots = sh.N, sh.n_user, sh.n_item, d, sh.n_active, sh.n_slots
+        D.batch, D.epochs, D.lam, D.mu, D.touch_mode = self.batch, self.epochs, self._lam, self._mu, self.touch_mode
+        if self.snapshots:
+            D.snap_a = self._small[1 + s].data_ptr()
+            if self.snapshots == 'compact':
+                D.snap, D.row_slot = self._addr(s, 'snap'), sh.ptr('_row_slot')
+            else:
+                D.snapU, D.snapV = self._addr(s, 'snapU'), self._addr(s, 'snapV')
+        if self.lazy_rows:
+            D.U0, D.V0, D.lr_host, D.lazy_rows = self._addr(s, 'U0'), self._addr(s, 'V0'), self._lr_host.ctypes.data, 1
+
+    def _copy_start_tables(self):
+        """The start tables into buffer 0 (and the closed form's copy), every shard's in one launch."""
+        src, dst, dst2, rows = zip(*[(t.data_ptr(), self._addr(s, name), self._addr(s, name + '0'), n_rows)
+                                     for s, (sh, (U0, V0)) in enumerate(zip(self.shards, self._init_src))
+                                     for t, name, n_rows in ((U0, 'U', sh.n_user), (V0, 'V', sh.n_item))])
+        ptrs = lambda v: (ctypes.c_void_p * len(v))(*v)
+        nv.check(nv.lib().ure_copy_rows_batch(len(src), ptrs(src), ptrs(dst), ptrs(dst2) if self.lazy_rows else None, (ctypes.c_int64 * len(rows))(*rows),
+                                              self.k, self.d, nv.stream_handle()), 'ure_copy_rows_batch')
+        self._init_src = None             # (allocator: their memory is reused only after the streams they were recorded on have passed this point)
 
     def _state_of(self, s):
-        sh, d, pool = self.shards[s], self.d, self._pool
-        o = self._offs[s]
-        st = {'U': pool[o[0]:o[0] + 2 * sh.n_user * d].view(2, sh.n_user, d), 'V': pool[o[1]:o[1] + 2 * sh.n_item * d].view(2, sh.n_item, d),
-              'mU': pool[o[2]:o[2] + sh.n_user * d].view(sh.n_user, d), 'mV': pool[o[3]:o[3] + sh.n_item * d].view(sh.n_item, d),
-              'perm': self._perms[s], 'sse': pool[o[4]:o[4] + self.epochs * sh.n_user].view(self.epochs, sh.n_user)}
-        if self.lazy_rows:
-            st.update(U0=pool[o[5]:o[5] + sh.n_user * d].view(sh.n_user, d), V0=pool[o[6]:o[6] + sh.n_item * d].view(sh.n_item, d))
+        st = {'perm': self._perms[s]}
+        for regions, mem in zip(self._regions[s], (self._pool, self._snap_pool)):
+            for name, (first, n, shape) in regions.items():
+                if n:                                   # (without lazy_rows a job keeps no U0, V0)
+                    st[name] = mem[first:first + n].view(shape)
         if self.snapshots:
-            at, sp = self._snap_offs[s], self._snap_pool
-            st.update(snap_a=self._small[1 + s])
-            if self.snapshots == 'compact':
-                st.update(snap=sp[at:at + self.epochs * sh.n_active * d].view(self.epochs, sh.n_active, d))
-            else:
-                nU = self.epochs * sh.n_user * d
-                st.update(snapU=sp[at:at + nU].view(self.epochs, sh.n_user, d),
-                          snapV=sp[at + nU:at + nU + self.epochs * sh.n_item * d].view(self.epochs, sh.n_item, d))
+            st['snap_a'] = self._small[1 + s]
         return st
 
     @property
@@ -711,10 +731,8 @@ class TrainJob:
 
     def tables(self, s):
         """Current (U, V) of shard s as device views [rows, k]."""
-        self.materialize()
-        cur = min(self.done, self.shard_steps[s]) & 1
-        st = self.state[s]
-        return st['U'][cur, :, :self.k], st['V'][cur, :, :self.k]
+        U, V = self.padded_tables(s)
+        return U[:, :self.k], V[:, :self.k]
 
     def padded_tables(self, s):
         self.materialize()
@@ -754,8 +772,7 @@ class TrainJob:
         n = len(which)
         out = torch.empty(n, self.epochs, dtype=torch.float64, device=self.device) if out is None else out
         assert out.shape == (n, self.epochs) and out.dtype == torch.float64 and out.is_contiguous()
-        base = self._pool.data_ptr()
-        ptrs = (ctypes.c_void_p * n)(*[base + 4 * self._offs[s][4] for s in which])
+        ptrs = (ctypes.c_void_p * n)(*[self._addr(s, 'sse') for s in which])
         rows = (ctypes.c_int64 * n)(*[self.shards[s].n_user for s in which])
         nv.check(nv.lib().ure_epoch_sse_batch(n, ptrs, rows, self.epochs, out.data_ptr(), nv.stream_handle(stream)), 'ure_epoch_sse_batch')
         return out
@@ -834,15 +851,19 @@ class ScoreCache:
         return FixedBase(n, out)
 
 
+def _ptr_arrays(tables, d):
+    """-> (U pointers, V pointers) of a list of padded (U, V): contiguous device tables of row width d."""
+    for U, V in tables:
+        assert U.is_contiguous() and V.is_contiguous() and U.shape[1] == d and V.shape[1] == d
+    n = max(len(tables), 1)
+    return (ctypes.c_void_p * n)(*[U.data_ptr() for U, _ in tables]), (ctypes.c_void_p * n)(*[V.data_ptr() for _, V in tables])
+
+
 def _fixed_args(fixed, d, own_base):
     """-> (U pointers, V pointers, n_fixed, base pointer) of a series call for `fixed` = a list of padded (U, V) or a FixedBase."""
     if isinstance(fixed, FixedBase):
         return None, None, fixed.n, (nv.ptr(fixed.base) if fixed.n else nv.ptr(own_base))
-    for U, V in fixed:
-        assert U.is_contiguous() and V.is_contiguous() and U.shape[1] == d and V.shape[1] == d
-    Up = (ctypes.c_void_p * max(len(fixed), 1))(*[U.data_ptr() for U, _ in fixed])
-    Vp = (ctypes.c_void_p * max(len(fixed), 1))(*[V.data_ptr() for _, V in fixed])
-    return Up, Vp, len(fixed), nv.ptr(own_base)
+    return (*_ptr_arrays(fixed, d), len(fixed), nv.ptr(own_base))
 
 
 class EvalSet:
@@ -952,10 +973,7 @@ class EvalSet:
             score_weighted(models, d, self.uid, self.iid, self.rating, combiner.link_code, W, gou, pred=self.pred, sse=self.sse, stream=stream)
         for c0 in (range(0, S, nv.MAX_MODELS_PER_CALL) if combiner is None else ()):
             chunk = models[c0:c0 + nv.MAX_MODELS_PER_CALL]
-            for U, V in chunk:
-                assert U.is_contiguous() and V.is_contiguous() and U.shape[1] == d and V.shape[1] == d
-            Up = (ctypes.c_void_p * len(chunk))(*[U.data_ptr() for U, _ in chunk])
-            Vp = (ctypes.c_void_p * len(chunk))(*[V.data_ptr() for _, V in chunk])
+            Up, Vp = _ptr_arrays(chunk, d)
             nv.check(L.ure_score(Up, Vp, len(chunk), S, int(c0 == 0), int(c0 + len(chunk) >= S),
                                  nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating), self.n, d,
                                  nv.ptr(self.pred), nv.ptr(self.sse), st), 'ure_score')
@@ -990,75 +1008,58 @@ class EvalSet:
     def score_vector(self, U, V, d, stream=None):
         """What the model (U, V) (padded, device) adds to an ensemble's running sum on this set's pairs: 0 + <u, v> per pair, float32
         [n] in the set's own order (ure_score with one model, first = 1, last = 0)."""
-        assert U.is_contiguous() and V.is_contiguous() and U.shape[1] == d and V.shape[1] == d
+        Up, Vp = _ptr_arrays([(U, V)], d)
         out = torch.empty(max(self.n, 1), dtype=torch.float32, device=self.device)
         if self.n:
-            Up, Vp = (ctypes.c_void_p * 1)(U.data_ptr()), (ctypes.c_void_p * 1)(V.data_ptr())
             nv.check(nv.lib().ure_score(Up, Vp, 1, 1, 1, 0, nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating), self.n, d, nv.ptr(out), None,
                                         nv.stream_handle(stream)), 'ure_score')
+        return out
+
+    def _series(self, E, fixed, d, out, stream, call, subset=None, lane=0, nan_if_empty=True):
+        """The frame the three series routes share: out [E, 3] checked, the scratch of `lane`, the fixed models, then per chunk of
+        members call(e0, m, head, tail) -- the route's native call for members e0 .. e0 + m, between the arguments every route starts
+        (the fixed models) and ends with (the set, the scratch, out[e0], the stream) -- and the subset's numbers."""
+        assert out.shape == (E, 3) and out.dtype == torch.float64 and out.is_contiguous()
+        if nan_if_empty and self.n == 0:
+            return out.fill_(float('nan'))
+        st = nv.stream_handle(stream)
+        b, per_call = self._series_buffers(E, lane)
+        Up, Vp, n_fixed, base_ptr = _fixed_args(fixed, d, b['base'])
+        for e0 in range(0, E, per_call):
+            m = min(per_call, E - e0)
+            call(e0, m, (Up, Vp, n_fixed),
+                 (nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating), self.n, d, nv.ptr(self.off), self.n_users, nv.ptr(self.log2), base_ptr,
+                  nv.ptr(b['pred']), nv.ptr(b['sse']), nv.ptr(b['hits']), nv.ptr(b['ndcg']), nv.ptr(out[e0]), nv.ptr(self.top_rating),
+                  self.n_wide, self.n_half, st))
+            if subset is not None:
+                self._subset_after(subset, m, e0, st, b)
         return out
 
     def evaluate_series(self, fixed, U_series, V_series, d, out, stream=None, subset=None, lane=0):
         """scratch.py:83-97 for every epoch of a shard in four launches (ure_eval_series): member e of
         the series is the ensemble `fixed` + [(U_series[e], V_series[e])]; out[e] (device float64
         [E, 3]) receives its (rmse, ndcg, hr).  Nothing synchronises."""
-        E = int(U_series.shape[0])
-        assert out.shape == (E, 3) and out.dtype == torch.float64 and out.is_contiguous()
         assert U_series.is_contiguous() and V_series.is_contiguous() and U_series.shape[2] == d and V_series.shape[2] == d
-        if self.n == 0:
-            return out.fill_(float('nan'))
-        L, st = nv.lib(), nv.stream_handle(stream)
-        b, per_call = self._series_buffers(E, lane)
-        Up, Vp, n_fixed, base_ptr = _fixed_args(fixed, d, b['base'])
-        for e0 in range(0, E, per_call):
-            m = min(per_call, E - e0)
-            nv.check(L.ure_eval_series(Up, Vp, n_fixed, nv.ptr(U_series[e0]), nv.ptr(V_series[e0]), U_series.stride(0),
-                                       V_series.stride(0), m, nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating), self.n, d,
-                                       nv.ptr(self.off), self.n_users, nv.ptr(self.log2), base_ptr, nv.ptr(b['pred']),
-                                       nv.ptr(b['sse']), nv.ptr(b['hits']), nv.ptr(b['ndcg']), nv.ptr(out[e0]), nv.ptr(self.top_rating),
-                                       self.n_wide, self.n_half, st),
-                     'ure_eval_series')
-            if subset is not None:
-                self._subset_after(subset, m, e0, st, b)
-        return out
+        call = lambda e0, m, head, tail: nv.check(nv.lib().ure_eval_series(
+            *head, nv.ptr(U_series[e0]), nv.ptr(V_series[e0]), U_series.stride(0), V_series.stride(0), m, *tail), 'ure_eval_series')
+        return self._series(int(U_series.shape[0]), fixed, d, out, stream, call, subset, lane)
 
     def evaluate_series_compact(self, fixed, snap, row_slot, U0, V0, snap_a, n_user_rows, d, out, stream=None, subset=None, lane=0):
         """evaluate_series on COMPACT snapshots (ure_eval_series_compact): snap [E, n_active, d] holds the rows with
         interactions in the shard, row_slot maps a row id to its place in it (-1: the row is snap_a[e] * (U0 | V0)[row])."""
         E = int(snap.shape[0])
-        assert out.shape == (E, 3) and out.dtype == torch.float64 and out.is_contiguous()
         assert snap.is_contiguous() and snap.shape[2] == d and U0.is_contiguous() and V0.is_contiguous() and U0.shape[1] == d and V0.shape[1] == d
         assert row_slot.dtype == torch.int32 and row_slot.numel() == U0.shape[0] + V0.shape[0] and snap_a.numel() == E
-        if self.n == 0:
-            return out.fill_(float('nan'))
-        L, st = nv.lib(), nv.stream_handle(stream)
-        b, per_call = self._series_buffers(E, lane)
-        Up, Vp, n_fixed, base_ptr = _fixed_args(fixed, d, b['base'])
-        for e0 in range(0, E, per_call):
-            m = min(per_call, E - e0)
-            nv.check(L.ure_eval_series_compact(Up, Vp, n_fixed, nv.ptr(snap[e0]), snap.stride(0), nv.ptr(row_slot), nv.ptr(U0), nv.ptr(V0),
-                                               nv.ptr(snap_a[e0:]), int(n_user_rows), m, nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating),
-                                               self.n, d, nv.ptr(self.off), self.n_users, nv.ptr(self.log2), base_ptr, nv.ptr(b['pred']),
-                                               nv.ptr(b['sse']), nv.ptr(b['hits']), nv.ptr(b['ndcg']), nv.ptr(out[e0]), nv.ptr(self.top_rating),
-                                               self.n_wide, self.n_half, st), 'ure_eval_series_compact')
-            if subset is not None:
-                self._subset_after(subset, m, e0, st, b)
-        return out
+        call = lambda e0, m, head, tail: nv.check(nv.lib().ure_eval_series_compact(
+            *head, nv.ptr(snap[e0]), snap.stride(0), nv.ptr(row_slot), nv.ptr(U0), nv.ptr(V0), nv.ptr(snap_a[e0:]), int(n_user_rows), m, *tail),
+            'ure_eval_series_compact')
+        return self._series(E, fixed, d, out, stream, call, subset, lane)
 
     def evaluate_series_own(self, fixed, own, d, out, stream=None):
         """The second half of a series whose own scores own [E, n] exist (ure_eval_series_own)."""
-        E = int(own.shape[0])
-        assert out.shape == (E, 3) and out.dtype == torch.float64 and out.is_contiguous() and own.is_contiguous() and own.shape[1] == self.n
-        L, st = nv.lib(), nv.stream_handle(stream)
-        b, per_call = self._series_buffers(E)
-        Up, Vp, n_fixed, base_ptr = _fixed_args(fixed, d, b['base'])
-        for e0 in range(0, E, per_call):
-            m = min(per_call, E - e0)
-            nv.check(L.ure_eval_series_own(Up, Vp, n_fixed, nv.ptr(own[e0]), m, nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating), self.n, d,
-                                           nv.ptr(self.off), self.n_users, nv.ptr(self.log2), base_ptr, nv.ptr(b['pred']), nv.ptr(b['sse']),
-                                           nv.ptr(b['hits']), nv.ptr(b['ndcg']), nv.ptr(out[e0]), nv.ptr(self.top_rating), self.n_wide, self.n_half, st),
-                     'ure_eval_series_own')
-        return out
+        assert own.is_contiguous() and own.shape[1] == self.n
+        call = lambda e0, m, head, tail: nv.check(nv.lib().ure_eval_series_own(*head, nv.ptr(own[e0]), m, *tail), 'ure_eval_series_own')
+        return self._series(int(own.shape[0]), fixed, d, out, stream, call, nan_if_empty=False)
 
     def predictions(self):
         """Ensemble predictions of the last evaluate() in the caller's original row order."""
@@ -1344,9 +1345,8 @@ def _table_ptrs(tables, d, what):
     for U, V in tables:
         if not (torch.is_tensor(U) and U.is_cuda and V.is_cuda):
             raise nv.NativeError(f'{what} runs on the HIP device only (no CPU fallback)')
-        assert U.is_contiguous() and V.is_contiguous() and U.dtype == torch.float32 and V.dtype == torch.float32
-        assert U.shape[1] == d and V.shape[1] == d and U.shape[0] == tables[0][0].shape[0] and V.shape[0] == tables[0][1].shape[0]
-    return (ctypes.c_void_p * S)(*[U.data_ptr() for U, _ in tables]), (ctypes.c_void_p * S)(*[V.data_ptr() for _, V in tables]), S
+        assert U.dtype == torch.float32 and V.dtype == torch.float32 and U.shape[0] == tables[0][0].shape[0] and V.shape[0] == tables[0][1].shape[0]
+    return (*_ptr_arrays(tables, d), S)
 
 
 def _link_code(link):
