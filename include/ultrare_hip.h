@@ -654,6 +654,42 @@ int ure_csr_centroids(const int64_t *col_off, const int32_t *row, const float *v
                       float *Ct, int ldc, int32_t *counts, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Attribute unlearning losses (csrc/mmd.hip; new symbols, the ABI number is unchanged): the reference's rbk / mmd_loss /
+ * buildLap (utils.py:223-279) on selected rows of a table, the m x m kernel matrix streamed and never written.  The
+ * arithmetic is stated in numpy in ultrare_amd/attr_unlearn.py.
+ * ------------------------------------------------------------------------- */
+/* X (device) float32 with row stride ld >= d, 1 <= d <= 128; rows (device) int32 [n1 + n2], distinct and in range (not
+ * checked here): the first n1 are the source group S, the other n2 the target group T, n1, n2 >= 1.  Rows that are not
+ * selected and the columns d .. ld - 1 are never read.  2 <= n1 + n2 <= 2^31 - 65.  scratch (device) holds ure_mmd_scratch(n1 + n2, d) bytes, at
+ * most 16 (n1 + n2) d float64 plus under 1 MiB and never quadratic in m; -1 for a shape the calls refuse.  ure_mmd_splits:
+ * the column splits ure_mmd_loss_grad runs at that shape (a function of (m, d) alone; -1 likewise).  No floating-point
+ * atomics and a fixed summation order: equal arguments give equal bytes on any stream.  Nothing synchronises. */
+int64_t ure_mmd_scratch(int64_t m, int32_t d);
+int32_t ure_mmd_splits(int64_t m, int32_t d);
+/* *bandwidth (device float64) = sum_ij |x_i - x_j|^2 / (m^2 - m) over the selected rows by its closed form
+ * (2 m sum |t_i|^2 - 2 |sum t_i|^2) / (m^2 - m), t_i = x_i - s in float64 (s = the first selected row). */
+int ure_mmd_bandwidth(const float *X, int64_t ld, int32_t d, const int32_t *rows, int64_t n1, int64_t n2, double *bandwidth, void *scratch,
+                      int64_t scratch_bytes, void *stream);
+/* With bw = *bandwidth (device float64, read by the kernel), bw_q = bw / kernel_mul^(kernel_num / 2) * kernel_mul^q,
+ * K_ij = sum_q expf(-L_ij / bw_q) and L_ij = |x_i - x_j|^2 (difference form, float32): sums (device float64 [4]) = the sums
+ * of K over the blocks S x S, T x T, S x T, T x S, the diagonal included; the MMD loss is
+ * sums[0] / n1^2 + sums[1] / n2^2 - (sums[2] + sums[3]) / (n1 n2).  grad (device float32 [m x d], optional; NULL skips the
+ * gradient pass and leaves sums unchanged): its gradient with respect to every selected row, no gradient through bw.  Float32
+ * partial sums are at most 64 terms long before they enter float64 accumulators.  kernel_mul > 0, 1 <= kernel_num <= 16;
+ * a bandwidth that is not positive and finite gives NaN. */
+int ure_mmd_loss_grad(const float *X, int64_t ld, int32_t d, const int32_t *rows, int64_t n1, int64_t n2, double kernel_mul, int32_t kernel_num,
+                      const double *bandwidth, double *sums, float *grad, void *scratch, int64_t scratch_bytes, void *stream);
+/* *value (device float64) = sum over i in S, j in T of |x_i - x_j|^2 = trace(U^T Lap U) of the complete bipartite graph
+ * S - T, by its closed form from float64 column sums; grad (device float32 [m x d], optional) = 2 (n2 x_i - sum_T x_j)
+ * for i in S and the mirror image for T. */
+int ure_u2u_loss_grad(const float *X, int64_t ld, int32_t d, const int32_t *rows, int64_t n1, int64_t n2, double *value, float *grad, void *scratch,
+                      int64_t scratch_bytes, void *stream);
+/* K [m x m] float32 (device) itself for 1 <= m <= 8192 selected rows, from the same tile arithmetic: symmetric bit for bit,
+ * diagonal kernel_num. */
+int ure_mmd_matrix(const float *X, int64_t ld, int32_t d, const int32_t *rows, int64_t m, double kernel_mul, int32_t kernel_num,
+                   const double *bandwidth, float *K, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Comparison clusterers (utils.py:354-418: k-means / balanced k-means on the user embedding;
  * never called on the reference's CLI path, kept for the OT-vs-k-means comparison of its notebook)
  * ------------------------------------------------------------------------- */

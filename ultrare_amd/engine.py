@@ -1620,3 +1620,124 @@ def csr_centroids(S, label, k, ldc=None, stream=None):
                                         nv.ptr(counts), nv.stream_handle(stream)), 'ure_csr_centroids')
     _csr_held_for(stream, lab_d, Ct, counts)
     return Ct, counts
+
+
+# ---------------------------------------------------------------------------
+# Attribute unlearning losses (csrc/mmd.hip; the contract and the argument checks are attr_unlearn.py)
+# ---------------------------------------------------------------------------
+class GroupRows:
+    """The selected rows of two attribute groups on the device: rows int32 [n1 + n2], the first n1 the source group.
+    Checked once on the host (attr_unlearn.check_groups) so that the calls of a fine-tune loop read nothing back."""
+
+    def __init__(self, id1, id2, n_rows, device=None):
+        from .attr_unlearn import check_groups
+        self.host, self.n1, self.n2 = check_groups(id1, id2, n_rows)
+        self.n_rows = int(n_rows)
+        self.rows = to_device_async(self.host, device or _device())
+
+    @classmethod
+    def leading(cls, n1, n2, device):
+        """Rows 0 .. n1 + n2 - 1 of a table that holds the source rows and then the target rows."""
+        g = cls.__new__(cls)
+        if n1 < 1 or n2 < 1:
+            raise ValueError(f'both groups need at least one row, not {n1} and {n2}')
+        g.host, g.n1, g.n2, g.n_rows = None, int(n1), int(n2), int(n1 + n2)
+        g.rows = torch.arange(n1 + n2, dtype=torch.int32, device=device)
+        return g
+
+    @property
+    def m(self):
+        return self.n1 + self.n2
+
+
+def _attr_table(X, groups, what):
+    """(d, ld) of a device table the attribute kernels may read in place."""
+    from .attr_unlearn import check_width
+    if not (torch.is_tensor(X) and X.is_cuda):
+        raise nv.NativeError(f'{what} runs on the HIP device only (no CPU fallback)')
+    if not (X.dtype == torch.float32 and X.dim() == 2 and X.stride(1) == 1 and X.shape[0] >= groups.n_rows and X.stride(0) >= X.shape[1]):
+        raise ValueError(f'{what}: X must be a float32 [>= {groups.n_rows}, d] device tensor with unit column stride, not {tuple(X.shape)} {X.dtype}')
+    if X.device != groups.rows.device:
+        raise ValueError(f'X is on {X.device} but the rows were uploaded to {groups.rows.device}')
+    return check_width(X.shape[1], X.stride(0)), int(X.stride(0))
+
+
+def _attr_scratch(m, d, dev, stream):
+    nbytes = int(nv.lib().ure_mmd_scratch(m, d))
+    if nbytes < 0:
+        raise ValueError(f'ure_mmd_scratch refused m = {m}, d = {d}')
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _csr_held_for(stream, scratch)
+    return scratch, nbytes
+
+
+def mmd_bandwidth(X, groups, fix_sigma=None, check=False, stream=None):
+    """The bandwidth of the selected rows as a 0-d float64 device tensor (ure_mmd_bandwidth), or fix_sigma put there.
+    check: read it back and raise ValueError when it is not positive and finite (synchronises)."""
+    d, ld = _attr_table(X, groups, 'mmd_bandwidth')
+    if fix_sigma is not None:
+        bw = torch.full((), float(fix_sigma), dtype=torch.float64, device=X.device)
+    else:
+        bw = torch.empty((), dtype=torch.float64, device=X.device)
+        scratch, nbytes = _attr_scratch(groups.m, d, X.device, stream)
+        nv.check(nv.lib().ure_mmd_bandwidth(X.data_ptr(), ld, d, nv.ptr(groups.rows), groups.n1, groups.n2, bw.data_ptr(), nv.ptr(scratch), nbytes,
+                                            nv.stream_handle(stream)), 'ure_mmd_bandwidth')
+    _csr_held_for(stream, bw)
+    if check:
+        from .attr_unlearn import check_bandwidth
+        if stream is not None:
+            stream.synchronize()
+        check_bandwidth(float(bw.cpu()))
+    return bw
+
+
+def mmd_loss_grad(X, groups, bandwidth, kernel_mul=2.0, kernel_num=5, want_grad=True, stream=None):
+    """ure_mmd_loss_grad on the selected rows of the device table X, read in place: (sums float64 [4] = the sums of the kernel
+    matrix over S x S, T x T, S x T, T x S; grad float32 [m, d] or None), on the device.  bandwidth: the 0-d float64 device
+    tensor of mmd_bandwidth.  Nothing synchronises."""
+    from .attr_unlearn import check_mmd_args
+    kernel_mul, kernel_num, _ = check_mmd_args(kernel_mul, kernel_num)
+    d, ld = _attr_table(X, groups, 'mmd_loss_grad')
+    if not (torch.is_tensor(bandwidth) and bandwidth.is_cuda and bandwidth.dtype == torch.float64 and bandwidth.numel() == 1):
+        raise ValueError('bandwidth must be a float64 device tensor of one value (mmd_bandwidth)')
+    dev = X.device
+    scratch, nbytes = _attr_scratch(groups.m, d, dev, stream)
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(groups.m, d, dtype=torch.float32, device=dev) if want_grad else None
+    nv.check(nv.lib().ure_mmd_loss_grad(X.data_ptr(), ld, d, nv.ptr(groups.rows), groups.n1, groups.n2, kernel_mul, kernel_num, bandwidth.data_ptr(),
+                                        nv.ptr(sums), nv.ptr(grad), nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_mmd_loss_grad')
+    _csr_held_for(stream, sums, *([grad] if want_grad else []))
+    return sums, grad
+
+
+def mmd_loss_of(sums, groups):
+    """The MMD loss (0-d float64 device tensor) from the four block sums."""
+    n1, n2 = float(groups.n1), float(groups.n2)
+    return sums[0] / (n1 * n1) + sums[1] / (n2 * n2) - sums[2] / (n1 * n2) - sums[3] / (n1 * n2)
+
+
+def u2u_loss_grad(X, groups, want_grad=True, stream=None):
+    """ure_u2u_loss_grad: (value 0-d float64, grad float32 [m, d] or None) on the device.  Nothing synchronises."""
+    d, ld = _attr_table(X, groups, 'u2u_loss_grad')
+    dev = X.device
+    scratch, nbytes = _attr_scratch(groups.m, d, dev, stream)
+    value = torch.empty((), dtype=torch.float64, device=dev)
+    grad = torch.empty(groups.m, d, dtype=torch.float32, device=dev) if want_grad else None
+    nv.check(nv.lib().ure_u2u_loss_grad(X.data_ptr(), ld, d, nv.ptr(groups.rows), groups.n1, groups.n2, value.data_ptr(), nv.ptr(grad),
+                                        nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_u2u_loss_grad')
+    _csr_held_for(stream, value, *([grad] if want_grad else []))
+    return value, grad
+
+
+def mmd_matrix(X, groups, bandwidth, kernel_mul=2.0, kernel_num=5, stream=None):
+    """ure_mmd_matrix: the kernel matrix K [m, m] float32 of the selected rows on the device, m <= 8192."""
+    from .attr_unlearn import RBK_MAX_M, check_mmd_args
+    kernel_mul, kernel_num, _ = check_mmd_args(kernel_mul, kernel_num)
+    d, ld = _attr_table(X, groups, 'mmd_matrix')
+    if groups.m > RBK_MAX_M:
+        raise ValueError(f'the kernel matrix of {groups.m} rows is not formed (limit {RBK_MAX_M}): mmd_loss streams it')
+    K = torch.empty(groups.m, groups.m, dtype=torch.float32, device=X.device)
+    nv.check(nv.lib().ure_mmd_matrix(X.data_ptr(), ld, d, nv.ptr(groups.rows), groups.m, kernel_mul, kernel_num, bandwidth.data_ptr(), nv.ptr(K),
+                                     nv.stream_handle(stream)), 'ure_mmd_matrix')
+    _csr_held_for(stream, K)
+    return K

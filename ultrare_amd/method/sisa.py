@@ -596,6 +596,39 @@ class Sisa(Scratch):
         self.forget_rows()
         self.combiner = None
 
+    # ------------------------------------------------------------------ attribute unlearning
+    def attribute_unlearn(self, id1, id2, **kw):
+        """Make the user rows of the attribute groups id1 and id2 indistinguishable, shard by shard, without retraining
+        (utils.attribute_unlearn; its keywords pass through).  Shard s fine-tunes the rows of its OWN users only --
+        group_index[s] & id1 against group_index[s] & id2, in the order id1 / id2 list them -- in the merged user table all
+        models share, so a row is moved by the shard that trained it and by no other; users no shard lists are not touched.
+        A shard where either side is empty is skipped.  Returns one entry per shard: utils.attribute_unlearn's log plus
+        'rows' (n1, n2), or {'skipped': reason, 'rows': (n1, n2)}.  A fitted combiner is dropped (its weights were fitted on
+        the rows this call moves); test, recommend, rank_eval and unlearn read the table itself and see the new rows.
+        ValueError before any device work for groups that are empty, overlap, repeat a user or leave the table."""
+        from ..attr_unlearn import check_groups
+        if not self.model_list:
+            raise ValueError('attribute_unlearn needs trained models: call learn first')
+        rows, n1, _ = check_groups(id1, id2, self.n_user)
+        a, b = rows[:n1].astype(np.int64), rows[n1:].astype(np.int64)
+        utils.attribute_unlearn_check(**kw)
+        self._merged_table()
+        logs = []
+        for s in range(self.n_group):
+            own = np.zeros(self.n_user, dtype=bool)
+            ids = np.asarray(self.group_index[s], dtype=np.int64)
+            own[ids[(ids >= 0) & (ids < self.n_user)]] = True
+            sa, sb = a[own[a]], b[own[b]]
+            if len(sa) == 0 or len(sb) == 0:
+                logs.append({'skipped': f'shard {s} holds {len(sa)} users of id1 and {len(sb)} of id2: both sides need one', 'rows': (len(sa), len(sb))})
+                continue
+            log = utils.attribute_unlearn(self.model_list[s], sa, sb, **kw)
+            log['rows'] = (len(sa), len(sb))
+            logs.append(log)
+        self.forget_rows()
+        self.combiner = None
+        return logs
+
     # ------------------------------------------------------------------ unlearn
     def recommend(self, users, top_k=10, exclude=None):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers

@@ -16,6 +16,9 @@ the reference), backed by the HIP engine.
   findNeighbor utils.py:422-455  the k-nearest-neighbour user graph
   lpa          utils.py:458-519  (balanced) label propagation, a comparison clusterer
   kmedoids     utils.py:546-611  (balanced) k-medoids, a comparison clusterer
+  rbk / mmd_loss  utils.py:223-267  the multi-bandwidth Gaussian kernel matrix and the MMD loss of two groups (streamed)
+  attribute_unlearn (new)        post-training attribute unlearning: a short fine-tune of the groups' user rows on the
+                                 MMD ('d2d') or Laplacian ('u2u', utils.py:75-78 with buildLap) loss
   saveObject / loadObject / timefn  utils.py:319-326, 616-626
 
 Training does not go through a `baseTrain(dataloader, model, loss_fn, opt, ...)` loop:
@@ -809,3 +812,94 @@ def lpa(n_group, n_user, dist_arr, balanced=False, n_init=5, max_iter=10, metric
             tmp_inertia = inertia
             fin_label = label
     return fin_label
+
+
+# ---------------------------------------------------------------------------
+# Attribute unlearning (utils.py:223-279; csrc/mmd.hip, the contract is attr_unlearn.py)
+# ---------------------------------------------------------------------------
+def _two_groups(source, target):
+    """(X [n1 + n2, d] float32 on the device, GroupRows) of two device tensors [n1, d], [n2, d]."""
+    for t in (source, target):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise nv.NativeError('the MMD kernels run on the HIP device only (no CPU fallback)')
+    if source.dim() != 2 or target.dim() != 2 or source.shape[1] != target.shape[1]:
+        raise ValueError(f'source and target must be [n1, d] and [n2, d], not {tuple(source.shape)} and {tuple(target.shape)}')
+    groups = engine.GroupRows.leading(source.shape[0], target.shape[0], source.device)
+    return torch.cat([source.detach().float(), target.detach().float()], dim=0), groups
+
+
+def rbk(source, target, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
+    """utils.py:223-256: the kernel matrix sum_q exp(-|x_i - x_j|^2 / bw_q) [m, m] float32 of the rows of source and target
+    (device tensors), built on the device tile by tile.  m = n1 + n2 above 8,192 is refused: mmd_loss needs no matrix."""
+    from ..attr_unlearn import RBK_MAX_M, check_mmd_args
+    kernel_mul, kernel_num, fix_sigma = check_mmd_args(kernel_mul, kernel_num, fix_sigma)
+    m = int(source.shape[0]) + int(target.shape[0])
+    if m > RBK_MAX_M:
+        raise ValueError(f'rbk would write a {m} x {m} matrix (limit {RBK_MAX_M} rows): use mmd_loss, which streams it')
+    X, groups = _two_groups(source, target)
+    bw = engine.mmd_bandwidth(X, groups, fix_sigma, check=True)
+    return engine.mmd_matrix(X, groups, bw, kernel_mul, kernel_num)
+
+
+def mmd_loss(source, target, kernel_mul=2.0, kernel_num=5, fix_sigma=None, want_grad=False):
+    """utils.py:258-267: the MMD loss of two groups of rows (device tensors [n1, d], [n2, d]) as a 0-d float64 device tensor;
+    the m x m kernel matrix is streamed, never formed.  want_grad: (loss, grad_source [n1, d], grad_target [n2, d]) float32,
+    no gradient through the bandwidth (the reference's .data).  ValueError when the bandwidth is not positive and finite."""
+    from ..attr_unlearn import check_mmd_args
+    kernel_mul, kernel_num, fix_sigma = check_mmd_args(kernel_mul, kernel_num, fix_sigma)
+    X, groups = _two_groups(source, target)
+    bw = engine.mmd_bandwidth(X, groups, fix_sigma, check=True)
+    sums, grad = engine.mmd_loss_grad(X, groups, bw, kernel_mul, kernel_num, want_grad=want_grad)
+    loss = engine.mmd_loss_of(sums, groups)
+    return (loss, grad[:groups.n1], grad[groups.n1:]) if want_grad else loss
+
+
+def attribute_unlearn_check(var='d2d', eta=1.0, alpha=0.0, lr=0.1, steps=10, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
+    """The settings of attribute_unlearn, checked on the host (ValueError) -> the eight values."""
+    from ..attr_unlearn import check_loop_args, check_mmd_args, check_var
+    return (check_var(var),) + check_loop_args(eta, alpha, lr, steps) + check_mmd_args(kernel_mul, kernel_num, fix_sigma)
+
+
+def attribute_unlearn(model, id1, id2, var='d2d', eta=1.0, alpha=0.0, lr=0.1, steps=10, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
+    """Post-training attribute unlearning: `steps` plain gradient steps U_i -= lr grad_i J on the rows id1 + id2 of
+    model.user_mat.weight, in place, J(U) = eta dis(U[id1], U[id2]) + alpha sum_i |U_i - U*_i|^2 with U* the table at entry and
+    dis the MMD loss ('d2d', mmd_loss) or the Laplacian value of the complete bipartite graph id1 - id2 ('u2u').  Every other
+    row and the item table keep their bytes.  The bandwidth is recomputed from the current rows every step unless fix_sigma is
+    given.  The pairwise work is csrc/mmd.hip; the update itself is elementwise float64 on the device, rounded once.  The loop
+    reads nothing back: the log -- dict of dis, reg, bandwidth (u2u: NaN), each steps + 1 values, before every step and after
+    the last -- comes to the host in one copy at the end.  ValueError before any device work for groups that are empty,
+    overlap, repeat a row or leave the table, and for var outside {'d2d', 'u2u'}; ValueError as well for a bandwidth that is
+    not positive and finite (at entry: before any change)."""
+    from ..attr_unlearn import check_bandwidth
+    var, eta, alpha, lr, steps, kernel_mul, kernel_num, fix_sigma = attribute_unlearn_check(var, eta, alpha, lr, steps, kernel_mul, kernel_num, fix_sigma)
+    W = model.user_mat.weight
+    groups = engine.GroupRows(id1, id2, W.shape[0], W.device if W.is_cuda else None)
+    U = W.detach()
+    if not U.is_cuda:
+        raise nv.NativeError('model tables are not on the HIP device (call model.to("cuda")): no CPU fallback')
+    if U.dtype != torch.float32 or U.stride(1) != 1:
+        raise ValueError('the user table must be float32 with unit column stride')
+    at = groups.rows.long()
+    start = U.index_select(0, at).double()
+    dis_log, reg_log, bw_log = [], [], []
+    nan = torch.full((), float('nan'), dtype=torch.float64, device=U.device)
+    for t in range(steps + 1):
+        if var == 'd2d':
+            bw = engine.mmd_bandwidth(U, groups, fix_sigma, check=(t == 0 and fix_sigma is None))
+            sums, grad = engine.mmd_loss_grad(U, groups, bw, kernel_mul, kernel_num, want_grad=t < steps)
+            dis = engine.mmd_loss_of(sums, groups)
+        else:
+            bw = nan
+            dis, grad = engine.u2u_loss_grad(U, groups, want_grad=t < steps)
+        cur = U.index_select(0, at).double()
+        delta = cur - start
+        dis_log.append(dis)
+        reg_log.append((delta * delta).sum())
+        bw_log.append(bw)
+        if t < steps:
+            U.index_copy_(0, at, (cur - lr * (eta * grad.double() + (2.0 * alpha) * delta)).float())
+    host = torch.stack(dis_log + reg_log + bw_log).cpu().numpy().reshape(3, steps + 1)
+    if var == 'd2d':
+        for b in host[2]:
+            check_bandwidth(b)
+    return {'dis': host[0].tolist(), 'reg': host[1].tolist(), 'bandwidth': host[2].tolist()}

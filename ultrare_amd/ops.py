@@ -30,6 +30,10 @@ to resident shards -- and stays behind engine.TrainJob.
                                                                           centroids held transposed in Ct [n_item, ldc]
     torch.ops.ultrare.csr_centroids(col_off, row, val, label, k)
                                                         (new)             (Ct [n_item, k], counts [k]) from the CSC
+    torch.ops.ultrare.mmd_grad(X, rows, n1, kernel_mul, kernel_num, fix_sigma)
+                                                        utils.py:223-267  (block sums [4], grad [m, d], bandwidth) of the MMD
+                                                                          loss on the rows `rows` of X, the first n1 the source
+    torch.ops.ultrare.u2u_grad(X, rows, n1)             utils.py:75-78    (value, grad [m, d]) of trace(U^T Lap U), S - T bipartite
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -267,3 +271,34 @@ def csr_centroids(col_off: torch.Tensor, row: torch.Tensor, val: torch.Tensor, l
 @csr_centroids.register_fake
 def _(col_off, row, val, label, k):
     return val.new_empty(col_off.numel() - 1, k), val.new_empty(k, dtype=torch.int32)
+
+
+def _group_rows(X, rows, n1):
+    ids = rows.cpu().numpy()
+    return engine.GroupRows(ids[:n1], ids[n1:], X.shape[0], X.device)
+
+
+@torch.library.custom_op('ultrare::mmd_grad', mutates_args=())
+def mmd_grad(X: torch.Tensor, rows: torch.Tensor, n1: int, kernel_mul: float, kernel_num: int,
+             fix_sigma: Optional[float]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    _dev(X, rows)
+    groups = _group_rows(X, rows, n1)
+    bw = engine.mmd_bandwidth(X, groups, fix_sigma)
+    sums, grad = engine.mmd_loss_grad(X, groups, bw, kernel_mul, kernel_num)
+    return sums, grad, bw
+
+
+@mmd_grad.register_fake
+def _(X, rows, n1, kernel_mul, kernel_num, fix_sigma):
+    return X.new_empty(4, dtype=torch.float64), X.new_empty(rows.numel(), X.shape[1]), X.new_empty((), dtype=torch.float64)
+
+
+@torch.library.custom_op('ultrare::u2u_grad', mutates_args=())
+def u2u_grad(X: torch.Tensor, rows: torch.Tensor, n1: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(X, rows)
+    return engine.u2u_loss_grad(X, _group_rows(X, rows, n1))
+
+
+@u2u_grad.register_fake
+def _(X, rows, n1):
+    return X.new_empty((), dtype=torch.float64), X.new_empty(rows.numel(), X.shape[1])
