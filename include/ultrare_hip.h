@@ -654,6 +654,42 @@ int ure_csr_centroids(const int64_t *col_off, const int32_t *row, const float *v
                       float *Ct, int ldc, int32_t *counts, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * k-means and balanced k-means on the sparse rating matrix (csrc/csr_kmeans.hip; new symbols, the ABI number is unchanged):
+ * the arithmetic of ure_kmeans_cost / ure_kmeans_centroids below restricted to the stored entries of a CSR / CSC, and the
+ * balanced fill of ure_host_kmeans_assign on the device.  Stated in numpy in ultrare_amd/sparse_kmeans.py; the kernels
+ * are held to it bit for bit.
+ * ------------------------------------------------------------------------- */
+/* A device CSR as ure_csr_cost takes it; Ct (device, [n_item][k] fp32): the k centroids TRANSPOSED.  For row i and centroid
+ * c, over the row's stored entries in ascending column, in float32 from +0.0 with one rounded multiply and one rounded add
+ * per term: dot += x Ct[j][c], esq += x x; csq[c] = the same sequential sum of Ct[j][c]^2 over ALL n_item items (one small
+ * launch per call writes the k values into workspace); dist_nk[i][c] = ((-2 dot) + esq) + csq[c], row-major [n][k] as
+ * ure_kmeans_cost.  For finite centroids that is ure_kmeans_cost on the densified matrix bit for bit.  1 <= k <= 256,
+ * 1 <= n, n_item < 2^31; workspace (device): ure_csr_kmeans_cost_scratch(k) = 4 k bytes (-1 for k outside 1 .. 256).  No
+ * floating-point atomics and no sum split across lanes.  Nothing synchronises. */
+int64_t ure_csr_kmeans_cost_scratch(int k);
+int ure_csr_kmeans_cost(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, const float *Ct, int k,
+                        float *dist_nk, void *workspace, int64_t workspace_bytes, void *stream);
+/* The CSC of the same matrix (n_item columns over n users); label (device, int32 [n]) in [0, k); counts[c] (device, int32
+ * [k]) = members of cluster c.  Ct[j][c] (device, [n_item][k]) = the sequential float32 sum from +0.0, in ascending user id,
+ * of x * (float)(1.0 / (double)counts[c]) over the entries of column j whose user has label c, and 0 for a cluster without
+ * members (counts says so; callers raise): ure_kmeans_centroids on the densified matrix bit for bit, transposed.  A label
+ * outside [0, k) joins no cluster.  Nothing synchronises. */
+int ure_csr_kmeans_centroids(const int64_t *col_off, const int32_t *row, const float *val, int64_t n_item, int64_t n, const int32_t *label, int k,
+                             float *Ct, int32_t *counts, void *stream);
+/* ure_host_kmeans_assign's labels from a DEVICE dist_nk [n][k]: capacity <= 0 gives the argmin (first minimum, the first NaN
+ * wins) in one launch; capacity > 0 the balanced fill, as rounds of deferred acceptance on the host's own 64-bit keys (map
+ * of the float bits << 32 | flat index): every user picks the group with its smallest key at or below the group's threshold,
+ * every group with more than `capacity` choosers lowers its threshold to its capacity-th smallest chooser key, until a round
+ * moves no threshold.  The fixed point is the host walk's result for every input (the one stable matching of the keys).  The
+ * host reads a 4-byte flag once per round, so the call SYNCHRONISES the stream and cannot be captured into a graph.
+ * *rounds_out (host, optional) = the rounds run, the last one included; an error, never a wrong answer, after n k + 1 rounds.
+ * 1 <= k <= 256, n k < 2^32, capacity * k >= n.  workspace (device): ure_balanced_fill_scratch(n, k) = 4096 + 8 n bytes (-1
+ * for a shape the call refuses); it may be NULL for capacity <= 0.  label (device, int32 [n]). */
+int64_t ure_balanced_fill_scratch(int64_t n, int32_t k);
+int ure_balanced_fill(const float *dist_nk, int64_t n, int32_t k, int64_t capacity, int32_t *label, int64_t *rounds_out, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Attribute unlearning losses (csrc/mmd.hip; new symbols, the ABI number is unchanged): the reference's rbk / mmd_loss /
  * buildLap (utils.py:223-279) on selected rows of a table, the m x m kernel matrix streamed and never written.  The
  * arithmetic is stated in numpy in ultrare_amd/attr_unlearn.py.

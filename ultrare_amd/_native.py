@@ -144,6 +144,11 @@ _PROTOTYPES = {
     'ure_csr_cost_scratch': (_i64, [ctypes.c_int]),
     'ure_csr_cost': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _i64, _vp]),
     'ure_csr_centroids': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp]),
+    'ure_csr_kmeans_cost_scratch': (_i64, [ctypes.c_int]),
+    'ure_csr_kmeans_cost': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int, _vp, _vp, _i64, _vp]),
+    'ure_csr_kmeans_centroids': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    'ure_balanced_fill_scratch': (_i64, [_i64, _i32]),
+    'ure_balanced_fill': (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, ctypes.POINTER(_i64), _vp, _i64, _vp]),
     'ure_mmd_scratch': (_i64, [_i64, _i32]),
     'ure_mmd_splits': (_i32, [_i64, _i32]),
     'ure_mmd_bandwidth': (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),

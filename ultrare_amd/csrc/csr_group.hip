@@ -15,11 +15,10 @@
 // pair (cost) or one (item, cluster) pair (centroids); a group of G = pow2 >= min(k, 64) lanes shares the row (item), 64 / G
 // of them per wavefront; k > 64 loops over chunks of 64 centroids.  The (index, value) stream of a row is uniform across its
 // group: the group loads G entries with one instruction and hands them round with cross-lane reads.
-#include "ure_internal.h"
+#include "csr_lanes.h"
 
 namespace ure {
 
-constexpr int kCsrMaxK = 256;
 constexpr int kCcLanes = 256;        // lanes of the squared-norm reduction: the contract's, not a tuning knob
 
 // cc[c] = |C_c|^2 in the contract's order: thread l adds Ct[j][c]^2 for j = l, l + 256, ... ascending, then thread 0 adds
@@ -40,13 +39,6 @@ __global__ __launch_bounds__(kCcLanes) void csr_cc_kernel(const float *__restric
         for (int l = 0; l < kCcLanes; ++l) t += part[l];
         cc[c] = t;
     }
-}
-
-// Lane `sub` of a group of G reads entry u of the G entries the group holds (one per lane).
-template <int G, typename T>
-__device__ __forceinline__ T group_read(T v, int u)
-{
-    return G == 1 ? v : __shfl(v, u, G);
 }
 
 template <int G>
@@ -108,21 +100,6 @@ __global__ __launch_bounds__(kBlock) void csr_cost_kernel(const int64_t *__restr
     }
 }
 
-// counts[c] = members of cluster c (integer atomics: exact in any order).  counts is cleared by the caller.
-__global__ __launch_bounds__(kBlock) void csr_counts_kernel(const int32_t *__restrict__ label, int64_t n, int k, int32_t *__restrict__ counts)
-{
-    __shared__ int hist[kCsrMaxK];
-    for (int c = threadIdx.x; c < k; c += kBlock) hist[c] = 0;
-    __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const int l = ldg(label + i);
-        if (l >= 0 && l < k) atomicAdd(&hist[l], 1);
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < k; c += kBlock)
-        if (hist[c]) atomicAdd(&counts[c], hist[c]);
-}
-
 // Owner computes: the group that owns item j walks its column in ascending user id; lane c adds the value when the user's
 // label is c.  The entry and its label are uniform across the group: lane `sub` fetches entry p0 + sub AND that user's
 // label, so the dependent label reads of G entries are in flight together.
@@ -176,13 +153,6 @@ __global__ __launch_bounds__(kBlock) void csr_centroid_kernel(const int64_t *__r
             stg(Ct + (size_t)j * ldc + c, cnt > 0 ? (float)(s / (double)cnt) : 0.f);
         }
     }
-}
-
-inline int group_width(int k)
-{
-    int g = 1;
-    while (g < k && g < kWave) g <<= 1;
-    return g;
 }
 
 }  // namespace ure

@@ -1623,6 +1623,82 @@ def csr_centroids(S, label, k, ldc=None, stream=None):
 
 
 # ---------------------------------------------------------------------------
+# k-means / balanced k-means on the sparse rating matrix (csrc/csr_kmeans.hip; the contract is sparse_kmeans.py)
+# ---------------------------------------------------------------------------
+def csr_kmeans_cost(S, Ct, k, stream=None):
+    """ure_csr_kmeans_cost: dist [n, k] float32 on the device (ure_kmeans_cost's layout) of the rows of S (a CsrSet) against
+    the k centroids held transposed in the device tensor Ct [n_item, k] float32.  Nothing synchronises."""
+    k = _csr_k(k)
+    if not (torch.is_tensor(Ct) and Ct.is_cuda):
+        raise nv.NativeError('csr_kmeans_cost runs on the HIP device only (no CPU fallback)')
+    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and tuple(Ct.shape) == (S.n_item, k)):
+        raise ValueError(f'Ct must be a contiguous float32 [{S.n_item}, {k}] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
+    _csr_same_device(S, Ct, 'Ct')
+    L, dev = nv.lib(), Ct.device
+    nbytes = int(L.ure_csr_kmeans_cost_scratch(k))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(S.n, k, dtype=torch.float32, device=dev)
+    nv.check(L.ure_csr_kmeans_cost(nv.ptr(S.row_off), nv.ptr(S.col), nv.ptr(S.val), S.n, S.n_item, nv.ptr(Ct), k, nv.ptr(dist),
+                                   nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_csr_kmeans_cost')
+    _csr_held_for(stream, scratch, dist)
+    return dist
+
+
+def csr_kmeans_centroids(S, label, k, stream=None):
+    """ure_csr_kmeans_centroids: (Ct [n_item, k] float32, counts [k] int32) on the device, scipy's sparse mean of the users of
+    every cluster of label (n values in [0, k): a host array, or a device int32 tensor whose range is read back once),
+    transposed as csr_kmeans_cost reads them.  A cluster without members gives zeros and counts 0.  Nothing synchronises
+    after the launch."""
+    k = _csr_k(k)
+    if torch.is_tensor(label):
+        if not label.is_cuda:
+            raise nv.NativeError('csr_kmeans_centroids runs on the HIP device only (no CPU fallback)')
+        if label.dtype != torch.int32 or label.shape != (S.n,) or int(label.min()) < 0 or int(label.max()) >= k:
+            raise ValueError(f'label must be n = {S.n} int32 values in [0, {k})')
+        _csr_same_device(S, label, 'label')
+        lab_d = label.contiguous()
+    else:
+        lab = np.ascontiguousarray(label)
+        if lab.shape != (S.n,) or lab.min() < 0 or lab.max() >= k:
+            raise ValueError(f'label must be n = {S.n} values in [0, {k})')
+        lab_d = to_device_async(lab.astype(np.int32), S.device)
+    dev = lab_d.device
+    Ct = torch.empty(S.n_item, k, dtype=torch.float32, device=dev)
+    counts = torch.empty(k, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_csr_kmeans_centroids(nv.ptr(S.col_off), nv.ptr(S.row), nv.ptr(S.cval), S.n_item, S.n, nv.ptr(lab_d), k, nv.ptr(Ct),
+                                               nv.ptr(counts), nv.stream_handle(stream)), 'ure_csr_kmeans_centroids')
+    _csr_held_for(stream, lab_d, Ct, counts)
+    return Ct, counts
+
+
+def balanced_fill(dist_d, capacity, stream=None):
+    """ure_balanced_fill: (label int32 [n] on the device, rounds) from the device matrix dist_d [n, k] float32 --
+    ure_host_kmeans_assign's labels without the copy, the sort and the walk.  capacity <= 0: the argmin (first minimum, the
+    first NaN wins), rounds = 1.  capacity > 0: the balanced fill; the host reads a 4-byte flag once per round, so the call
+    synchronises the stream `rounds` times."""
+    if not (torch.is_tensor(dist_d) and dist_d.is_cuda):
+        raise nv.NativeError('balanced_fill runs on the HIP device only (no CPU fallback)')
+    if not (dist_d.dtype == torch.float32 and dist_d.dim() == 2 and dist_d.is_contiguous() and dist_d.numel() > 0):
+        raise ValueError(f'dist must be a contiguous float32 [n, k] tensor, not {tuple(dist_d.shape)} {dist_d.dtype}')
+    n, k = (int(v) for v in dist_d.shape)
+    k = _csr_k(k)
+    capacity = int(capacity)
+    if n * k >= 2 ** 32:
+        raise ValueError(f'n * k = {n} * {k} must stay below 2^32')
+    if capacity > 0 and min(capacity, n) * k < n:
+        raise ValueError(f'capacity {capacity} x {k} groups < {n} users')
+    L, dev = nv.lib(), dist_d.device
+    nbytes = int(L.ure_balanced_fill_scratch(n, k)) if capacity > 0 else 0
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    label = torch.empty(n, dtype=torch.int32, device=dev)
+    rounds = ctypes.c_int64(0)
+    nv.check(L.ure_balanced_fill(nv.ptr(dist_d), n, k, capacity, nv.ptr(label), ctypes.byref(rounds), nv.ptr(scratch), nbytes,
+                                 nv.stream_handle(stream)), 'ure_balanced_fill')
+    _csr_held_for(stream, scratch, label)
+    return label, int(rounds.value)
+
+
+# ---------------------------------------------------------------------------
 # Attribute unlearning losses (csrc/mmd.hip; the contract and the argument checks are attr_unlearn.py)
 # ---------------------------------------------------------------------------
 class GroupRows:

@@ -51,6 +51,10 @@ class Group(object):
                 # (csrc/csr_group.hip) and n_user x n_item is never formed; bad input is refused before any device work
                 from .sparse_group import check_cluster_args
                 embedding = check_cluster_args(self.rating, n_group)
+            elif cluster_var in ('kmeans', 'bkmeans') and self.n_item > DENSE_MAX_ITEMS:
+                # likewise: kmeans runs its cost, fill and centroid update on the sparse matrix (csrc/csr_kmeans.hip)
+                from .sparse_kmeans import check_kmeans_args
+                embedding = check_kmeans_args(self.rating, n_group)
             else:
                 embedding = np.asarray(self.rating.todense(), dtype=np.float32)
         elif trans_var == 'emb':
@@ -62,7 +66,7 @@ class Group(object):
         elif cluster_var == 'sinkhorn':
             _, label = ot_cluster(embedding, n_group, solver='sinkhorn', reg=reg)
         elif cluster_var in ('kmeans', 'bkmeans'):
-            label = kmeans(n_group, len(embedding), embedding, balanced=cluster_var == 'bkmeans')
+            label = kmeans(n_group, self.n_user if isinstance(embedding, tuple) else len(embedding), embedding, balanced=cluster_var == 'bkmeans')
         elif cluster_var in ('kmedoids', 'bkmedoids'):
             X = _dense_f32(embedding)
             label = kmedoids(n_group, len(X), X, balanced=cluster_var == 'bkmedoids', metric='euclidean')

@@ -13,7 +13,9 @@ Same flags, defaults and assertions; additions are optional:
                  set, URE_EVAL_SUBSET=0, snapshots beyond URE_SNAPSHOT_LIMIT_GB); NDCG and HR are the same bits on both routes
   --dataset toy  the small rating set shipped with the reference (data/toy)
   --group-type   'emb-ot' (the reference's only route), 'uniform', or 'rating-ot': the reference's documented alternative, OT groups on
-                 the sparse rating matrix (csrc/csr_group.hip), which needs no user matrix of an earlier --group 0 run
+                 the sparse rating matrix (csrc/csr_group.hip, DESIGN 4.17), which needs no user matrix of an earlier --group 0 run;
+                 'rating-bkmeans': the balanced k-means the reference compares OT grouping against, on the same sparse matrix
+                 (csrc/csr_kmeans.hip).  Plain 'rating-kmeans' stays with Group.grouping: its shards are not balanced
   --data-dir / --save-dir   roots of data/ and result/ (default: ./data, ./result)
 """
 import argparse
@@ -31,7 +33,7 @@ parser.add_argument('--delper', type=int, default=2, help='deleted user proporti
 parser.add_argument('--deltype', type=str, default='rand', help='deletion type')
 parser.add_argument('--k', type=int, default=16, help='embedding width')
 parser.add_argument('--parallel', type=int, default=1, help='1 (default): shards side by side / across GPUs; 0: one after the other')
-parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', or 'rating-ot': OT groups on the sparse rating matrix, no --group 0 run needed")
+parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', 'rating-ot' (OT groups) or 'rating-bkmeans' (balanced k-means groups) on the sparse rating matrix, no --group 0 run needed")
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -49,7 +51,7 @@ def main(argv=None):
     assert args.learn in ['sisa']
     assert args.delper in [2, 5]
     assert args.deltype in ['rand']
-    assert args.group_type in ['emb-ot', 'uniform', 'rating-ot']
+    assert args.group_type in ['emb-ot', 'uniform', 'rating-ot', 'rating-bkmeans']
 
     import torch
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:

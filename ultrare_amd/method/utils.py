@@ -631,9 +631,63 @@ def _dense_f32(sp_mat):
     return np.ascontiguousarray(sp_mat.toarray() if hasattr(sp_mat, 'toarray') else sp_mat, dtype=np.float32)
 
 
+def _kmeans_takes_csr(sp_mat):
+    """The CSR route (csrc/csr_kmeans.hip): always for a (csr, csc) pair of Compressed, and for a SciPy sparse matrix wider
+    than group.DENSE_MAX_ITEMS; everything else keeps the dense route."""
+    if not _is_sparse(sp_mat):
+        return False
+    if isinstance(sp_mat, tuple):
+        return True
+    from ..group import DENSE_MAX_ITEMS
+    return len(sp_mat.shape) != 2 or sp_mat.shape[1] > DENSE_MAX_ITEMS      # (not 2-D: check_kmeans_args refuses it)
+
+
+def _kmeans_csr_set(sp_mat, k, n_user):
+    """The checked matrix on the device; every refusal comes before any device work."""
+    from ..sparse_kmeans import check_kmeans_args
+    halves = check_kmeans_args(sp_mat, k)
+    if halves[0].shape[0] != n_user:
+        raise ValueError(f'n_user = {n_user} but the matrix has {halves[0].shape[0]} rows')
+    return engine.CsrSet(halves)
+
+
+def _single_kmeans_csr(k, n_user, S, balanced, max_iter, rounds=None):
+    """singleKmeans on the sparse rating matrix S (an engine.CsrSet, checked by check_kmeans_args), never densified: per
+    round ure_csr_kmeans_cost -> ure_balanced_fill (the fill, or the argmin) -> the labels and the n chosen distances to
+    the host -> ure_csr_kmeans_centroids.  The same draw, the same float32 arithmetic and the same stop as the dense route:
+    equal labels and inertia.  rounds (a list) receives the fill's round count of every k-means round."""
+    from ..sparse_group import dense_rows
+    n = S.n
+    assert n == n_user
+    group_len = int(np.ceil(n_user / k))
+    cen_idx = np.random.choice(n_user, k, replace=False)
+    Ct = torch.from_numpy(np.ascontiguousarray(dense_rows(S.csr, cen_idx).T)).to(S.device)
+    label = np.zeros(n, dtype=np.int32)
+    inertia = 0.0
+    for _ in range(max_iter):
+        dist_d = engine.csr_kmeans_cost(S, Ct, k)
+        label_d, fill_rounds = engine.balanced_fill(dist_d, group_len if balanced else 0)
+        if rounds is not None:
+            rounds.append(fill_rounds)
+        chosen = dist_d.gather(1, label_d.to(torch.int64).unsqueeze(1)).squeeze(1)
+        new_label = label_d.cpu().numpy()
+        inertia = float(np.sum(chosen.cpu().numpy()))       # numpy's float32 pairwise sum, as ure_host_kmeans_assign restates it
+        if (new_label == label).all():
+            break
+        label = new_label
+        Ct, counts = engine.csr_kmeans_centroids(S, label_d, k)
+        if int(counts.min().item()) == 0:
+            raise ZeroDivisionError('a cluster lost all its members (utils.py:403 divides by its size)')
+    return label.astype(np.int64), inertia
+
+
 def singleKmeans(k, n_user, sp_mat, balanced, max_iter):
     """utils.py:354-404.  sp_mat: csr_matrix or array [n_user, n_embedding]; initial centroids from
-    numpy's global generator.  Returns (label int64 [n_user], inertia)."""
+    numpy's global generator.  Returns (label int64 [n_user], inertia).  A (csr, csc) pair of sparse_group.Compressed, and a
+    SciPy sparse matrix wider than group.DENSE_MAX_ITEMS, run on the sparse matrix (_single_kmeans_csr); bad input is
+    refused before any device work."""
+    if _kmeans_takes_csr(sp_mat):
+        return _single_kmeans_csr(k, n_user, _kmeans_csr_set(sp_mat, k, n_user), balanced, max_iter)
     X = _dense_f32(sp_mat)
     n, d = X.shape
     assert n == n_user
@@ -667,10 +721,15 @@ def singleKmeans(k, n_user, sp_mat, balanced, max_iter):
 
 
 def kmeans(n_group, n_user, sp_mat, balanced=False, n_init=5, max_iter=10):
-    """utils.py:406-418: the labels of the best of n_init runs (smallest inertia)."""
+    """utils.py:406-418: the labels of the best of n_init runs (smallest inertia).  On the CSR route the matrix is checked
+    and uploaded once for all runs."""
+    S = _kmeans_csr_set(sp_mat, n_group, n_user) if _kmeans_takes_csr(sp_mat) else None
     tmp_inertia, fin_label = 1e10, None
     for _ in range(n_init):
-        label, inertia = singleKmeans(n_group, n_user, sp_mat, balanced, max_iter)
+        if S is not None:
+            label, inertia = _single_kmeans_csr(n_group, n_user, S, balanced, max_iter)
+        else:
+            label, inertia = singleKmeans(n_group, n_user, sp_mat, balanced, max_iter)
         if inertia < tmp_inertia:
             tmp_inertia = inertia
             fin_label = label

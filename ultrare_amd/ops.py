@@ -30,6 +30,12 @@ to resident shards -- and stays behind engine.TrainJob.
                                                                           centroids held transposed in Ct [n_item, ldc]
     torch.ops.ultrare.csr_centroids(col_off, row, val, label, k)
                                                         (new)             (Ct [n_item, k], counts [k]) from the CSC
+    torch.ops.ultrare.csr_kmeans_cost(row_off, col, val, Ct, k)
+                                                        utils.py:373-375  [n, k] k-means distances of CSR rows, scipy's fp32 order
+    torch.ops.ultrare.csr_kmeans_centroids(col_off, row, val, label, k)
+                                                        utils.py:402-403  (Ct [n_item, k], counts [k]): scipy's sparse mean from the CSC
+    torch.ops.ultrare.balanced_fill(dist, capacity)     utils.py:377-396  (label [n], rounds [1] on the host) of a device [n, k] matrix:
+                                                                          argmin (capacity <= 0) or the balanced greedy fill
     torch.ops.ultrare.mmd_grad(X, rows, n1, kernel_mul, kernel_num, fix_sigma)
                                                         utils.py:223-267  (block sums [4], grad [m, d], bandwidth) of the MMD
                                                                           loss on the rows `rows` of X, the first n1 the source
@@ -271,6 +277,66 @@ def csr_centroids(col_off: torch.Tensor, row: torch.Tensor, val: torch.Tensor, l
 @csr_centroids.register_fake
 def _(col_off, row, val, label, k):
     return val.new_empty(col_off.numel() - 1, k), val.new_empty(k, dtype=torch.int32)
+
+
+@torch.library.custom_op('ultrare::csr_kmeans_cost', mutates_args=())
+def csr_kmeans_cost(row_off: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Ct: torch.Tensor, k: int) -> torch.Tensor:
+    _dev(row_off, col, val, Ct)
+    row_off, col, val = _csr_half(row_off, col, val)
+    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and k == Ct.shape[1]):
+        raise ValueError(f'Ct must be a contiguous float32 [n_item, k] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
+    if int(col.max()) >= Ct.shape[0] or int(col.min()) < 0:
+        raise ValueError(f'column indices outside the {Ct.shape[0]} rows of Ct')
+    L, n = nv.lib(), row_off.numel() - 1
+    nbytes = int(L.ure_csr_kmeans_cost_scratch(k))
+    if nbytes < 0:
+        raise ValueError(f'k = {k} outside 1 .. 256')
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=Ct.device)
+    dist = torch.empty(n, k, dtype=torch.float32, device=Ct.device)
+    nv.check(L.ure_csr_kmeans_cost(nv.ptr(row_off), nv.ptr(col), nv.ptr(val), n, int(Ct.shape[0]), nv.ptr(Ct), k, nv.ptr(dist), nv.ptr(scratch),
+                                   nbytes, nv.stream_handle()), 'ure_csr_kmeans_cost')
+    return dist
+
+
+@csr_kmeans_cost.register_fake
+def _(row_off, col, val, Ct, k):
+    return Ct.new_empty(row_off.numel() - 1, k)
+
+
+@torch.library.custom_op('ultrare::csr_kmeans_centroids', mutates_args=())
+def csr_kmeans_centroids(col_off: torch.Tensor, row: torch.Tensor, val: torch.Tensor, label: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(col_off, row, val, label)
+    col_off, row, val = _csr_half(col_off, row, val)
+    label = label.to(torch.int32).contiguous()
+    n, n_item = label.numel(), col_off.numel() - 1
+    if int(row.max()) >= n or int(row.min()) < 0:
+        raise ValueError(f'row indices outside the {n} labels')
+    if int(label.min()) < 0 or int(label.max()) >= k:
+        raise ValueError(f'label must hold values in [0, {k})')
+    if not 1 <= k <= 256:
+        raise ValueError(f'k = {k} outside 1 .. 256')
+    Ct = torch.empty(n_item, k, dtype=torch.float32, device=val.device)
+    counts = torch.empty(k, dtype=torch.int32, device=val.device)
+    nv.check(nv.lib().ure_csr_kmeans_centroids(nv.ptr(col_off), nv.ptr(row), nv.ptr(val), n_item, n, nv.ptr(label), k, nv.ptr(Ct), nv.ptr(counts),
+                                               nv.stream_handle()), 'ure_csr_kmeans_centroids')
+    return Ct, counts
+
+
+@csr_kmeans_centroids.register_fake
+def _(col_off, row, val, label, k):
+    return val.new_empty(col_off.numel() - 1, k), val.new_empty(k, dtype=torch.int32)
+
+
+@torch.library.custom_op('ultrare::balanced_fill', mutates_args=())
+def balanced_fill(dist: torch.Tensor, capacity: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _dev(dist)
+    label, rounds = engine.balanced_fill(dist, capacity)
+    return label, torch.tensor([rounds], dtype=torch.int64)
+
+
+@balanced_fill.register_fake
+def _(dist, capacity):
+    return dist.new_empty(dist.shape[0], dtype=torch.int32), torch.empty(1, dtype=torch.int64)
 
 
 def _group_rows(X, rows, n1):
