@@ -13,6 +13,10 @@
  *     host passes torch tensors' data_ptr()); the library never frees it.
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  All
  *     work is enqueued on it; nothing here synchronises unless it says so.
+ *   - memory contract of every stateless device entry point: the call writes every byte of every output
+ *     buffer, no result depends on what the outputs or the scratch held before it, nothing is written outside
+ *     [out, out + size) of an output or [scratch, scratch + its _scratch sizer's bytes) of the scratch, and no input
+ *     buffer is modified (in-place entries such as ure_merge_rows modify only the rows they name).
  *   - return value: 0 = success, otherwise a hipError_t (or -1 for argument
  *     errors); ure_last_error() returns a thread-local message.
  *   - fp32 tables are row-major [rows][d]; d is a power of two, 4 <= d <= 256

@@ -88,7 +88,7 @@ def test_fixture_cases_match_the_contract_and_the_reference(gold, case):
 SHAPES = [(63, 1), (64, 64), (65, 64), (1, 200), (700, 900)]
 
 
-@pytest.mark.parametrize('d', [1, 5, 16, 17, 32, 128])
+@pytest.mark.parametrize('d', [1, 5, 16, 17, 32, 33, 64, 128])       # (33 and 64: both ends of the DQ = 4 instantiation, 33 <= d <= 64)
 @pytest.mark.parametrize('shape', SHAPES)
 def test_synthetic_crossings_match_the_contract(d, shape):
     n1, n2 = shape
