@@ -309,8 +309,8 @@ def test_no_csr_kernel_spills(nv):
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import isa_report
     rows = [r for r in isa_report.kernels(nv.LIB_PATH) if r['name'].startswith('csr_')]
-    assert len([r for r in rows if r['name'].startswith('csr_cost_kernel<')]) == 7
-    assert len([r for r in rows if r['name'].startswith('csr_centroid_kernel<')]) == 7
+    assert len([r for r in rows if r['name'].startswith('csr_row_walk<OtCost,')]) == 7
+    assert len([r for r in rows if r['name'].startswith('csr_col_walk<OtMean,')]) == 7
     for r in rows:
         assert r['vgpr_spill'] == 0 and r['sgpr_spill'] == 0 and r['scratch'] == 0, r
 

@@ -269,9 +269,9 @@ def test_no_kmeans_kernel_spills(nv):
     import sys
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import isa_report
-    rows = [r for r in isa_report.kernels(nv.LIB_PATH) if r['name'].startswith(('km_', 'fill_'))]
-    assert len([r for r in rows if r['name'].startswith('km_cost_kernel<')]) == 7
-    assert len([r for r in rows if r['name'].startswith('km_centroid_kernel<')]) == 7
+    rows = [r for r in isa_report.kernels(nv.LIB_PATH) if r['name'].startswith(('km_', 'fill_', 'csr_row_walk<KmCost,', 'csr_col_walk<KmMean,'))]
+    assert len([r for r in rows if r['name'].startswith('csr_row_walk<KmCost,')]) == 7
+    assert len([r for r in rows if r['name'].startswith('csr_col_walk<KmMean,')]) == 7
     assert {'km_csq_kernel', 'fill_argmin_kernel', 'fill_choose_kernel', 'fill_select_kernel'} <= {r['name'].split('(')[0] for r in rows}
     for r in rows:
         assert r['vgpr_spill'] == 0 and r['sgpr_spill'] == 0 and r['scratch'] == 0, r

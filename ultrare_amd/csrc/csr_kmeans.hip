@@ -12,9 +12,9 @@
 // at +0.0 and change no bit, so for finite centroids the results equal the dense route's bit for bit.  A chain is never split
 // across lanes and nothing is accumulated with floating-point atomics.
 //
-// The lane layout is csr_group.hip's: the centroids travel TRANSPOSED, Ct [n_item][k]; a lane owns one (row, centroid) or
-// (item, cluster) pair, a group of G = pow2 >= min(k, 64) lanes shares the row (item) and hands its entries round with
-// cross-lane reads; k > 64 loops over chunks of 64.
+// The lane layout and the two walks are csr_lanes.h's, shared with csr_group.hip: the centroids travel TRANSPOSED,
+// Ct [n_item][k]; a lane owns one (row, centroid) or (item, cluster) pair, a group of G = pow2 >= min(k, 64) lanes shares the
+// row (item) and hands its entries round with cross-lane reads; k > 64 loops over chunks of 64.
 //
 // The fill.  ure_host_kmeans_assign sorts the n k keys (order-preserving map of the float bits << 32 | flat index) and walks
 // them, giving a user its first group with room.  That walk yields the one stable matching of the market in which users and
@@ -70,113 +70,34 @@ __global__ __launch_bounds__(kBlock) void km_csq_kernel(const float *__restrict_
     if ((int)threadIdx.x < k) stg(csq + threadIdx.x, s);
 }
 
-template <int G>
-__global__ __launch_bounds__(kBlock) void km_cost_kernel(const int64_t *__restrict__ row_off, const int32_t *__restrict__ col,
-                                                         const float *__restrict__ val, int64_t n, int64_t n_item,
-                                                         const float *__restrict__ Ct, int k, const float *__restrict__ csq,
-                                                         float *__restrict__ dist)
-{
-    constexpr int kRows = kBlock / G;                      // rows of a workgroup
-    const int sub = threadIdx.x % G;
-    const int64_t i = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    if (i >= n) return;                                    // whole groups leave together
-    const int64_t b = ldg(row_off + i), e = ldg(row_off + i + 1);
-    const unsigned last_item = (unsigned)(n_item - 1);
-    for (int c0 = 0; c0 < k; c0 += G) {                    // one pass for k <= 64
-        const int c = c0 + sub;
-        const float *__restrict__ ct = Ct + min(c, k - 1);  // padding lanes read a valid column and store nothing
-        float dot = 0.f, esq = 0.f;
-        // (an index outside the catalogue never leaves Ct: the callers check their matrices, this keeps a bad one harmless)
-        unsigned next_j = b + sub < e ? min((unsigned)ldg(col + b + sub), last_item) : 0u;
-        float next_x = b + sub < e ? ldg(val + b + sub) : 0.f;
-        for (int64_t p0 = b; p0 < e; p0 += G) {
-            const unsigned mine_j = next_j;
-            const float mine_x = next_x;
-            const int64_t q = p0 + G + sub;                // the next tile's entries travel while this one is added
-            next_j = q < e ? min((unsigned)ldg(col + q), last_item) : 0u;
-            next_x = q < e ? ldg(val + q) : 0.f;
-            const int m = (int)min<int64_t>(G, e - p0);
-            if (m == G && G >= 4) {                        // a full tile: the G centroid values are requested four at a time
-#pragma unroll
-                for (int u = 0; u < G; u += 4) {
-                    float cv[4], x[4];
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        const unsigned j = group_read<G>(mine_j, u + w);
-                        x[w] = group_read<G>(mine_x, u + w);
-                        cv[w] = ldg(ct + (size_t)j * k);
-                    }
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        dot = __fadd_rn(dot, __fmul_rn(x[w], cv[w]));
-                        esq = __fadd_rn(esq, __fmul_rn(x[w], x[w]));
-                    }
-                }
-            } else {
-                for (int u = 0; u < m; ++u) {
-                    const unsigned j = group_read<G>(mine_j, u);
-                    const float x = group_read<G>(mine_x, u);
-                    dot = __fadd_rn(dot, __fmul_rn(x, ldg(ct + (size_t)j * k)));
-                    esq = __fadd_rn(esq, __fmul_rn(x, x));
-                }
-            }
-        }
-        if (c < k) stg(dist + (size_t)i * k + c, __fadd_rn(__fadd_rn(__fmul_rn(-2.0f, dot), esq), ldg(csq + c)));
+// The cost's arithmetic: float32 chains, one rounded multiply and one rounded add per term (the _rn intrinsics say so whatever
+// the contraction flag of the build).
+struct KmCost {
+    using acc_t = float;
+    using norm_t = float;
+    static __device__ __forceinline__ int stride(int, int k) { return k; }          // Ct [n_item][k]: the stride is k itself
+    static __device__ __forceinline__ float madd(float acc, float a, float b) { return __fadd_rn(acc, __fmul_rn(a, b)); }
+    static __device__ __forceinline__ void store(float *dist, int c, int64_t i, int64_t, int k, float dot, float esq, const float *csq)
+    {
+        stg(dist + (size_t)i * k + c, __fadd_rn(__fadd_rn(__fmul_rn(-2.0f, dot), esq), ldg(csq + c)));   // dist[i][c]
     }
-}
+};
 
-// Owner computes, as csr_centroid_kernel: the group that owns item j walks its column in ascending user id; lane c adds
-// x * inv_c when the user's label is c.  A long column stays with its one owner.
-template <int G>
-__global__ __launch_bounds__(kBlock) void km_centroid_kernel(const int64_t *__restrict__ col_off, const int32_t *__restrict__ row,
-                                                             const float *__restrict__ val, const int32_t *__restrict__ label, int64_t n,
-                                                             int64_t n_item, int k, const int32_t *__restrict__ counts,
-                                                             float *__restrict__ Ct)
-{
-    constexpr int kItems = kBlock / G;
-    const int sub = threadIdx.x % G;
-    const int64_t j = (int64_t)blockIdx.x * kItems + threadIdx.x / G;
-    if (j >= n_item) return;
-    const int64_t b = ldg(col_off + j), e = ldg(col_off + j + 1);
-    const unsigned last_user = (unsigned)(n - 1);
-    for (int c0 = 0; c0 < k; c0 += G) {
-        const int c = c0 + sub;
+// The centroids' arithmetic: lane c adds x * inv_c, inv_c = float32(1 / count_c) read before the walk.
+struct KmMean {
+    using acc_t = float;
+    struct prep_t {
+        int cnt;
+        float inv;
+    };
+    static __device__ __forceinline__ prep_t prepare(const int32_t *counts, int c, int k)
+    {
         const int cnt = ldg(counts + min(c, k - 1));
-        const float inv = (float)(1.0 / (double)cnt);      // (inf for a cluster without members: no entry is its, nothing is multiplied)
-        float s = 0.f;
-        int next_l = -1;
-        float next_x = 0.f;
-        if (b + sub < e) {
-            next_l = ldg(label + min((unsigned)ldg(row + b + sub), last_user));
-            next_x = ldg(val + b + sub);
-        }
-        for (int64_t p0 = b; p0 < e; p0 += G) {
-            const int mine_l = next_l;
-            const float mine_x = next_x;
-            const int64_t q = p0 + G + sub;                // the next tile's entries and labels travel while this one is added
-            if (q < e) {
-                next_l = ldg(label + min((unsigned)ldg(row + q), last_user));
-                next_x = ldg(val + q);
-            }
-            const int m = (int)min<int64_t>(G, e - p0);
-            if (m == G) {
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int l = group_read<G>(mine_l, u);
-                    const float x = group_read<G>(mine_x, u);
-                    if (l == c) s = __fadd_rn(s, __fmul_rn(x, inv));
-                }
-            } else {
-                for (int u = 0; u < m; ++u) {
-                    const int l = group_read<G>(mine_l, u);
-                    const float x = group_read<G>(mine_x, u);
-                    if (l == c) s = __fadd_rn(s, __fmul_rn(x, inv));
-                }
-            }
-        }
-        if (c < k) stg(Ct + (size_t)j * k + c, cnt > 0 ? s : 0.f);
+        return {cnt, (float)(1.0 / (double)cnt)};          // (inf for a cluster without members: no entry is its, nothing is multiplied)
     }
-}
+    static __device__ __forceinline__ float add(float s, float x, prep_t p) { return __fadd_rn(s, __fmul_rn(x, p.inv)); }
+    static __device__ __forceinline__ float finish(float s, prep_t p, const int32_t *, int) { return p.cnt > 0 ? s : 0.f; }
+};
 
 // ---- the fill ------------------------------------------------------------------------------------------------------------------
 // The host's key: the order-preserving map of the float's bit pattern above the flat index (-0.0 before +0.0, NaN patterns by
@@ -299,29 +220,17 @@ int ure_csr_kmeans_cost(const int64_t *row_off, const int32_t *col, const float 
                         float *dist_nk, void *workspace, int64_t workspace_bytes, void *stream)
 {
     URE_ARG(row_off && col && val && Ct && dist_nk);
-    URE_ARG(n >= 1 && n <= INT32_MAX);
-    URE_ARG(n_item >= 1 && n_item <= INT32_MAX);
-    URE_ARG(k >= 1);
-    URE_ARG(k <= kCsrMaxK);
+    URE_CSR_SIZES(n, n_item, k);
     URE_ARG(workspace != nullptr);
     URE_ARG(workspace_bytes >= ure_csr_kmeans_cost_scratch(k));
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *csq = static_cast<float *>(workspace);
     hipLaunchKernelGGL(km_csq_kernel, dim3(1), dim3(kBlock), 0, st, Ct, n_item, k, csq);
     const int G = group_width(k);
-    const unsigned blocks = (unsigned)((n + kBlock / G - 1) / (kBlock / G));
-#define URE_KM_COST(W) \
-    case W: hipLaunchKernelGGL(km_cost_kernel<W>, dim3(blocks), dim3(kBlock), 0, st, row_off, col, val, n, n_item, Ct, k, csq, dist_nk); break
-    switch (G) {
-        URE_KM_COST(1);
-        URE_KM_COST(2);
-        URE_KM_COST(4);
-        URE_KM_COST(8);
-        URE_KM_COST(16);
-        URE_KM_COST(32);
-        URE_KM_COST(64);
-    }
-#undef URE_KM_COST
+    const unsigned blocks = group_blocks(n, G);
+    dispatch_group_width(G, [&](auto W) {
+        hipLaunchKernelGGL((csr_row_walk<KmCost, decltype(W)::value>), dim3(blocks), dim3(kBlock), 0, st, row_off, col, val, n, n_item, Ct, k, k, csq, dist_nk);
+    });
     URE_HIP(hipGetLastError());
     return 0;
 }
@@ -330,28 +239,14 @@ int ure_csr_kmeans_centroids(const int64_t *col_off, const int32_t *row, const f
                              float *Ct, int32_t *counts, void *stream)
 {
     URE_ARG(col_off && row && val && label && Ct && counts);
-    URE_ARG(n >= 1 && n <= INT32_MAX);
-    URE_ARG(n_item >= 1 && n_item <= INT32_MAX);
-    URE_ARG(k >= 1);
-    URE_ARG(k <= kCsrMaxK);
+    URE_CSR_SIZES(n, n_item, k);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    URE_HIP(hipMemsetAsync(counts, 0, (size_t)k * sizeof(int32_t), st));
-    const unsigned cblocks = (unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 1024);
-    hipLaunchKernelGGL(csr_counts_kernel, dim3(cblocks), dim3(kBlock), 0, st, label, n, k, counts);
+    URE_HIP(launch_counts(label, n, k, counts, st));
     const int G = group_width(k);
-    const unsigned blocks = (unsigned)((n_item + kBlock / G - 1) / (kBlock / G));
-#define URE_KM_CENT(W) \
-    case W: hipLaunchKernelGGL(km_centroid_kernel<W>, dim3(blocks), dim3(kBlock), 0, st, col_off, row, val, label, n, n_item, k, counts, Ct); break
-    switch (G) {
-        URE_KM_CENT(1);
-        URE_KM_CENT(2);
-        URE_KM_CENT(4);
-        URE_KM_CENT(8);
-        URE_KM_CENT(16);
-        URE_KM_CENT(32);
-        URE_KM_CENT(64);
-    }
-#undef URE_KM_CENT
+    const unsigned blocks = group_blocks(n_item, G);
+    dispatch_group_width(G, [&](auto W) {
+        hipLaunchKernelGGL((csr_col_walk<KmMean, decltype(W)::value>), dim3(blocks), dim3(kBlock), 0, st, col_off, row, val, label, n, n_item, k, counts, Ct, k);
+    });
     URE_HIP(hipGetLastError());
     return 0;
 }

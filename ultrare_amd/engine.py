@@ -1552,10 +1552,32 @@ class CsrSet:
             torch.from_numpy(a).to(self.device)
             for a in (self.csr.off, pad(self.csr.idx), pad(self.csr.val), self.csc.off, pad(self.csc.idx), pad(self.csc.val))]
 
+    @classmethod
+    def from_device(cls, n, n_item, row_off=None, col=None, val=None, col_off=None, row=None, cval=None):
+        """Halves that are on the device already (int64 offsets, int32 indices, float32 values, at least one entry; the caller
+        vouches for the index ranges), n rows by n_item columns; no host copy.  A half that is not given stays None."""
+        S = cls.__new__(cls)
+        halves = (row_off, col, val, col_off, row, cval)
+        for half in (halves[:3], halves[3:]):
+            if any(t is not None for t in half) and [getattr(t, 'dtype', None) for t in half] != [torch.int64, torch.int32, torch.float32]:
+                raise ValueError('a CSR half is (int64 offsets, int32 indices, float32 values) tensors, all three')
+        if row_off is None and col_off is None:
+            raise ValueError('neither the CSR nor the CSC half is given')
+        S.csr = S.csc = None
+        S.n, S.n_item, S.nnz = int(n), int(n_item), int((cval if val is None else val).numel())
+        S.device = (col_off if row_off is None else row_off).device
+        S.row_off, S.col, S.val, S.col_off, S.row, S.cval = (None if t is None else t.contiguous() for t in halves)
+        return S
 
-def _csr_same_device(S, t, what):
-    if t.device != S.row_off.device:
-        raise ValueError(f'{what} is on {t.device} but the CsrSet was uploaded to {S.row_off.device}')
+
+def _csr_same_device(off, t, what):
+    if t.device != off.device:
+        raise ValueError(f'{what} is on {t.device} but the CsrSet was uploaded to {off.device}')
+
+
+def _csr_has(S, half):
+    if getattr(S, 'row_off' if half == 'CSR' else 'col_off') is None:
+        raise ValueError(f'this CsrSet was made without the {half} half')
 
 
 def _csr_held_for(stream, *tensors):
@@ -1573,23 +1595,50 @@ def _csr_k(k):
     return int(k)
 
 
+def _csr_label(S, label, k, who):
+    """label (n values in [0, k): a host array, or a device int32 tensor whose range is read back once) as a checked device
+    int32 tensor."""
+    if torch.is_tensor(label):
+        if not label.is_cuda:
+            raise nv.NativeError(f'{who} runs on the HIP device only (no CPU fallback)')
+        if label.dtype != torch.int32 or label.shape != (S.n,) or int(label.min()) < 0 or int(label.max()) >= k:
+            raise ValueError(f'label must be n = {S.n} int32 values in [0, {k})')
+        _csr_has(S, 'CSC')
+        _csr_same_device(S.col_off, label, 'label')
+        return label.contiguous()
+    lab = np.ascontiguousarray(label)
+    if lab.shape != (S.n,) or lab.min() < 0 or lab.max() >= k:
+        raise ValueError(f'label must be n = {S.n} values in [0, {k})')
+    _csr_has(S, 'CSC')
+    return to_device_async(lab.astype(np.int32), S.device)
+
+
+def _csr_cost_call(entry, S, Ct, k, exact, dist_shape, stream):
+    """Check Ct [n_item, >= k] (exact: [n_item, k]), size the scratch by `entry`_scratch, allocate dist and call `entry`
+    (ure_csr_cost's argument list; without the stride when exact)."""
+    if not (torch.is_tensor(Ct) and Ct.is_cuda):
+        raise nv.NativeError(f'{entry[4:]} runs on the HIP device only (no CPU fallback)')
+    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and Ct.shape[0] == S.n_item
+            and (Ct.shape[1] == k if exact else Ct.shape[1] >= k)):
+        raise ValueError(f"Ct must be a contiguous float32 [{S.n_item}, {'' if exact else '>= '}{k}] tensor, not {tuple(Ct.shape)} {Ct.dtype}")
+    _csr_has(S, 'CSR')
+    _csr_same_device(S.row_off, Ct, 'Ct')
+    L, dev = nv.lib(), Ct.device
+    nbytes = int(getattr(L, entry + '_scratch')(k))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(*dist_shape, dtype=torch.float32, device=dev)
+    stride = () if exact else (int(Ct.shape[1]),)
+    nv.check(getattr(L, entry)(nv.ptr(S.row_off), nv.ptr(S.col), nv.ptr(S.val), S.n, S.n_item, nv.ptr(Ct), *stride, k, nv.ptr(dist),
+                               nv.ptr(scratch), nbytes, nv.stream_handle(stream)), entry)
+    _csr_held_for(stream, scratch, dist)
+    return dist
+
+
 def csr_cost(S, Ct, k, stream=None):
     """ure_csr_cost: dist [k, n] float32 on the device (ure_ot_cost's layout) of the rows of S (a CsrSet) against the k
     centroids held transposed in the device tensor Ct [n_item, ldc] float32, ldc >= k.  Nothing synchronises."""
     k = _csr_k(k)
-    if not (torch.is_tensor(Ct) and Ct.is_cuda):
-        raise nv.NativeError('csr_cost runs on the HIP device only (no CPU fallback)')
-    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and Ct.shape[0] == S.n_item and Ct.shape[1] >= k):
-        raise ValueError(f'Ct must be a contiguous float32 [{S.n_item}, >= {k}] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
-    _csr_same_device(S, Ct, 'Ct')
-    L, dev = nv.lib(), Ct.device
-    nbytes = int(L.ure_csr_cost_scratch(k))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    dist = torch.empty(k, S.n, dtype=torch.float32, device=dev)
-    nv.check(L.ure_csr_cost(nv.ptr(S.row_off), nv.ptr(S.col), nv.ptr(S.val), S.n, S.n_item, nv.ptr(Ct), int(Ct.shape[1]), k, nv.ptr(dist),
-                            nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_csr_cost')
-    _csr_held_for(stream, scratch, dist)
-    return dist
+    return _csr_cost_call('ure_csr_cost', S, Ct, k, False, (k, S.n), stream)
 
 
 def csr_centroids(S, label, k, ldc=None, stream=None):
@@ -1601,18 +1650,7 @@ def csr_centroids(S, label, k, ldc=None, stream=None):
     ldc = k if ldc is None else int(ldc)
     if ldc < k:
         raise ValueError(f'ldc = {ldc} < k = {k}')
-    if torch.is_tensor(label):
-        if not label.is_cuda:
-            raise nv.NativeError('csr_centroids runs on the HIP device only (no CPU fallback)')
-        if label.dtype != torch.int32 or label.shape != (S.n,) or int(label.min()) < 0 or int(label.max()) >= k:
-            raise ValueError(f'label must be n = {S.n} int32 values in [0, {k})')
-        _csr_same_device(S, label, 'label')
-        lab_d = label.contiguous()
-    else:
-        lab = np.ascontiguousarray(label)
-        if lab.shape != (S.n,) or lab.min() < 0 or lab.max() >= k:
-            raise ValueError(f'label must be n = {S.n} values in [0, {k})')
-        lab_d = to_device_async(lab.astype(np.int32), S.device)
+    lab_d = _csr_label(S, label, k, 'csr_centroids')
     dev = lab_d.device
     Ct = (torch.empty if ldc == k else torch.zeros)(S.n_item, ldc, dtype=torch.float32, device=dev)
     counts = torch.empty(k, dtype=torch.int32, device=dev)
@@ -1629,19 +1667,7 @@ def csr_kmeans_cost(S, Ct, k, stream=None):
     """ure_csr_kmeans_cost: dist [n, k] float32 on the device (ure_kmeans_cost's layout) of the rows of S (a CsrSet) against
     the k centroids held transposed in the device tensor Ct [n_item, k] float32.  Nothing synchronises."""
     k = _csr_k(k)
-    if not (torch.is_tensor(Ct) and Ct.is_cuda):
-        raise nv.NativeError('csr_kmeans_cost runs on the HIP device only (no CPU fallback)')
-    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and tuple(Ct.shape) == (S.n_item, k)):
-        raise ValueError(f'Ct must be a contiguous float32 [{S.n_item}, {k}] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
-    _csr_same_device(S, Ct, 'Ct')
-    L, dev = nv.lib(), Ct.device
-    nbytes = int(L.ure_csr_kmeans_cost_scratch(k))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    dist = torch.empty(S.n, k, dtype=torch.float32, device=dev)
-    nv.check(L.ure_csr_kmeans_cost(nv.ptr(S.row_off), nv.ptr(S.col), nv.ptr(S.val), S.n, S.n_item, nv.ptr(Ct), k, nv.ptr(dist),
-                                   nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_csr_kmeans_cost')
-    _csr_held_for(stream, scratch, dist)
-    return dist
+    return _csr_cost_call('ure_csr_kmeans_cost', S, Ct, k, True, (S.n, k), stream)
 
 
 def csr_kmeans_centroids(S, label, k, stream=None):
@@ -1650,18 +1676,7 @@ def csr_kmeans_centroids(S, label, k, stream=None):
     transposed as csr_kmeans_cost reads them.  A cluster without members gives zeros and counts 0.  Nothing synchronises
     after the launch."""
     k = _csr_k(k)
-    if torch.is_tensor(label):
-        if not label.is_cuda:
-            raise nv.NativeError('csr_kmeans_centroids runs on the HIP device only (no CPU fallback)')
-        if label.dtype != torch.int32 or label.shape != (S.n,) or int(label.min()) < 0 or int(label.max()) >= k:
-            raise ValueError(f'label must be n = {S.n} int32 values in [0, {k})')
-        _csr_same_device(S, label, 'label')
-        lab_d = label.contiguous()
-    else:
-        lab = np.ascontiguousarray(label)
-        if lab.shape != (S.n,) or lab.min() < 0 or lab.max() >= k:
-            raise ValueError(f'label must be n = {S.n} values in [0, {k})')
-        lab_d = to_device_async(lab.astype(np.int32), S.device)
+    lab_d = _csr_label(S, label, k, 'csr_kmeans_centroids')
     dev = lab_d.device
     Ct = torch.empty(S.n_item, k, dtype=torch.float32, device=dev)
     counts = torch.empty(k, dtype=torch.int32, device=dev)

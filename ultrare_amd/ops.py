@@ -233,23 +233,34 @@ def _csr_half(off, idx, val):
     return off.contiguous(), idx.contiguous(), val.contiguous()
 
 
-@torch.library.custom_op('ultrare::csr_cost', mutates_args=())
-def csr_cost(row_off: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Ct: torch.Tensor, k: int) -> torch.Tensor:
+def _csr_rows(row_off, col, val, Ct, width='>= k'):
+    """The CSR half of a cost op as a CsrSet of Ct's item count, its column indices checked against it."""
     _dev(row_off, col, val, Ct)
     row_off, col, val = _csr_half(row_off, col, val)
-    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and 1 <= k <= Ct.shape[1]):
-        raise ValueError(f'Ct must be a contiguous float32 [n_item, >= k] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
+    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous()):
+        raise ValueError(f'Ct must be a contiguous float32 [n_item, {width}] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
     if int(col.max()) >= Ct.shape[0] or int(col.min()) < 0:
         raise ValueError(f'column indices outside the {Ct.shape[0]} rows of Ct')
-    L, n = nv.lib(), row_off.numel() - 1
-    nbytes = int(L.ure_csr_cost_scratch(k))
-    if nbytes < 0:
-        raise ValueError(f'k = {k} outside 1 .. 256')
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=Ct.device)
-    dist = torch.empty(k, n, dtype=torch.float32, device=Ct.device)
-    nv.check(L.ure_csr_cost(nv.ptr(row_off), nv.ptr(col), nv.ptr(val), n, int(Ct.shape[0]), nv.ptr(Ct), int(Ct.shape[1]), k, nv.ptr(dist),
-                            nv.ptr(scratch), nbytes, nv.stream_handle()), 'ure_csr_cost')
-    return dist
+    return engine.CsrSet.from_device(row_off.numel() - 1, Ct.shape[0], row_off, col, val)
+
+
+def _csr_cols(col_off, row, val, label, k):
+    """The CSC half of a centroid op as a CsrSet of as many users as labels, and the labels as int32 [n] in [0, k) (the engine
+    call reads the label range back a second time)."""
+    _dev(col_off, row, val, label)
+    col_off, row, val = _csr_half(col_off, row, val)
+    label = label.to(torch.int32).reshape(-1)
+    n = label.numel()
+    if int(row.max()) >= n or int(row.min()) < 0:
+        raise ValueError(f'row indices outside the {n} labels')
+    if int(label.min()) < 0 or int(label.max()) >= k:
+        raise ValueError(f'label must hold values in [0, {k})')
+    return engine.CsrSet.from_device(n, col_off.numel() - 1, col_off=col_off, row=row, cval=val), label
+
+
+@torch.library.custom_op('ultrare::csr_cost', mutates_args=())
+def csr_cost(row_off: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Ct: torch.Tensor, k: int) -> torch.Tensor:
+    return engine.csr_cost(_csr_rows(row_off, col, val, Ct), Ct, k)
 
 
 @csr_cost.register_fake
@@ -259,19 +270,7 @@ def _(row_off, col, val, Ct, k):
 
 @torch.library.custom_op('ultrare::csr_centroids', mutates_args=())
 def csr_centroids(col_off: torch.Tensor, row: torch.Tensor, val: torch.Tensor, label: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    _dev(col_off, row, val, label)
-    col_off, row, val = _csr_half(col_off, row, val)
-    label = label.to(torch.int32).contiguous()
-    n, n_item = label.numel(), col_off.numel() - 1
-    if int(row.max()) >= n or int(row.min()) < 0:
-        raise ValueError(f'row indices outside the {n} labels')
-    if int(label.min()) < 0 or int(label.max()) >= k:
-        raise ValueError(f'label must hold values in [0, {k})')
-    Ct = torch.empty(n_item, k, dtype=torch.float32, device=val.device)
-    counts = torch.empty(k, dtype=torch.int32, device=val.device)
-    nv.check(nv.lib().ure_csr_centroids(nv.ptr(col_off), nv.ptr(row), nv.ptr(val), nv.ptr(label), n, n_item, k, nv.ptr(Ct), k, nv.ptr(counts),
-                                        nv.stream_handle()), 'ure_csr_centroids')
-    return Ct, counts
+    return engine.csr_centroids(*_csr_cols(col_off, row, val, label, k), k)
 
 
 @csr_centroids.register_fake
@@ -281,21 +280,7 @@ def _(col_off, row, val, label, k):
 
 @torch.library.custom_op('ultrare::csr_kmeans_cost', mutates_args=())
 def csr_kmeans_cost(row_off: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Ct: torch.Tensor, k: int) -> torch.Tensor:
-    _dev(row_off, col, val, Ct)
-    row_off, col, val = _csr_half(row_off, col, val)
-    if not (Ct.dtype == torch.float32 and Ct.dim() == 2 and Ct.is_contiguous() and k == Ct.shape[1]):
-        raise ValueError(f'Ct must be a contiguous float32 [n_item, k] tensor, not {tuple(Ct.shape)} {Ct.dtype}')
-    if int(col.max()) >= Ct.shape[0] or int(col.min()) < 0:
-        raise ValueError(f'column indices outside the {Ct.shape[0]} rows of Ct')
-    L, n = nv.lib(), row_off.numel() - 1
-    nbytes = int(L.ure_csr_kmeans_cost_scratch(k))
-    if nbytes < 0:
-        raise ValueError(f'k = {k} outside 1 .. 256')
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=Ct.device)
-    dist = torch.empty(n, k, dtype=torch.float32, device=Ct.device)
-    nv.check(L.ure_csr_kmeans_cost(nv.ptr(row_off), nv.ptr(col), nv.ptr(val), n, int(Ct.shape[0]), nv.ptr(Ct), k, nv.ptr(dist), nv.ptr(scratch),
-                                   nbytes, nv.stream_handle()), 'ure_csr_kmeans_cost')
-    return dist
+    return engine.csr_kmeans_cost(_csr_rows(row_off, col, val, Ct, 'k'), Ct, k)
 
 
 @csr_kmeans_cost.register_fake
@@ -305,21 +290,7 @@ def _(row_off, col, val, Ct, k):
 
 @torch.library.custom_op('ultrare::csr_kmeans_centroids', mutates_args=())
 def csr_kmeans_centroids(col_off: torch.Tensor, row: torch.Tensor, val: torch.Tensor, label: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    _dev(col_off, row, val, label)
-    col_off, row, val = _csr_half(col_off, row, val)
-    label = label.to(torch.int32).contiguous()
-    n, n_item = label.numel(), col_off.numel() - 1
-    if int(row.max()) >= n or int(row.min()) < 0:
-        raise ValueError(f'row indices outside the {n} labels')
-    if int(label.min()) < 0 or int(label.max()) >= k:
-        raise ValueError(f'label must hold values in [0, {k})')
-    if not 1 <= k <= 256:
-        raise ValueError(f'k = {k} outside 1 .. 256')
-    Ct = torch.empty(n_item, k, dtype=torch.float32, device=val.device)
-    counts = torch.empty(k, dtype=torch.int32, device=val.device)
-    nv.check(nv.lib().ure_csr_kmeans_centroids(nv.ptr(col_off), nv.ptr(row), nv.ptr(val), n_item, n, nv.ptr(label), k, nv.ptr(Ct), nv.ptr(counts),
-                                               nv.stream_handle()), 'ure_csr_kmeans_centroids')
-    return Ct, counts
+    return engine.csr_kmeans_centroids(*_csr_cols(col_off, row, val, label, k), k)
 
 
 @csr_kmeans_centroids.register_fake
