@@ -156,6 +156,30 @@ typedef struct ure_shard {
      * each, the first n_split <= n_multi of them ("split": >= 384) one per 256 slots of the step -- their partial sums are
      * added in a fixed order by a second launch.  n_multi <= 256.  Any values are correct; they only place the work.     */
     int32_t n_split;
+    /* Optimizer of the shard (every shard of a job the same).  The fields from here on were APPENDED to the descriptor and a zeroed
+     * tail is the optimizer the library has always run, so URE_ABI_VERSION did not move: no entry point was added, removed or
+     * changed, a caller that zeroes the descriptor and fills the fields above trains exactly as before, and the only caller that
+     * lays the struct out by hand -- the ctypes mirror, ultrare_amd/_native.py -- is tied to this header by the source hash
+     * (ure_source_hash), which rebuilds the library whenever the two could disagree.
+     * 0: SGD with momentum (scratch.py:64-69), as above.
+     * 1: Adam as torch.optim.Adam(weight_decay = lam) runs it (L2 term added to the gradient, dense over all rows, no amsgrad):
+     *      g  = acc + lam*w
+     *      m' = m + c1*(g - m)                     c1 = 1 - beta1
+     *      v' = beta2*v + (c2*g)*g                 c2 = 1 - beta2
+     *      w' = w - s1[t] * ( m' / ( sqrt(v')/s2[t] + eps ) )
+     *    every operation a float32 operation rounded on its own (no fused multiply-add), c1 and c2 float32 differences.  mU / mV
+     *    hold the first moment.  Rows without interactions have no closed form under Adam: they are streamed every step, so an Adam
+     *    shard has lazy_rows = 0, touch_mode = 0 and full snapshots (snapU / snapV) only; lr is not read (s1 carries it).  */
+    int32_t optimizer;
+    float   beta1, beta2;   /* in [0, 1)                                             */
+    float   eps;            /* > 0                                                   */
+    float *vU;              /* [n_user][d] second moment, zero before step 0         */
+    float *vV;              /* [n_item][d]                                           */
+    const float *opt_sc;    /* [epochs * ceil(N/B)][2] device: step t's scalars s1[t] = lr(epoch of t) / (1 - beta1^(t+1)) and
+                             * s2[t] = sqrt(1 - beta2^(t+1)), computed by the caller in double and rounded to float32 once */
+    /* Reserved, zero.  Keeps the descriptor's size -- the stride of the job's descriptor array -- a multiple of 128 bytes (384);
+     * nothing reads it, later fields go here, and it can be reclaimed.                                                       */
+    int64_t reserved_[7];
 } ure_shard_t;
 
 typedef struct ure_job ure_job_t;   /* a set of shards trained side by side */

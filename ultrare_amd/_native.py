@@ -33,6 +33,9 @@ class UreShard(ctypes.Structure):
         ('lam', ctypes.c_float), ('mu', ctypes.c_float),
         ('touch_mode', _i32), ('n_multi', _i32),
         ('file_tags', _vp), ('n_split', _i32),
+        ('optimizer', _i32), ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float),
+        ('vU', _vp), ('vV', _vp), ('opt_sc', _vp),
+        ('reserved_', _i64 * 7),
     ]
 
 

@@ -6,6 +6,7 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
   D2  dis_type = 'nor', attr = []            (set here; Scratch needs them)
   D5  data / result roots are configurable   ($ULTRARE_DATA_DIR, $ULTRARE_SAVE_DIR, default ./data, ./result)
   +   InsParam(..., k=16, parallel=False)    optional embedding width and shard-parallel mode
+  +   InsParam(..., optimizer='sgd', lr=None) optional optimizer ('adam': engine.TrainJob) and learning rate (None: 0.001)
   +   dataset 'toy' is usable end to end     (the reference only has its batch size)
 """
 import os
@@ -30,7 +31,7 @@ DATASETS = {
 
 class InsParam(object):
     def __init__(self, dataset='toy', epochs=50, n_worker=24, layers=[32], n_group=2, del_per=2, del_type='test',
-                 k=16, parallel=False, data_dir=None):
+                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None):
         # model param
         self.k = k  # dimension of embedding (config.py:19 hard-codes 16)
         self.lam = 0.1  # regularization coefficient
@@ -40,7 +41,7 @@ class InsParam(object):
         self.seed = 42
         self.n_worker = n_worker
         self.batch = 3000 if dataset == 'toy' else 30000
-        self.lr = 0.001
+        self.lr = 0.001 if lr is None else float(lr)
         self.lr_decay = 0.95
         self.momentum = 0.9
         self.epochs = epochs
@@ -48,6 +49,11 @@ class InsParam(object):
         self.dis_type = 'nor'   # D2
         self.attr = []          # D2
         self.parallel = parallel
+        if optimizer not in ('sgd', 'adam'):
+            raise ValueError(f"optimizer {optimizer!r}: 'sgd' or 'adam'")
+        self.optimizer = optimizer  # 'adam': momentum is not used; betas / eps are torch.optim.Adam's defaults
+        self.betas = (0.9, 0.999)
+        self.eps = 1e-8
 
         # dataset-varied param
         self.del_rating = []  # 2d array/list [[uid, iid], ...]

@@ -35,6 +35,24 @@ static bool snapshot_set_ok(const ure_shard_t &S)
     return !(S.snapU || S.snapV || S.snap) || ((full || compact) && (!S.lazy_rows || S.snap_a));
 }
 
+// The optimizer (struct ure_shard: optimizer): every shard of a job the same.  Adam has no closed form for rows without interactions, so
+// nothing that rests on one goes with it.  Why shard k may not have what it asks for, or nullptr.
+static const char *optimizer_refusal(const ure_shard_t *shards, int k)
+{
+    const ure_shard_t &S = shards[k];
+    if (S.optimizer != 0 && S.optimizer != 1) return "optimizer is 0 (SGD with momentum) or 1 (Adam)";
+    if (S.optimizer != shards[0].optimizer) return "every shard of a job must ask for the same optimizer";
+    if (S.optimizer == 0) return nullptr;
+    if (!S.vU || !S.vV) return "Adam needs the second-moment tables vU and vV";
+    if (!S.opt_sc) return "Adam needs the per-step scalars opt_sc";
+    if (!(S.beta1 >= 0.f && S.beta1 < 1.f) || !(S.beta2 >= 0.f && S.beta2 < 1.f)) return "Adam needs beta1 and beta2 in [0, 1)";
+    if (!(S.eps > 0.f)) return "Adam needs eps > 0";
+    if (S.touch_mode) return "Adam does not go with touch_mode (rows between their own steps have no closed form)";
+    if (S.snap) return "Adam does not go with compact snapshots (snap): full ones, snapU + snapV";
+    if (S.lazy_rows) return "Adam does not go with lazy_rows (rows without interactions have no closed form: they are streamed every step)";
+    return nullptr;
+}
+
 // touch mode: all shards of the job or none, all in the same mode and on the same optimizer schedule (one closed-form table per job).
 // Why shard k may not have it, or nullptr; `steps` = its steps per epoch (valid descriptors only).
 static const char *touch_refusal(const ure_shard_t *shards, int k, int steps)
@@ -56,7 +74,7 @@ static const char *touch_refusal(const ure_shard_t *shards, int k, int steps)
     return nullptr;
 }
 
-// Every check of ure_job_create, in the order its messages have always come: descriptors shard by shard, then snapshot sets, then touch mode.
+// Every check of ure_job_create, in the order its messages have always come: descriptors shard by shard, (the optimizer,) then snapshot sets, then touch mode.
 static int check_shards(const ure_shard_t *shards, int n_shards)
 {
     bool touch = false;
@@ -64,6 +82,8 @@ static int check_shards(const ure_shard_t *shards, int n_shards)
         if (int rc = check_descriptor(shards, k)) return rc;
         touch = touch || shards[k].touch_mode != 0;
     }
+    for (int k = 0; k < n_shards; ++k)
+        if (const char *why = optimizer_refusal(shards, k)) return fail(-1, "ure_job_create: optimizer refused for shard %d: %s", k, why);
     for (int k = 0; k < n_shards; ++k)
         if (!snapshot_set_ok(shards[k])) return fail(-1, "ure_job_create: shard %d has an incomplete snapshot set (full: snapU + snapV; compact: snap with lazy_rows; snap_a with lazy_rows)", k);
     for (int k = 0; k < n_shards && touch; ++k)
@@ -79,6 +99,7 @@ static void plan_job(ure_job *job, const ure_shard_t *shards, int n_shards)
     job->d = shards[0].d;
     if (const char *e = std::getenv("URE_SHARD_FAST")) { job->shard_fast = e[0] != '0'; job->shard_sliced = e[0] == '2'; }
     if (const char *e = std::getenv("URE_INDEX_STAGED")) job->scatter_staged = e[0] != '0';
+    job->adam = shards[0].optimizer == 1;
     job->ahead = shards[0].touch_mode == 2;
     job->index = shards[0].touch_mode == 3;
     for (int k = 0; k < n_shards; ++k) {

@@ -74,6 +74,16 @@
 #ifndef URE_TOUCH_WAVES
 #define URE_TOUCH_WAVES 4     // touch mode (mf_touch.h)
 #endif
+// Adam (mf_adam_step_kernel): the owner also holds its second-moment row from the start of the scan, V4 * 4 registers more
+#ifndef URE_ADAM_WAVES_NARROW
+#define URE_ADAM_WAVES_NARROW 6
+#endif
+#ifndef URE_ADAM_WAVES_SMALL
+#define URE_ADAM_WAVES_SMALL 5    // d <= 16
+#endif
+#ifndef URE_ADAM_WAVES_WIDE
+#define URE_ADAM_WAVES_WIDE 4
+#endif
 #ifndef URE_TOUCH_KGB
 #define URE_TOUCH_KGB 4       // rows a lane group gathers together in touch mode
 #endif
@@ -93,6 +103,8 @@ __host__ __device__ constexpr int lanes_per_row(int d) { return d <= URE_NARROW_
 __host__ __device__ constexpr int step_kgb(int lpr, int v4) { return v4 > 1 ? URE_KGB_WIDE : lpr >= 8 ? URE_KGB_NARROW : lpr == 4 ? URE_KGB_D16 : URE_KGB_D8; }
 __host__ __device__ constexpr int step_waves(int lpr, int v4) { return v4 > 1 ? URE_WAVES_WIDE : lpr >= 8 ? URE_WAVES_NARROW : lpr == 4 ? URE_WAVES_D16 : URE_WAVES_D8; }
 
+__host__ __device__ constexpr int adam_waves(int lpr, int v4) { return v4 > 1 ? URE_ADAM_WAVES_WIDE : lpr >= 8 ? URE_ADAM_WAVES_NARROW : URE_ADAM_WAVES_SMALL; }
+
 __device__ __forceinline__ int shard_steps(const ure_shard_t &S) { return (S.N + S.batch - 1) / S.batch; }
 
 #ifdef URE_TIMELINE
@@ -106,11 +118,60 @@ __device__ long long *g_timeline = nullptr;
         const size_t lin_ = (size_t)blockIdx.y * gridDim.x + blockIdx.x;                                      \
         if (g_timeline && threadIdx.x == 0 && lin_ < 16384) g_timeline[((size_t)(tick & 15) * 16384 + lin_) * 8 + (i)] = wall_clock64(); \
     } while (0)
+// a step kernel's own start and end (values 0 and 1 of its workgroup)
+__device__ __forceinline__ void timeline_close(long long t0, int64_t tick)
+{
+    __syncthreads();
+    if (g_timeline && threadIdx.x == 0) {
+        const size_t lin = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+        if (lin < 16384) {
+            long long *e = g_timeline + ((size_t)(tick & 15) * 16384 + lin) * 8;
+            e[0] = t0;
+            e[1] = wall_clock64();
+        }
+    }
+}
 #else
 #define URE_STAMP(i)
 #endif
 
+// torch.optim.Adam (weight_decay = lam: L2 in the gradient; no amsgrad) on one row slice, as include/ultrare_hip.h states it
+// (struct ure_shard: optimizer): every operation rounded on its own and no fmaf, so that numpy float32 restates it bit for bit
+// (ultrare_amd/adam.py: adam_update_ref).  s1 = lr / (1 - beta1^(t+1)), s2 = sqrt(1 - beta2^(t+1)) of this step.  Writes both
+// moments and the step-(t+1) weights.  There is no first-step case: the moments start at zero.
+struct AdamScalars {
+    float lam, c1, b2, c2, s1, s2, eps;
+};
+__device__ __forceinline__ float adam_element(float w, float acc, float &m, float &v, const AdamScalars &k)
+{
+    const float g = __fadd_rn(acc, __fmul_rn(k.lam, w));
+    m = __fadd_rn(m, __fmul_rn(k.c1, __fsub_rn(g, m)));
+    v = __fadd_rn(__fmul_rn(k.b2, v), __fmul_rn(__fmul_rn(k.c2, g), g));
+    // (sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the intrinsic is the native 1-ulp square root; sqrtf and the division
+    // are correctly rounded in this build -- hipcc's default for float32, and no fast-math flag)
+    const float den = __fadd_rn(__fdiv_rn(sqrtf(v), k.s2), k.eps);
+    return __fsub_rn(w, __fmul_rn(k.s1, __fdiv_rn(m, den)));
+}
 template <int LPR, int V4>
+__device__ __forceinline__ void adam_update(const RowVec<V4> &wr, RowVec<V4> mr, RowVec<V4> vr, const RowVec<V4> &ar, const AdamScalars &k, int sub,
+                                            float *mom_row, float *var_row, float *next_row)
+{
+    RowVec<V4> nr;
+#pragma unroll
+    for (int i = 0; i < V4; ++i) {
+        const float4 w = wr.q[i], acc = ar.q[i];
+        nr.q[i].x = adam_element(w.x, acc.x, mr.q[i].x, vr.q[i].x, k);
+        nr.q[i].y = adam_element(w.y, acc.y, mr.q[i].y, vr.q[i].y, k);
+        nr.q[i].z = adam_element(w.z, acc.z, mr.q[i].z, vr.q[i].z, k);
+        nr.q[i].w = adam_element(w.w, acc.w, mr.q[i].w, vr.q[i].w, k);
+    }
+    row_store<LPR, V4>(mom_row, sub, mr);
+    row_store<LPR, V4>(var_row, sub, vr);
+    row_store<LPR, V4>(next_row, sub, nr);
+}
+
+// OPT: the optimizer the owners apply (struct ure_shard: optimizer) -- 0 SGD with momentum, 1 Adam.  Everything else is shared.
+template <int LPR, int V4, int OPT = 0>
 __device__ __forceinline__ void mf_step(const ure_shard_t *__restrict__ shards, const shard_aux *__restrict__ aux, int64_t tick, int shard_fast)
 {
     constexpr int D = LPR * V4 * 4;          // row width: LPR lanes x V4 float4 per lane
@@ -165,6 +226,10 @@ __device__ __forceinline__ void mf_step(const ure_shard_t *__restrict__ shards, 
                      "s"(S.lr), "s"(S.sched), "s"(S.units), "s"(S.ent_oid), "s"(S.ent_r), "s"(S.ent_tag), "s"(S.U[0]), "s"(S.U[1]),
                      "s"(S.V[0]), "s"(S.V[1]), "s"(S.mU), "s"(S.mV), "s"(S.sse), "s"(A.steps), "s"(A.inv_steps), "s"(A.ride_m),
                      "s"(A.ride_ab), "s"(A.ride_c), "s"(A.ranges), "s"(A.derive_blocks));
+        if constexpr (OPT == 1) {
+            const float p_b1 = S.beta1, p_b2 = S.beta2, p_eps = S.eps;
+            asm volatile("" ::"s"(p_b1), "s"(p_b2), "s"(p_eps), "s"(S.vU), "s"(S.vV), "s"(S.opt_sc));
+        }
     }
     const int steps = A.steps;
     if (tick >= (int64_t)steps * S.epochs) return;
@@ -252,6 +317,16 @@ __device__ __forceinline__ void mf_step(const ure_shard_t *__restrict__ shards, 
     }
     // the momentum row is requested together with the weights: its latency hides behind the scan and the gathers
     // instead of forming a memory level of its own in front of the update (bench: 12.6 -> 12.5 us per launch)
+    [[maybe_unused]] Row v2 = w;
+    [[maybe_unused]] float2 sc = make_float2(0.f, 1.f);
+    if constexpr (OPT == 1) {
+        // Adam: both moment rows, and the step's two scalars (the shard's own step t is the job's tick)
+        if (owner) {
+            m4 = row_load<LPR, V4>((is_user ? S.mU : S.mV) + row_off, sub);
+            v2 = row_load<LPR, V4>((is_user ? S.vU : S.vV) + row_off, sub);
+            sc = make_float2(ldg(S.opt_sc + 2 * tick), ldg(S.opt_sc + 2 * tick + 1));
+        }
+    } else
     if (owner && !first) m4 = row_load<LPR, V4>((is_user ? S.mU : S.mV) + row_off, sub);
     // compact end-of-epoch snapshots written by the owners themselves (every active row is rewritten in every step, so the
     // last step of an epoch writes them all): the row's place in the snapshot is requested here, with the row
@@ -366,6 +441,12 @@ __device__ __forceinline__ void mf_step(const ure_shard_t *__restrict__ shards, 
         }
     }
     if (owner) {
+        if constexpr (OPT == 1) {
+            const float b1 = S.beta1, b2 = S.beta2;
+            const AdamScalars k = {lam, __fsub_rn(1.0f, b1), b2, __fsub_rn(1.0f, b2), sc.x, sc.y, S.eps};
+            adam_update<LPR, V4>(w, m4, v2, acc, k, sub, (is_user ? S.mU : S.mV) + row_off, (is_user ? S.vU : S.vV) + row_off,
+                                 (is_user ? S.U[cur ^ 1] : S.V[cur ^ 1]) + row_off);      // (no compact snapshots: ure_job_create refuses them)
+        } else
         sgd_update(w, m4, acc, (is_user ? S.mU : S.mV) + row_off, (is_user ? S.U[cur ^ 1] : S.V[cur ^ 1]) + row_off,
                    snap_slot >= 0 ? S.snap + ((size_t)epoch * S.n_active + snap_slot) * D : nullptr);
         // train loss (utils.py:82): each user row adds its own squared errors to its own slot of
@@ -385,15 +466,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(step_wav
 #endif
     mf_step<LPR, V4>(shards, aux, tick, shard_fast);
 #ifdef URE_TIMELINE
-    __syncthreads();
-    if (g_timeline && threadIdx.x == 0) {
-        const size_t lin = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        if (lin < 16384) {
-            long long *e = g_timeline + ((size_t)(tick & 15) * 16384 + lin) * 8;
-            e[0] = t0;
-            e[1] = wall_clock64();
-        }
-    }
+    timeline_close(t0, tick);
+#endif
+}
+
+// The same step with Adam's update (struct ure_shard: optimizer = 1); a kernel of its own so that its register budget is its own
+template <int LPR, int V4>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(adam_waves(LPR, V4)))) void mf_adam_step_kernel(const ure_shard_t *__restrict__ shards, const shard_aux *__restrict__ aux, int64_t tick, int shard_fast)
+{
+#ifdef URE_TIMELINE
+    const long long t0 = wall_clock64();
+#endif
+    mf_step<LPR, V4, 1>(shards, aux, tick, shard_fast);
+#ifdef URE_TIMELINE
+    timeline_close(t0, tick);
 #endif
 }
 
@@ -703,6 +789,10 @@ static void launch_step(const ure_job *job, int64_t tick, hipStream_t st)
     }
     if (job->touch) {
         hipLaunchKernelGGL((mf_touch_step_kernel<LPR, V4>), grid, dim3(kBlock), 0, st, job->dev, job->dev_aux, tick, shard_fast);
+        return;
+    }
+    if (job->adam) {
+        hipLaunchKernelGGL((mf_adam_step_kernel<LPR, V4>), grid, dim3(kBlock), 0, st, job->dev, job->dev_aux, tick, shard_fast);
         return;
     }
     hipLaunchKernelGGL((mf_step_kernel<LPR, V4>), grid, dim3(kBlock), 0, st, job->dev, job->dev_aux, tick, shard_fast);

@@ -62,6 +62,7 @@ struct ure_job {
     bool snapshots = false;
     unsigned snap_blocks = 1;
     int64_t max_lazy = 0;                              // float4 slices of lazily advanced rows, max over shards
+    bool adam = false;                                 // struct ure_shard: optimizer = 1 (mf_adam_step_kernel): all shards of the job or none
     bool touch = false;                                // touch mode (mf_touch.h): all shards of the job or none
     bool ahead = false;                                // touch_mode 2 (masks one epoch ahead): all shards of the job or none
     bool index = false;                                // touch_mode 3 (per-step slot index, mf_index.h): all shards of the job or none

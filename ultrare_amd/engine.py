@@ -11,7 +11,7 @@ HBM layout of one shard:
   file_tag[N] u16          scratch: batch of interaction j in the epoch being prepared
   sched[n_user+n_item][4] i32   {row id, first slot, end slot, nnz}, heaviest row first
   units[n_units][4] i32    work units of the step kernel for one table width (ShardData.units(d))
-  U[2][n_user][d] V[2][n_item][d] f32 ping-pong weights ; mU, mV momentum
+  U[2][n_user][d] V[2][n_item][d] f32 ping-pong weights ; mU, mV momentum (Adam: first moment; vU, vV second moment)
   perm[epochs][N] i32 ; lr[epochs] f32 ; sse[epochs][n_user] f32 (per-user squared error)
 """
 import contextlib
@@ -420,15 +420,17 @@ def touch_plan(steps_max, d, batch, live_bytes, lazy_rows, snapshots, touch, fin
     return 1
 
 
-def shard_regions(n_user, n_item, n_active, d, epochs, lazy_rows, snapshots, at=0, snap_at=0):
+def shard_regions(n_user, n_item, n_active, d, epochs, lazy_rows, snapshots, at=0, snap_at=0, *, adam=False):
     """Where one shard's tables live in a job's two device pools: -> (pool, snap, end, snap_end), pool and snap dicts name -> (first float,
     floats, view shape); the shard starts at `at` / `snap_at` (multiples of 64), the next one at end / snap_end.  The float pool: U and V
     (both buffers), mU, mV, sse and -- lazy_rows -- the start tables U0, V0, each rounded up to 64 floats.  The snapshot pool: snapU and
-    straight after it snapV ('full') or snap ('compact': the n_active rows), the shard's snapshots as a whole rounded up to 64 floats."""
+    straight after it snapV ('full') or snap ('compact': the n_active rows), the shard's snapshots as a whole rounded up to 64 floats.
+    adam: the second moments vU, vV follow V0 (no other region moves)."""
     al = lambda x: (x + 63) // 64 * 64
     pool, snap, E = {}, {}, epochs
     for name, shape in (('U', (2, n_user, d)), ('V', (2, n_item, d)), ('mU', (n_user, d)), ('mV', (n_item, d)), ('sse', (E, n_user)),
-                        ('U0', (n_user if lazy_rows else 0, d)), ('V0', (n_item if lazy_rows else 0, d))):
+                        ('U0', (n_user if lazy_rows else 0, d)), ('V0', (n_item if lazy_rows else 0, d))) + \
+                       ((('vU', (n_user, d)), ('vV', (n_item, d))) if adam else ()):
         pool[name] = (at, math.prod(shape), shape)
         at += al(math.prod(shape))
     for name, shape in {'full': (('snapU', (E, n_user, d)), ('snapV', (E, n_item, d))), 'compact': (('snap', (E, n_active, d)),)}.get(snapshots, ()):
@@ -474,10 +476,28 @@ class TrainJob:
     """
 
     def __init__(self, shards, inits, perms, k, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50, lazy_rows=None, snapshots=False,
-                 touch=None, final_only=False, epoch_reads=False):
+                 touch=None, final_only=False, epoch_reads=False, *, optimizer='sgd', betas=(0.9, 0.999), eps=1e-8):
         """touch: None = the auto rule (touch mode when the job's live rows exceed the Infinity Cache AND the caller reads the tables
         at epoch ends only (epoch_reads) or after the last epoch only (final_only): a job in touch mode cannot be read inside an
-        epoch), True / False, or 'index' (touch_mode 3 whatever the epoch length)."""
+        epoch), True / False, or 'index' (touch_mode 3 whatever the epoch length).
+        optimizer: 'sgd' (momentum, the reference's) or 'adam' (ultrare_amd/adam.py; betas, eps: its parameters, taken at their float32
+        values; `momentum` is not used).  Rows without interactions have no closed form under Adam: the job streams them every step
+        (lazy_rows False, no touch mode -- asking for either raises ValueError) and its snapshots are full ones."""
+        if optimizer not in ('sgd', 'adam'):
+            raise ValueError(f"optimizer {optimizer!r}: 'sgd' or 'adam'")
+        self.optimizer = optimizer
+        if optimizer == 'adam':
+            from . import adam
+            if lazy_rows:
+                raise ValueError("optimizer='adam' has no closed form for rows without interactions: lazy_rows must be False or None")
+            if touch:
+                raise ValueError("optimizer='adam' does not run in touch mode: touch must be False or None")
+            self._beta1, self._beta2, self._eps = adam.betas32(betas, eps)
+            if not (0.0 <= self._beta1 < 1.0 and 0.0 <= self._beta2 < 1.0):
+                raise ValueError(f'betas {tuple(betas)!r} must lie in [0, 1)')
+            if not self._eps > 0.0:
+                raise ValueError(f'eps {eps!r} must be positive (as a float32)')
+            lazy_rows, touch = False, False
         assert len(shards) == len(inits) == len(perms) and len(shards) > 0
         self.shards, self.k, self.d = shards, int(k), pad_dim(int(k))
         self.batch, self.epochs, self.device = int(batch), int(epochs), shards[0].device
@@ -495,10 +515,18 @@ class TrainJob:
         # end-of-epoch snapshots: 'compact' keeps the n_active rows with interactions only (every other row is a_e * w0 and is
         # rebuilt where it is read: ure_eval_series_compact; needs lazy_rows), True / 'full' keeps complete tables
         self.snapshots = ('compact' if self.lazy_rows else 'full') if snapshots == 'compact' else ('full' if snapshots else False)
-        small = [self._lr_host] + ([closed_form_scalars(self._lr_host, st_, float(np.float32(lam)), float(np.float32(momentum))) for st_ in self._steps]
-                                   if self.snapshots else [])
-        self._small = upload_many(small, self.device)          # the learning rates and every shard's closed-form scalars: one copy
+        # the small arrays of the job in one copy: the learning rates, then per shard the closed-form scalars its snapshots need
+        # (lazy rows: SGD only) or its per-step Adam scalars (struct ure_shard: opt_sc)
+        if optimizer == 'adam':
+            per_shard = [adam.adam_scalars(self._lr_host, st_, self._beta1, self._beta2) for st_ in self._steps]
+        elif self.snapshots:
+            per_shard = [closed_form_scalars(self._lr_host, st_, float(np.float32(lam)), float(np.float32(momentum))) for st_ in self._steps]
+        else:
+            per_shard = []
+        self._small = upload_many([self._lr_host] + per_shard, self.device)
         self.lr = self._small[0]
+        self._opt_sc = self._small[1:] if optimizer == 'adam' else None
+        self._snap_a = self._small[1:] if optimizer == 'sgd' and self.snapshots else None
         self._arrivals = []      # the rng.Arrival of every order that has one: run() waits for their chunks, check_tags() reads their flags
         self.wait_marks = None   # a list: run() adds an event pair around each wait of its stream for a chunk (bench.py)
         self._descs = (nv.UreShard * len(shards))()
@@ -532,7 +560,8 @@ class TrainJob:
         request does after its launches are queued."""
         self._regions, at, snap_at = [], 0, 0                        # per shard: (regions in _pool, regions in _snap_pool)
         for sh in self.shards:
-            pool, snap, at, snap_at = shard_regions(sh.n_user, sh.n_item, sh.n_active, self.d, self.epochs, self.lazy_rows, self.snapshots, at, snap_at)
+            pool, snap, at, snap_at = shard_regions(sh.n_user, sh.n_item, sh.n_active, self.d, self.epochs, self.lazy_rows, self.snapshots, at, snap_at,
+                                                    adam=self.optimizer == 'adam')
             self._regions.append((pool, snap))
         self._pool = torch.zeros(at, dtype=torch.float32, device=self.device)
         self._snap_pool = torch.empty(snap_at, dtype=torch.float32, device=self.device) if self.snapshots else None
@@ -602,13 +631,17 @@ class TrainJob:
         D.N, D.n_user, D.n_item, D.d, D.n_active, D.n_slots = sh.N, sh.n_user, sh.n_item, d, sh.n_active, sh.n_slots
         D.batch, D.epochs, D.lam, D.mu, D.touch_mode = self.batch, self.epochs, self._lam, self._mu, self.touch_mode
         if self.snapshots:
-            D.snap_a = self._small[1 + s].data_ptr()
+            if self._snap_a is not None:
+                D.snap_a = self._snap_a[s].data_ptr()
             if self.snapshots == 'compact':
                 D.snap, D.row_slot = self._addr(s, 'snap'), sh.ptr('_row_slot')
             else:
                 D.snapU, D.snapV = self._addr(s, 'snapU'), self._addr(s, 'snapV')
         if self.lazy_rows:
             D.U0, D.V0, D.lr_host, D.lazy_rows = self._addr(s, 'U0'), self._addr(s, 'V0'), self._lr_host.ctypes.data, 1
+        if self.optimizer == 'adam':
+            D.optimizer, D.beta1, D.beta2, D.eps = 1, self._beta1, self._beta2, self._eps
+            D.vU, D.vV, D.opt_sc = self._addr(s, 'vU'), self._addr(s, 'vV'), self._opt_sc[s].data_ptr()
 
     def _copy_start_tables(self):
         """The start tables into buffer 0 (and the closed form's copy), every shard's in one launch."""
@@ -626,8 +659,8 @@ class TrainJob:
             for name, (first, n, shape) in regions.items():
                 if n:                                   # (without lazy_rows a job keeps no U0, V0)
                     st[name] = mem[first:first + n].view(shape)
-        if self.snapshots:
-            st['snap_a'] = self._small[1 + s]
+        if self._snap_a is not None:
+            st['snap_a'] = self._snap_a[s]
         return st
 
     @property
@@ -797,7 +830,7 @@ class TrainJob:
                 self.check_tags()                 # (ure_job_destroy has waited for the device)
             finally:
                 # the device memory goes back now: tables, snapshots, batch tags and what made them
-                self._pool = self._snap_pool = self._small = None
+                self._pool = self._snap_pool = self._small = self._opt_sc = self._snap_a = None
                 self._perms, self._arrivals = [], []
                 if isinstance(getattr(self, 'state', None), _States):
                     self.state._got.clear()

@@ -16,6 +16,9 @@ Same flags, defaults and assertions; additions are optional:
                  the sparse rating matrix (csrc/csr_group.hip, DESIGN 4.17), which needs no user matrix of an earlier --group 0 run;
                  'rating-bkmeans': the balanced k-means the reference compares OT grouping against, on the same sparse matrix
                  (csrc/csr_kmeans.hip).  Plain 'rating-kmeans' stays with Group.grouping: its shards are not balanced
+  --optimizer    'sgd' (default: the reference's SGD with momentum 0.9) or 'adam' (torch.optim.Adam with weight_decay, fused into the step
+                 kernel: DESIGN 4.21) -- the one that trains wide tables (--k 128) the reference's summed-loss SGD diverges on
+  --lr           learning rate (default 0.001, config.py:27)
   --data-dir / --save-dir   roots of data/ and result/ (default: ./data, ./result)
 """
 import argparse
@@ -34,6 +37,8 @@ parser.add_argument('--deltype', type=str, default='rand', help='deletion type')
 parser.add_argument('--k', type=int, default=16, help='embedding width')
 parser.add_argument('--parallel', type=int, default=1, help='1 (default): shards side by side / across GPUs; 0: one after the other')
 parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', 'rating-ot' (OT groups) or 'rating-bkmeans' (balanced k-means groups) on the sparse rating matrix, no --group 0 run needed")
+parser.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adam'], help="'sgd' (reference) or 'adam'")
+parser.add_argument('--lr', type=float, default=None, help='learning rate (default 0.001)')
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -71,7 +76,7 @@ def main(argv=None):
 
     torch.manual_seed(42)   # the reference never seeds the CPU generator; a fixed run needs it
     param = InsParam(args.dataset, args.epoch, args.worker, args.layer, args.group, args.delper, args.deltype,
-                     k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir)
+                     k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr)
     ins = Instance(param, save_dir=args.save_dir)
 
     if args.group == 0:

@@ -94,6 +94,12 @@ class Scratch(object):
         self.momentum = param.momentum
         self.epochs = param.epochs
         self.batch = getattr(param, 'batch', 30000)
+        # the optimizer of every training job this object makes: 'sgd' (the reference's, scratch.py:64-69) or 'adam' (engine.TrainJob)
+        self.optimizer = getattr(param, 'optimizer', 'sgd')
+        if self.optimizer not in ('sgd', 'adam'):
+            raise ValueError(f"optimizer {self.optimizer!r}: 'sgd' or 'adam'")
+        self.betas = tuple(getattr(param, 'betas', (0.9, 0.999)))
+        self.eps = getattr(param, 'eps', 1e-8)
         self.device = 'cuda'
         # InsParam never sets dis_type / attr; 'nor' is the only branch that
         # works with MF (utils.py:64-65)
@@ -117,6 +123,14 @@ class Scratch(object):
         self.loss_fn = nn.MSELoss(reduction='sum')
         self.is_rmse = True
 
+    def _optimizer_args(self):
+        """What a TrainJob of this object takes beyond the reference's parameters."""
+        return dict(optimizer=self.optimizer, betas=self.betas, eps=self.eps)
+
+    def _snap_mode(self):
+        """The end-of-epoch snapshots its jobs keep: compact ones need the closed form of lazy rows, which Adam has not."""
+        return 'compact' if engine.LAZY_ROWS and self.optimizer == 'sgd' else 'full'
+
     def _models_before(self):
         return list(getattr(self, 'model_list', [])) if self.__class__.__name__ == 'Sisa' else []
 
@@ -134,10 +148,11 @@ class Scratch(object):
         # on the device (snapshots) and the two test series of scratch.py:83-97 are computed afterwards
         # in four launches each (ure_eval_series); otherwise each epoch synchronises to print
         queued = verbose == 0
-        snap_mode = 'compact' if engine.LAZY_ROWS else 'full'
+        snap_mode = self._snap_mode()
         series = queued and engine.TrainJob.snapshot_bytes([shard], self.epochs, self.k, snap_mode) <= snapshot_limit()
         job = engine.TrainJob([shard], [init], [perms], self.k, batch, self.epochs, self.lr, self.lam, self.momentum,
-                              self.lr_decay, snapshots=snap_mode if series else False, final_only=series, epoch_reads=True)       # (tables are read at epoch ends only)
+                              self.lr_decay, snapshots=snap_mode if series else False, final_only=series, epoch_reads=True,       # (tables are read at epoch ends only)
+                              **self._optimizer_args())
         rng.release(perms)                                  # uploaded: the host buffer goes back to the pool
         test_ev = as_loader(test_data).eval_set()
         total_ev = as_loader(test_total).eval_set() if has_total else None

@@ -308,7 +308,7 @@ class Sisa(Scratch):
         want_full = bool(dist) and (self.epoch_logs or len(save_dir) > 0)          # (the same on every rank: it sizes the collective)
         prepared = prepare_owned(ids, owner, rank, train_dlist, self.n_user, self.n_item, self.k, self.epochs)
         mine = [i for pos, i in enumerate(ids) if owner[pos] == rank]
-        snap_mode = 'compact' if engine.LAZY_ROWS else 'full'
+        snap_mode = self._snap_mode()
         snap_bytes = engine.TrainJob.snapshot_bytes([prepared[i][0] for i in mine], self.epochs, self.k, snap_mode)
         keep_logs = self.epoch_logs and snap_bytes <= snapshot_limit()
         if self.epoch_logs and not keep_logs:
@@ -321,7 +321,7 @@ class Sisa(Scratch):
             job = engine.TrainJob([prepared[i][0] for i in mine], [prepared[i][1] for i in mine],
                                   [prepared[i][2] for i in mine], self.k, batch, self.epochs, self.lr, self.lam,
                                   self.momentum, self.lr_decay, snapshots=snap_mode if keep_logs else False,
-                                  final_only=True)       # (the tables are read once, after the last epoch)
+                                  final_only=True, **self._optimizer_args())       # (the tables are read once, after the last epoch)
             from .. import rng
             engine.mark('job_created')
             job.run()
