@@ -328,7 +328,7 @@ MEMBER_SIZES = [1, 31, 32, 33, 63, 64, 65, 97, 1000]
 
 
 def _member_lists(label, k):
-    """order / off as utils._ot_round builds them: a stable argsort of the labels, the cumulative bincount."""
+    """order / off as utils._dense_rows builds them: a stable argsort of the labels, the cumulative bincount."""
     order = np.argsort(label.astype(np.uint8), kind='stable').astype(np.int32)
     off = np.concatenate([[0], np.cumsum(np.bincount(label, minlength=k))]).astype(np.int64)
     return order, off

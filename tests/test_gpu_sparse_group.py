@@ -353,6 +353,47 @@ def test_timing_is_served_for_sparse_input(toy):
     assert all(v >= 0 for t in exact + sink for v in t.values())
 
 
+DENSE_EXACT_PARTS = ['centroid_upload_ms', 'cost_kernel_ms', 'device_potentials_ms', 'cost_to_host_ms', 'host_solver_ms', 'centroids_ms']
+DENSE_SINKHORN_PARTS = ['centroid_upload_ms', 'cost_kernel_ms', 'device_sinkhorn_ms', 'centroids_ms']
+
+
+def small_dense():
+    return np.random.RandomState(0).standard_normal((96, 5)).astype(np.float32)
+
+
+def test_timing_is_served_for_dense_input():
+    """The parts bench.py's OT leg reads, in order, and the same list with the Sinkhorn part in place of the exact solver's
+    three.  reg = the median of the first round's cost matrix, as in the wiring test above."""
+    from ultrare_amd.method.utils import ot_cluster
+    X, k = small_dense(), 3
+    exact, sink = [], []
+    np.random.seed(0)
+    ot_cluster(X, k, max_iters=2, timing=exact)
+    assert 1 <= len(exact) <= 2
+    assert all(list(t) == DENSE_EXACT_PARTS for t in exact)
+    np.random.seed(0)
+    first = X[np.random.choice(len(X), size=k, replace=False)]
+    reg = float(np.median(((X - first[:, np.newaxis]) ** 2).sum(axis=2)))
+    np.random.seed(0)
+    ot_cluster(X, k, max_iters=1, timing=sink, solver='sinkhorn', reg=reg)
+    assert len(sink) == 1 and list(sink[0]) == DENSE_SINKHORN_PARTS
+    assert all(v >= 0 for t in exact + sink for v in t.values())
+
+
+@pytest.mark.parametrize('rows', ['dense', 'csr'])
+def test_timing_does_not_change_the_answer(rows):
+    from scipy import sparse
+    from ultrare_amd.method.utils import ot_cluster
+    X = small_dense()
+    if rows == 'csr':
+        X = sparse.csr_matrix(X * (X > 0.5))
+    np.random.seed(0)
+    inertia, label = ot_cluster(X, 3)
+    np.random.seed(0)
+    timed_inertia, timed_label = ot_cluster(X, 3, timing=[])
+    assert np.array_equal(label, timed_label) and float(inertia) == float(timed_inertia)
+
+
 # ---- 7. the torch ops ------------------------------------------------------------------------------------------------------------
 def test_torch_ops_equal_the_engine_calls(mats):
     from ultrare_amd import _native as nv

@@ -40,6 +40,7 @@ from .. import engine
 from ..combine import Combiner, check_fit_args, first_group_map, mean_weights, newton_fit
 from ..read import as_loader
 from ..rng import seed_all  # noqa: F401  (re-exported under the reference's name)
+from ..sparse_group import Compressed, check_cluster_args, dense_rows
 
 STD = 1
 OT_WARM_ITERS = 400      # dual-ascent steps that warm-start the exact OT solver (ure_ot_potentials) at large n
@@ -406,217 +407,177 @@ def timefn(fn):
     return measure_time
 
 
-def _ot_round(Xd, centroid, n, k, d, dist_d, label_d, cent_d, counts_d, pi=None, mfma_check=None, timing=None):
-    """One round of utils.py:637-648 on the device + the exact host LP.  mfma_check (a list): the round is also
-    solved on the MFMA form of the cost matrix (ure_ot_cost_mfma) and the number of labels that differ from the
-    exact path's is appended -- the cross-check that form needs before anyone may rely on it.
-    timing (a list): the round's parts are timed on the host's clock with a synchronisation between them (bench.py's OT leg) and
-    appended as a dict of milliseconds."""
-    L, st = nv.lib(), nv.stream_handle()
-    tick = None
-    if timing is not None:
-        marks = []
-
-        def tick(name):
-            torch.cuda.synchronize()
-            marks.append((name, time.perf_counter()))
-        tick('start')
-    cd = torch.from_numpy(np.ascontiguousarray(centroid, dtype=np.float32)).to(Xd.device)
-    fast_label = None
-    if mfma_check is not None:
-        nv.check(L.ure_ot_cost_mfma(nv.ptr(Xd), nv.ptr(cd), n, k, d, nv.ptr(dist_d), st), 'ure_ot_cost_mfma')
-        fpi = np.zeros(k, dtype=np.float64) if pi is None else pi.copy()
-        nv.check(L.ure_ot_potentials(nv.ptr(dist_d), n, k, ot_warm_iters(n), fpi.ctypes.data, None, st), 'ure_ot_potentials')
-        fast_label, _, _, _ = nv.ot_assign_warm(dist_d.cpu().numpy(), fpi, want_plan=False)
-    if tick:
-        tick('centroid_upload')
-    nv.check(L.ure_ot_cost(nv.ptr(Xd), nv.ptr(cd), n, k, d, nv.ptr(dist_d), st), 'ure_ot_cost')
-    if tick:
-        tick('cost_kernel')
-    # cluster potentials by dual ascent on the device (a warm start only: the LP below is solved exactly for any
-    # potentials), while the cost matrix travels to the host
-    pi = np.zeros(k, dtype=np.float64) if pi is None else pi         # in: the previous round's, out: this round's
-    nv.check(L.ure_ot_potentials(nv.ptr(dist_d), n, k, ot_warm_iters(n), pi.ctypes.data, None, st), 'ure_ot_potentials')
-    if tick:
-        tick('device_potentials')
-    dist = dist_d.cpu().numpy()                                       # [k, n] fp32 (synchronises)
-    if tick:
-        tick('cost_to_host')
-    label, _, _, _ = nv.ot_assign_warm(dist, pi, want_plan=False)     # exact EMD + argmax (host)
-    if tick:
-        tick('host_solver')
-    if fast_label is not None:
-        mfma_check.append(int((fast_label != label).sum()))
-    # utils.py:648 from member lists: a stable sort of the labels (ascending id inside a cluster = numpy's order of addition)
-    # (labels as the narrowest unsigned type: numpy's stable sort of 8- and 16-bit keys is a radix sort -- 0.3 ms instead of 3 at n = 162,000)
-    keys = label.astype(np.uint8 if k <= 256 else np.uint16 if k <= 65536 else np.int64)
-    order = torch.from_numpy(np.argsort(keys, kind='stable').astype(np.int32)).to(Xd.device)
-    off = torch.from_numpy(np.concatenate([[0], np.cumsum(np.bincount(label, minlength=k))]).astype(np.int64)).to(Xd.device)
-    nv.check(L.ure_ot_centroids_members(nv.ptr(Xd), nv.ptr(order), nv.ptr(off), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
-             'ure_ot_centroids_members')
-    new_centroid = cent_d.cpu().numpy()
-    if tick:
-        tick('centroids')
-        timing.append({b[0] + '_ms': round((b[1] - a[1]) * 1e3, 4) for a, b in zip(marks[:-1], marks[1:])})
-    return dist, label, new_centroid
-
-
-@timefn
-def ot_cluster(X, k, max_iters=10, timing=None, solver='exact', reg=1e-3, num_iter_max=1000, stop_thr=1e-9):
-    """utils.py:628-656.  Initial centroids come from the global numpy generator, as in
-    the reference.  Returns (inertia, label[int64]).  timing (a list, optional): every round's parts in milliseconds (_ot_round).
-    solver='exact' (the default, the reference's arithmetic: exact EMD) or 'sinkhorn': every round's transport is
-    entropic OT solved on the device (_ot_cluster_sinkhorn), an opt-in that is not bit-parity with the reference; reg,
-    num_iter_max and stop_thr are its settings and are ignored by the exact solver.
-    X may be a SciPy sparse matrix (the ratings): the same rounds then run through the CSR cost and centroid kernels
-    (_ot_cluster_csr) and the n x d array is never formed; dense inputs take the dense kernels as before.  timing is served
-    there for both solvers."""
-    if solver not in ('exact', 'sinkhorn'):
-        raise ValueError(f"solver must be 'exact' or 'sinkhorn', not {solver!r}")
-    if solver == 'sinkhorn':
-        engine.check_sinkhorn_args(reg, num_iter_max, stop_thr)
-    if _is_sparse(X):
-        return _ot_cluster_csr(X, k, max_iters, solver, reg, num_iter_max, stop_thr, timing)
-    X = np.ascontiguousarray(X, dtype=np.float32)
-    n, d = X.shape
-    if k < 1 or k > n:
-        raise ValueError('need 1 <= k <= n clusters')
-    if solver == 'sinkhorn' and k > engine.SINKHORN_MAX_K:
-        raise ValueError(f'the sinkhorn solver takes at most {engine.SINKHORN_MAX_K} clusters, not {k}')
-    centroid = X[np.random.choice(n, size=k, replace=False)]
-    if solver == 'sinkhorn':
-        return _ot_cluster_sinkhorn(X, centroid, k, max_iters, reg, num_iter_max, stop_thr)
-    dev = engine._device()
-    Xd = torch.from_numpy(X).to(dev)
-    dist_d = torch.empty(k, n, dtype=torch.float32, device=dev)
-    label_d = torch.empty(n, dtype=torch.int32, device=dev)
-    cent_d = torch.empty(k, d, dtype=torch.float32, device=dev)
-    counts_d = torch.empty(k, dtype=torch.int32, device=dev)
-    pi = np.zeros(k, dtype=np.float64)
-    # URE_OT_MFMA=1: every round is solved a second time on the MFMA cost matrix and compared (ot_cluster.mfma_mismatches);
-    # the labels returned are always the exact path's
-    check = [] if os.environ.get('URE_OT_MFMA', '0') == '1' else None
-    ot_cluster.mfma_mismatches = check
-    for _ in range(max_iters):
-        dist, label, new_centroid = _ot_round(Xd, centroid, n, k, d, dist_d, label_d, cent_d, counts_d, pi, check, timing)
-        inertia = np.min(dist, axis=0).sum()
-        if np.allclose(centroid, new_centroid):
-            break
-        centroid = new_centroid
-    print(f'{inertia:.3f}', end=' ')
-    return inertia, label.astype(np.int64)
-
-
-def _ot_cluster_sinkhorn(X, centroid, k, max_iters, reg, num_iter_max, stop_thr):
-    """ot_cluster's rounds with entropic OT in place of the exact LP: ure_ot_cost -> ure_ot_sinkhorn (labels = argmax of each
-    point's plan row, and every point's cheapest cost for the inertia) -> a stable sort of the labels -> ure_ot_centroids_members,
-    then utils.py's allclose stop.  Only n labels and n minima come to the host, never the [k, n] matrix.  Every round starts
-    from zero potentials.  ot_cluster.sinkhorn_stats: (iterations, marginal error) of every round."""
-    n, d = X.shape
-    L, st, dev = nv.lib(), nv.stream_handle(), engine._device()
-    Xd = torch.from_numpy(X).to(dev)
-    dist_d = torch.empty(k, n, dtype=torch.float32, device=dev)
-    cent_d = torch.empty(k, d, dtype=torch.float32, device=dev)
-    counts_d = torch.empty(k, dtype=torch.int32, device=dev)
-    stats = []
-    ot_cluster.sinkhorn_stats = stats
-    for rnd in range(max_iters):
-        cd = torch.from_numpy(np.ascontiguousarray(centroid, dtype=np.float32)).to(dev)
-        nv.check(L.ure_ot_cost(nv.ptr(Xd), nv.ptr(cd), n, k, d, nv.ptr(dist_d), st), 'ure_ot_cost')
-        r = engine.ot_sinkhorn(dist_d, reg, num_iter_max, stop_thr, want_u=False, want_cost_min=True)
-        stats.append((r['iters'], r['err']))
-        label = r['label'].cpu().numpy()
-        inertia = r['cost_min'].cpu().numpy().sum()                  # == np.min(dist, axis=0).sum(): the same float32 values and order
-        sizes = np.bincount(label, minlength=k)
-        if (sizes == 0).any():
-            raise ValueError(f'ot_cluster(solver=\'sinkhorn\'): round {rnd}: cluster(s) {np.flatnonzero(sizes == 0).tolist()} received no '
-                             f'point, so their centroid (utils.py:648) is undefined; reg = {reg:g} against costs up to '
-                             f'{float(dist_d.max()):.4g}: a larger reg balances the groups')
-        keys = label.astype(np.uint8 if k <= 256 else np.uint16)
-        order = torch.from_numpy(np.argsort(keys, kind='stable').astype(np.int32)).to(dev)
-        off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
-        nv.check(L.ure_ot_centroids_members(nv.ptr(Xd), nv.ptr(order), nv.ptr(off), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
-                 'ure_ot_centroids_members')
-        new_centroid = cent_d.cpu().numpy()
-        if np.allclose(centroid, new_centroid):
-            break
-        centroid = new_centroid
-    print(f'{inertia:.3f}', end=' ')
-    return inertia, label.astype(np.int64)
-
-
 def _is_sparse(X):
     """A SciPy sparse matrix, or the (csr, csc) pair sparse_group.canonical_csr made of one."""
     import sys
-    from ..sparse_group import Compressed
     if isinstance(X, tuple):
         return len(X) == 2 and all(isinstance(h, Compressed) for h in X)
     sp = sys.modules.get('scipy.sparse')           # (a sparse matrix cannot exist before scipy.sparse was imported)
     return sp is not None and sp.issparse(X)
 
 
-def _ot_cluster_csr(X, k, max_iters, solver, reg, num_iter_max, stop_thr, timing=None):
-    """ot_cluster's rounds on a SciPy sparse matrix (the ratings, n_user x n_item), never densified: ure_csr_cost ->
-    the exact LP on the host (warm-started by ure_ot_potentials, as _ot_round) or ure_ot_sinkhorn on the device matrix ->
-    the labels to the device -> ure_csr_centroids, then utils.py's allclose stop on the [k, n_item] centroids.  The
-    arithmetic of the two kernels is this project's (sparse_group.py): the reference's own branch raises.  Every refusal
-    (shape, non-finite values, k) comes before any device work.  timing (a list): the round's parts on the host's clock with a
-    synchronisation between them, appended as a dict of milliseconds, as _ot_round does."""
-    from ..sparse_group import check_cluster_args, dense_rows
-    halves = check_cluster_args(X, k)
-    n = halves[0].shape[0]
-    if solver == 'sinkhorn' and k > engine.SINKHORN_MAX_K:
-        raise ValueError(f'the sinkhorn solver takes at most {engine.SINKHORN_MAX_K} clusters, not {k}')
-    centroid = dense_rows(halves[0], np.random.choice(n, size=k, replace=False))
-    L, st = nv.lib(), nv.stream_handle()
-    S = engine.CsrSet(halves)
-    Ct = torch.from_numpy(np.ascontiguousarray(centroid.T)).to(S.device)
-    pi = np.zeros(k, dtype=np.float64)
-    stats = []
-    if solver == 'sinkhorn':
-        ot_cluster.sinkhorn_stats = stats
-    for rnd in range(max_iters):
-        marks = []
+def _round_clock(timing):
+    """A round's start on the host's clock -> part(name), which ends a part of the round (bench.py's OT leg): it synchronises
+    and takes a mark, and last=True appends the round's dict of milliseconds to `timing`.  Nothing unless timing is a list."""
+    marks = []
 
-        def tick(name):
-            if timing is not None:
-                torch.cuda.synchronize()
-                marks.append((name, time.perf_counter()))
-        tick('start')
-        dist_d = engine.csr_cost(S, Ct, k)
-        tick('cost_kernel')
-        if solver == 'sinkhorn':
-            r = engine.ot_sinkhorn(dist_d, reg, num_iter_max, stop_thr, want_u=False, want_cost_min=True)
-            stats.append((r['iters'], r['err']))
-            label = r['label'].cpu().numpy()
-            inertia = r['cost_min'].cpu().numpy().sum()              # == np.min(dist, axis=0).sum(): the same float32 values and order
-            tick('device_sinkhorn')
-        else:
-            nv.check(L.ure_ot_potentials(nv.ptr(dist_d), n, k, ot_warm_iters(n), pi.ctypes.data, None, st), 'ure_ot_potentials')
-            tick('device_potentials')
-            dist = dist_d.cpu().numpy()
-            tick('cost_to_host')
-            label, _, _, _ = nv.ot_assign_warm(dist, pi, want_plan=False)
-            inertia = np.min(dist, axis=0).sum()
-            tick('host_solver')
-        sizes = np.bincount(label, minlength=k)
-        if (sizes == 0).any():
-            empty = np.flatnonzero(sizes == 0).tolist()
-            if solver == 'sinkhorn':
-                raise ValueError(f'ot_cluster(solver=\'sinkhorn\'): round {rnd}: cluster(s) {empty} received no '
-                                 f'point, so their centroid (utils.py:648) is undefined; reg = {reg:g} against costs up to '
-                                 f'{float(dist_d.max()):.4g}: a larger reg balances the groups')
-            raise ValueError(f'ot_cluster(solver=\'exact\'): round {rnd}: cluster(s) {empty} received no point, so their centroid '
-                             f'(utils.py:648) is undefined; the exact plan gives every cluster n / k = {n / k:g} points, so '
-                             f'k = {k} is too large for n = {n}')
-        Ct, _ = engine.csr_centroids(S, label, k)
-        new_centroid = np.ascontiguousarray(Ct.cpu().numpy().T)
-        tick('centroids')
+    def part(name, last=False):
         if timing is not None:
-            timing.append({b[0] + '_ms': round((b[1] - a[1]) * 1e3, 4) for a, b in zip(marks[:-1], marks[1:])})
+            torch.cuda.synchronize()
+            marks.append((name, time.perf_counter()))
+            if last:
+                timing.append({b[0] + '_ms': round((b[1] - a[1]) * 1e3, 4) for a, b in zip(marks[:-1], marks[1:])})
+    part('start')
+    return part
+
+
+def _dense_rows(X, k, idx):
+    """The row side of _ot_rounds for a float32 array [n, d] -> (start centroids, cost, centroids, mfma_cost): ure_ot_cost
+    against centroids that go to the device every round (a timed part of its own), the update by ure_ot_centroids_members;
+    mfma_cost() is the MFMA form of the last cost matrix in a buffer of its own (_exact_lp's cross-check)."""
+    n, d = X.shape
+    L, st, dev = nv.lib(), nv.stream_handle(), engine._device()
+    Xd, cd = torch.from_numpy(X).to(dev), None
+    dist_d, cent_d = (torch.empty(k, m, dtype=torch.float32, device=dev) for m in (n, d))
+    counts_d = torch.empty(k, dtype=torch.int32, device=dev)
+
+    def launch(entry, out):
+        nv.check(getattr(L, entry)(nv.ptr(Xd), nv.ptr(cd), n, k, d, nv.ptr(out), st), entry)
+        return out
+
+    def cost(centroid, part):
+        nonlocal cd
+        cd = torch.from_numpy(np.ascontiguousarray(centroid, dtype=np.float32)).to(dev)
+        part('centroid_upload')
+        return launch('ure_ot_cost', dist_d)
+
+    def centroids(label, sizes):
+        # utils.py:648 from member lists: a stable sort of the labels (ascending id inside a cluster = numpy's order of addition)
+        # (labels as the narrowest unsigned type: numpy's stable sort of 8- and 16-bit keys is a radix sort -- 0.3 ms instead of 3 at n = 162,000)
+        keys = label.astype(np.uint8 if k <= 256 else np.uint16 if k <= 65536 else np.int64)
+        order = torch.from_numpy(np.argsort(keys, kind='stable').astype(np.int32)).to(dev)
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
+        nv.check(L.ure_ot_centroids_members(nv.ptr(Xd), nv.ptr(order), nv.ptr(off), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
+                 'ure_ot_centroids_members')
+        return cent_d.cpu().numpy()
+    return X[idx], cost, centroids, lambda: launch('ure_ot_cost_mfma', torch.empty_like(dist_d))
+
+
+def _csr_rows(halves, k, idx):
+    """The row side for the checked (csr, csc) pair of a SciPy sparse matrix (the ratings, n_user x n_item), never densified:
+    engine.csr_cost and engine.csr_centroids (arithmetic: sparse_group.py; the reference's own branch raises).  The centroids
+    stay on the device between rounds, transposed; the host's copy serves the allclose stop.  There is no MFMA form."""
+    start = dense_rows(halves[0], idx)
+    S = engine.CsrSet(halves)
+    Ct = torch.from_numpy(np.ascontiguousarray(start.T)).to(S.device)
+
+    def cost(centroid, part):
+        return engine.csr_cost(S, Ct, k)                              # (Ct holds `centroid`)
+
+    def centroids(label, sizes):
+        nonlocal Ct
+        Ct, _ = engine.csr_centroids(S, label, k)
+        return np.ascontiguousarray(Ct.cpu().numpy().T)
+    return start, cost, centroids, None
+
+
+def _exact_lp(n, k, mfma_cost=None, mismatches=None):
+    """The solver side of _ot_rounds for the exact LP on the host (the reference's arithmetic) -> (name, solve, why_empty);
+    solve(dist_d, part) -> (label, the host matrix).  The cluster potentials, by dual ascent on the device and carried from round
+    to round, are a warm start only: the LP is solved exactly for any potentials.  mismatches (a list): every round is also solved
+    on mfma_cost() from the same potentials and the labels that differ are counted -- what that form needs before anyone relies on it."""
+    pi = np.zeros(k, dtype=np.float64)
+
+    def assign(dist_d, pi, part):                                     # pi in: the previous round's, out: this round's
+        nv.check(nv.lib().ure_ot_potentials(nv.ptr(dist_d), n, k, ot_warm_iters(n), pi.ctypes.data, None, nv.stream_handle()), 'ure_ot_potentials')
+        part('device_potentials')
+        dist = dist_d.cpu().numpy()                                   # [k, n] fp32 (synchronises)
+        part('cost_to_host')
+        label = nv.ot_assign_warm(dist, pi, want_plan=False)[0]       # exact EMD + argmax (host)
+        part('host_solver')
+        return label, dist
+
+    def solve(dist_d, part):
+        fast_label = None if mismatches is None else assign(mfma_cost(), pi.copy(), _round_clock(None))[0]
+        label, dist = assign(dist_d, pi, part)
+        if mismatches is not None:
+            mismatches.append(int((fast_label != label).sum()))
+        return label, dist
+    return 'exact', solve, lambda dist_d: f'the exact plan gives every cluster n / k = {n / k:g} points, so k = {k} is too large for n = {n}'
+
+
+def _sinkhorn(reg, num_iter_max, stop_thr, stats):
+    """The solver side for entropic OT on the device (engine.ot_sinkhorn; labels = argmax of each point's plan row), every round
+    from zero potentials; solve -> (label, every point's cheapest cost as one row): only these 2 n values come to the host,
+    never the [k, n] matrix.  stats receives (iterations, marginal error) of every round."""
+    def solve(dist_d, part):
+        r = engine.ot_sinkhorn(dist_d, reg, num_iter_max, stop_thr, want_u=False, want_cost_min=True)
+        stats.append((r['iters'], r['err']))
+        label, cost_min = r['label'].cpu().numpy(), r['cost_min'].cpu().numpy()
+        part('device_sinkhorn')
+        return label, cost_min[None]
+    return 'sinkhorn', solve, lambda dist_d: f'reg = {reg:g} against costs up to {float(dist_d.max()):.4g}: a larger reg balances the groups'
+
+
+def _ot_rounds(k, rows, solver, max_iters, refuse_empty, timing):
+    """utils.py:637-648 for any row side and solver side, until utils.py's allclose stop or max_iters rounds -> (inertia, label)
+    of the last round.  The inertia is np.min(. , axis=0).sum() of what solve returned beside the labels: the same float32 values
+    in the same order for both solvers.  refuse_empty: a cluster without a point raises; otherwise it is the row side's business."""
+    (centroid, cost, centroids, _), (name, solve, why_empty) = rows, solver
+    for rnd in range(max_iters):
+        part = _round_clock(timing)
+        dist_d = cost(centroid, part)
+        part('cost_kernel')
+        label, costs = solve(dist_d, part)
+        sizes = np.bincount(label, minlength=k)
+        if refuse_empty and (sizes == 0).any():
+            raise ValueError(f'ot_cluster(solver=\'{name}\'): round {rnd}: cluster(s) {np.flatnonzero(sizes == 0).tolist()} received no '
+                             f'point, so their centroid (utils.py:648) is undefined; {why_empty(dist_d)}')
+        new_centroid = centroids(label, sizes)
+        part('centroids', last=True)
         if np.allclose(centroid, new_centroid):
             break
         centroid = new_centroid
+    return np.min(costs, axis=0).sum(), label
+
+
+@timefn
+def ot_cluster(X, k, max_iters=10, timing=None, solver='exact', reg=1e-3, num_iter_max=1000, stop_thr=1e-9):
+    """utils.py:628-656.  Initial centroids come from the global numpy generator, as in the reference.  Returns (inertia,
+    label[int64]).  solver='exact' (the default, the reference's arithmetic: exact EMD) or 'sinkhorn': every round's
+    transport is entropic OT solved on the device, an opt-in that is not bit-parity with the reference; reg, num_iter_max and
+    stop_thr are its settings and are ignored by the exact solver; ot_cluster.sinkhorn_stats: (iterations, error) per round.
+    X may be a SciPy sparse matrix (the ratings): the same rounds (_ot_rounds) then run through the CSR cost and centroid kernels
+    and the n x d array is never formed.  A cluster without a point is refused, except by the exact solver on dense rows: the
+    reference-parity route carries numpy's NaN row of an empty mean forward (and URE_OT_MFMA=1 sets ot_cluster.mfma_mismatches).
+    timing (a list, optional) receives every round's parts in milliseconds, for every combination: centroid_upload_ms (dense
+    rows only), cost_kernel_ms, device_potentials_ms + cost_to_host_ms + host_solver_ms or device_sinkhorn_ms, centroids_ms."""
+    if solver not in ('exact', 'sinkhorn'):
+        raise ValueError(f"solver must be 'exact' or 'sinkhorn', not {solver!r}")
+    if solver == 'sinkhorn':
+        engine.check_sinkhorn_args(reg, num_iter_max, stop_thr)
+    sparse = _is_sparse(X)
+    if sparse:
+        X = check_cluster_args(X, k)                                  # (the checked (csr, csc) pair)
+        n = X[0].shape[0]
+    else:
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, _ = X.shape
+        if k < 1 or k > n:
+            raise ValueError('need 1 <= k <= n clusters')
+    if solver == 'sinkhorn' and k > engine.SINKHORN_MAX_K:
+        raise ValueError(f'the sinkhorn solver takes at most {engine.SINKHORN_MAX_K} clusters, not {k}')
+    idx = np.random.choice(n, size=k, replace=False)
+    rows = _csr_rows(X, k, idx) if sparse else _dense_rows(X, k, idx)
+    if solver == 'sinkhorn':
+        ot_cluster.sinkhorn_stats = []
+        side = _sinkhorn(reg, num_iter_max, stop_thr, ot_cluster.sinkhorn_stats)
+    elif sparse:
+        side = _exact_lp(n, k)
+    else:
+        ot_cluster.mfma_mismatches = [] if os.environ.get('URE_OT_MFMA', '0') == '1' else None
+        side = _exact_lp(n, k, rows[3], ot_cluster.mfma_mismatches)
+    inertia, label = _ot_rounds(k, rows, side, max_iters, sparse or solver == 'sinkhorn', timing)
     print(f'{inertia:.3f}', end=' ')
     return inertia, label.astype(np.int64)
 
@@ -627,6 +588,23 @@ def _ot_cluster_csr(X, k, max_iters, solver, reg, num_iter_max, stop_thr, timing
 # GPU in scipy's csr arithmetic (labels identical to the reference's), the assignment -- a global
 # sort of n*k distances and a greedy fill -- on the host.
 # ---------------------------------------------------------------------------
+def _best_of(n_init, run):
+    """The labels of the first of n_init calls of run() -> (label, inertia, ...) with the smallest inertia below 1e10, else None."""
+    best, fin_label = 1e10, None
+    for _ in range(n_init):
+        label, inertia = run()[:2]
+        if inertia < best:
+            best, fin_label = inertia, label
+    return fin_label
+
+
+def _host_assign(dist, n, k, capacity):
+    """ure_host_kmeans_assign on a host dist [n, k] float32 -> (label int32 [n], inertia): the nearest column, or groups of `capacity` filled in ascending distance."""
+    label, inertia = np.empty(n, dtype=np.int32), ctypes.c_double(0.0)
+    nv.check(nv.lib().ure_host_kmeans_assign(dist.ctypes.data, n, k, capacity, label.ctypes.data, ctypes.byref(inertia)), 'ure_host_kmeans_assign')
+    return label, float(inertia.value)
+
+
 def _dense_f32(sp_mat):
     return np.ascontiguousarray(sp_mat.toarray() if hasattr(sp_mat, 'toarray') else sp_mat, dtype=np.float32)
 
@@ -656,14 +634,12 @@ def _single_kmeans_csr(k, n_user, S, balanced, max_iter, rounds=None):
     round ure_csr_kmeans_cost -> ure_balanced_fill (the fill, or the argmin) -> the labels and the n chosen distances to
     the host -> ure_csr_kmeans_centroids.  The same draw, the same float32 arithmetic and the same stop as the dense route:
     equal labels and inertia.  rounds (a list) receives the fill's round count of every k-means round."""
-    from ..sparse_group import dense_rows
     n = S.n
     assert n == n_user
     group_len = int(np.ceil(n_user / k))
     cen_idx = np.random.choice(n_user, k, replace=False)
     Ct = torch.from_numpy(np.ascontiguousarray(dense_rows(S.csr, cen_idx).T)).to(S.device)
-    label = np.zeros(n, dtype=np.int32)
-    inertia = 0.0
+    label, inertia = np.zeros(n, dtype=np.int32), 0.0
     for _ in range(max_iter):
         dist_d = engine.csr_kmeans_cost(S, Ct, k)
         label_d, fill_rounds = engine.balanced_fill(dist_d, group_len if balanced else 0)
@@ -701,39 +677,28 @@ def singleKmeans(k, n_user, sp_mat, balanced, max_iter):
     dist_d = torch.empty(n, k, dtype=torch.float32, device=dev)
     label_d = torch.empty(n, dtype=torch.int32, device=dev)
     counts_d = torch.empty(k, dtype=torch.int32, device=dev)
-    label = np.zeros(n, dtype=np.int32)
-    new_label = np.empty(n, dtype=np.int32)
-    inertia = ctypes.c_double(0.0)
+    label, inertia = np.zeros(n, dtype=np.int32), 0.0
     for _ in range(max_iter):
         nv.check(L.ure_kmeans_cost(nv.ptr(Xd), nv.ptr(cent_d), n, k, d, nv.ptr(dist_d), st), 'ure_kmeans_cost')
-        dist = dist_d.cpu().numpy()
-        nv.check(L.ure_host_kmeans_assign(dist.ctypes.data, n, k, group_len if balanced else 0, new_label.ctypes.data,
-                                          ctypes.byref(inertia)), 'ure_host_kmeans_assign')
+        new_label, inertia = _host_assign(dist_d.cpu().numpy(), n, k, group_len if balanced else 0)
         if (new_label == label).all():
             break
-        label = new_label.copy()
+        label = new_label
         label_d.copy_(torch.from_numpy(label))
         nv.check(L.ure_kmeans_centroids(nv.ptr(Xd), nv.ptr(label_d), n, k, d, nv.ptr(cent_d), nv.ptr(counts_d), st),
                  'ure_kmeans_centroids')
         if int(counts_d.min().item()) == 0:
             raise ZeroDivisionError('a cluster lost all its members (utils.py:403 divides by its size)')
-    return label.astype(np.int64), float(inertia.value)
+    return label.astype(np.int64), inertia
 
 
 def kmeans(n_group, n_user, sp_mat, balanced=False, n_init=5, max_iter=10):
     """utils.py:406-418: the labels of the best of n_init runs (smallest inertia).  On the CSR route the matrix is checked
     and uploaded once for all runs."""
-    S = _kmeans_csr_set(sp_mat, n_group, n_user) if _kmeans_takes_csr(sp_mat) else None
-    tmp_inertia, fin_label = 1e10, None
-    for _ in range(n_init):
-        if S is not None:
-            label, inertia = _single_kmeans_csr(n_group, n_user, S, balanced, max_iter)
-        else:
-            label, inertia = singleKmeans(n_group, n_user, sp_mat, balanced, max_iter)
-        if inertia < tmp_inertia:
-            tmp_inertia = inertia
-            fin_label = label
-    return fin_label
+    if _kmeans_takes_csr(sp_mat):
+        S = _kmeans_csr_set(sp_mat, n_group, n_user)
+        return _best_of(n_init, lambda: _single_kmeans_csr(n_group, n_user, S, balanced, max_iter))
+    return _best_of(n_init, lambda: singleKmeans(n_group, n_user, sp_mat, balanced, max_iter))
 
 
 # ---------------------------------------------------------------------------
@@ -777,19 +742,15 @@ def findNeighbor(cache_dir, sp_mat, n_user, var='euclidean', n_neighbor=10):
 
 
 def _kmedoids_run(k, n, src, R, balanced, max_iter, metric):
-    L = nv.lib()
     group_len = int(np.ceil(n / k))
     cen_idx = np.random.choice(n, k, replace=False)
-    label = np.zeros(n, dtype=np.int32)
-    new_label = np.empty(n, dtype=np.int32)
-    inertia = ctypes.c_double(0.0)
+    label, inertia = np.zeros(n, dtype=np.int32), 0.0
     for _ in range(max_iter):
         dist = np.ascontiguousarray(engine.pair_cols(src, cen_idx, metric).cpu().numpy())
-        nv.check(L.ure_host_kmeans_assign(dist.ctypes.data, n, k, group_len if balanced else 0, new_label.ctypes.data,
-                                          ctypes.byref(inertia)), 'ure_host_kmeans_assign')
+        new_label, inertia = _host_assign(dist, n, k, group_len if balanced else 0)
         if (new_label == label).all():
             break
-        label = new_label.copy()
+        label = new_label
         # as shipped (utils.py:589-594): the new medoid is the member with the smallest sum over ALL n columns (first
         # minimum), not over its own cluster as in textbook PAM
         for c in range(k):
@@ -797,7 +758,7 @@ def _kmedoids_run(k, n, src, R, balanced, max_iter, metric):
             if members.size == 0:
                 raise ValueError(f'cluster {c} lost all its members (the reference fails on argmin of an empty array)')
             cen_idx[c] = members[np.argmin(R[members])]
-    return label.astype(np.int64), float(inertia.value), cen_idx
+    return label.astype(np.int64), inertia, cen_idx
 
 
 def singleKmedoids(k, n_user, dist_arr, balanced, max_iter, metric=None, return_medoids=False):
@@ -818,13 +779,7 @@ def kmedoids(n_group, n_user, arr, balanced=False, n_init=5, max_iter=10, metric
     gets there, as kmeans).  The row sums are computed once and shared by every run."""
     src = _pair_input(n_group, n_user, arr, metric)
     R = engine.pair_rowsum(src, metric).cpu().numpy()
-    tmp_inertia, fin_label = 1e10, None
-    for _ in range(n_init):
-        label, inertia, _ = _kmedoids_run(n_group, n_user, src, R, balanced, max_iter, metric)
-        if inertia < tmp_inertia:
-            tmp_inertia = inertia
-            fin_label = label
-    return fin_label
+    return _best_of(n_init, lambda: _kmedoids_run(n_group, n_user, src, R, balanced, max_iter, metric))
 
 
 def _lpa_run(n_group, n, src, balanced, max_iter, metric):
@@ -864,13 +819,7 @@ def lpa(n_group, n_user, dist_arr, balanced=False, n_init=5, max_iter=10, metric
     weight is the better grouping); None when no run gets there, as kmeans.  Reference defect fixed: utils.py:515 passes
     n_user into singleLPA's `balanced` slot, so the reference always runs balanced LPA; here `balanced` is honoured."""
     src = _pair_input(n_group, n_user, dist_arr, metric, k_max=128)
-    tmp_inertia, fin_label = 1e10, None
-    for _ in range(n_init):
-        label, inertia = _lpa_run(n_group, n_user, src, balanced, max_iter, metric)
-        if inertia < tmp_inertia:
-            tmp_inertia = inertia
-            fin_label = label
-    return fin_label
+    return _best_of(n_init, lambda: _lpa_run(n_group, n_user, src, balanced, max_iter, metric))
 
 
 # ---------------------------------------------------------------------------
