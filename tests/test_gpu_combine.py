@@ -50,7 +50,7 @@ def device_scores(tables, d, uid, iid):
 
 
 # ---- 5. the score pin ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('d', [4, 32, 128, 256])
+@pytest.mark.parametrize('d', [4, 8, 16, 32, 64, 128, 256])
 @pytest.mark.parametrize('n', [1, 63, 64, 65, 100003])
 def test_stats_see_the_scores_of_ure_score(n, d):
     from ultrare_amd import engine
@@ -172,6 +172,31 @@ def test_mean_weights_score_like_the_mean_within_the_float32_bound(S, d):
 
 def _ulps(got, want):
     return np.abs(got.astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want)).astype(np.float64)
+
+
+@pytest.mark.parametrize('d', [4, 8, 16, 32, 64, 128, 256])
+@pytest.mark.parametrize('link', [0, 1])
+def test_weighted_scores_follow_the_contract_at_every_width(link, d):
+    """score_weighted_kernel<d / 4> round the edges of its 64-pair tile: the predictions against the contract on ure_score's
+    scores, the layout of the squared-error partials (one per tile, zeros behind them, whatever the buffer held) and their sum."""
+    from ultrare_amd import engine
+    for S in (1, 5):
+        for n in (1, 63, 64, 65, 257):
+            tables, (uid, iid, r) = random_case(n, S, d, seed=7)
+            P = device_scores(tables, d, uid, iid)
+            W = np.random.RandomState(100 * S + n + d).standard_normal((2, S + 1))
+            gou = (np.arange(300) % 2).astype(np.int32)
+            u, i, rt = (torch.from_numpy(a).cuda() for a in (uid, iid, r))
+            sse = torch.full((engine.SCORE_PARTIALS,), float('nan'), dtype=torch.float64, device='cuda')
+            pred, sse = engine.score_weighted(tables, d, u, i, rt, link, torch.from_numpy(W).cuda(), torch.from_numpy(gou).cuda(), sse=sse)
+            pred, sse = pred.cpu().numpy(), sse.cpu().numpy()
+            ulps = _ulps(pred, predict_contract(P, link, W[gou[uid]]))
+            used = min(-(-n // 64), engine.SCORE_PARTIALS)
+            want_sse = ((pred.astype(np.float64) - r.astype(np.float64)) ** 2).sum()
+            print(f'd={d} link={link} S={S} n={n}: worst {ulps.max():.2g} ulp, {used} partials, sse {sse.sum():.9g} against {want_sse:.9g}')
+            assert ulps.max() <= 1.0
+            assert sse.shape == (engine.SCORE_PARTIALS,) and (sse[used:] == 0.0).all() and np.isfinite(sse[:used]).all()
+            assert abs(sse.sum() - want_sse) <= 1e-6 * want_sse
 
 
 @pytest.mark.parametrize('link', ['linear', 'logistic'])

@@ -6,8 +6,7 @@
 // between the OT route and the k-means route, nothing else; the ORDER in which a chain receives its terms -- the part of the
 // contract both share -- is the walk's: ascending index, never split across lanes.
 #pragma once
-#include <type_traits>
-
+#include "group_width.h"
 #include "ure_internal.h"
 
 namespace ure {
@@ -32,21 +31,6 @@ inline int group_width(int k)
 inline unsigned group_blocks(int64_t owners, int G)
 {
     return (unsigned)((owners + kBlock / G - 1) / (kBlock / G));
-}
-
-// f(std::integral_constant<int, G>) for the group width G: the one place that lists the widths.
-template <typename F>
-inline void dispatch_group_width(int G, F &&f)
-{
-    switch (G) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        case 16: f(std::integral_constant<int, 16>{}); break;
-        case 32: f(std::integral_constant<int, 32>{}); break;
-        case 64: f(std::integral_constant<int, 64>{}); break;
-    }
 }
 
 // The size checks every entry of the family makes, reported with the entry's own file and line.

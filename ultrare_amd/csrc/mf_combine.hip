@@ -230,28 +230,7 @@ __global__ __launch_bounds__(kBlock) void score_weighted_kernel(TableList T, int
         }
         __syncthreads();
     }
-    if (sse) {
-        __shared__ float part[kWavesPerBlock];
-        sq = wave_sum(sq);
-        if (lane == 0) part[threadIdx.x >> 6] = sq;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < kWavesPerBlock; ++k) t += (double)part[k];
-            sse[blockIdx.x] = t;
-        }
-        for (int t = gridDim.x + threadIdx.x; blockIdx.x == 0 && t < URE_SCORE_PARTIALS; t += kBlock) sse[t] = 0.0;
-    }
-}
-
-template <int LPR>
-static void launch_weighted(const TableList &T, int S, const int32_t *uid, const int32_t *iid, const float *rating, int64_t n, int link,
-                            const double *W, int n_groups, const int32_t *gou, int n_user, float *pred, double *sse, hipStream_t st)
-{
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + kCbTile - 1) / kCbTile, URE_SCORE_PARTIALS);
-    hipLaunchKernelGGL(score_weighted_kernel<LPR>, dim3(blocks), dim3(kBlock), 0, st, T, S, uid, iid, rating, n, link, W,
-                       n_groups, gou, n_user, pred, sse);
+    if (sse) sq_partials(sq, sse);
 }
 
 }  // namespace ure
@@ -285,27 +264,16 @@ int ure_combine_stats(const float *const *U_tables, const float *const *V_tables
     URE_ARG(w && out && scratch);
     URE_ARG(scratch_bytes >= ure_combine_stats_scratch(n, n_models));
     TableList T;
-    for (int m = 0; m < n_models; ++m) {
-        URE_ARG(U_tables[m] && V_tables[m]);
-        T.U[m] = U_tables[m];
-        T.V[m] = V_tables[m];
-    }
+    if (int rc = fill_tables(T, U_tables, V_tables, n_models)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int len = (int)cb_len(n_models);
     const unsigned blocks = (unsigned)cb_blocks(n);
     double *partial = static_cast<double *>(scratch);
-#define URE_CB(L) hipLaunchKernelGGL(combine_stats_kernel<L>, dim3(blocks), dim3(kBlock), 0, st, T, n_models, uid, iid, rating, n, link, w, partial, len)
-    switch (d / 4) {
-        case 1: URE_CB(1); break;
-        case 2: URE_CB(2); break;
-        case 4: URE_CB(4); break;
-        case 8: URE_CB(8); break;
-        case 16: URE_CB(16); break;
-        case 32: URE_CB(32); break;
-        case 64: URE_CB(64); break;
-        default: return fail(-1, "ure_combine_stats: unsupported d=%d", d);
-    }
-#undef URE_CB
+    const bool known = dispatch_group_width(d / 4, [&](auto W) {
+        hipLaunchKernelGGL(combine_stats_kernel<decltype(W)::value>, dim3(blocks), dim3(kBlock), 0, st, T, n_models, uid, iid, rating, n, link, w,
+                           partial, len);
+    });
+    if (!known) return fail(-1, "ure_combine_stats: unsupported d=%d", d);
     hipLaunchKernelGGL(combine_reduce_kernel, dim3((unsigned)(len - 1)), dim3(kBlock), 0, st, (const double *)partial, (int)blocks, len, n, out);
     URE_HIP(hipGetLastError());
     return 0;
@@ -325,24 +293,14 @@ int ure_score_weighted(const float *const *U_tables, const float *const *V_table
     URE_ARG(n_groups >= 1);
     URE_ARG(!group_of_user || n_user >= 1);
     TableList T;
-    for (int m = 0; m < n_models; ++m) {
-        URE_ARG(U_tables[m] && V_tables[m]);
-        T.U[m] = U_tables[m];
-        T.V[m] = V_tables[m];
-    }
+    if (int rc = fill_tables(T, U_tables, V_tables, n_models)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define URE_SW(L) launch_weighted<L>(T, n_models, uid, iid, rating, n, link, W, n_groups, group_of_user, n_user, pred, sse, st)
-    switch (d / 4) {
-        case 1: URE_SW(1); break;
-        case 2: URE_SW(2); break;
-        case 4: URE_SW(4); break;
-        case 8: URE_SW(8); break;
-        case 16: URE_SW(16); break;
-        case 32: URE_SW(32); break;
-        case 64: URE_SW(64); break;
-        default: return fail(-1, "ure_score_weighted: unsupported d=%d", d);
-    }
-#undef URE_SW
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + kCbTile - 1) / kCbTile, URE_SCORE_PARTIALS);
+    const bool known = dispatch_group_width(d / 4, [&](auto lpr) {
+        hipLaunchKernelGGL(score_weighted_kernel<decltype(lpr)::value>, dim3(blocks), dim3(kBlock), 0, st, T, n_models, uid, iid, rating, n, link,
+                           W, n_groups, group_of_user, n_user, pred, sse);
+    });
+    if (!known) return fail(-1, "ure_score_weighted: unsupported d=%d", d);
     URE_HIP(hipGetLastError());
     return 0;
 }

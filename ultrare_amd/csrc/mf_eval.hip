@@ -25,15 +25,12 @@ __global__ __launch_bounds__(kBlock) void score_kernel(TableList T, int n_models
                                                         const float *__restrict__ rating, int64_t n,
                                                         float *__restrict__ pred, double *__restrict__ sse)
 {
-    constexpr int D = LPR * 4;
-    constexpr int G = kWave / LPR;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (LPR - 1), grp = lane / LPR;
-    const int64_t wave_id = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    const PairLanes<LPR> L;
+    constexpr int D = L.D, G = L.G;
+    const int sub = L.sub;
     float sq = 0.f;
-    for (int64_t base = wave_id * G; base < n; base += n_waves * G) {
-        const int64_t j = base + grp;
+    for (int64_t base = L.wave_id * G; base < n; base += L.n_waves * G) {
+        const int64_t j = base + L.grp;
         const bool act = j < n;
         const int u = act ? uid[j] : 0, i = act ? iid[j] : 0;
         float acc = (act && !first) ? pred[j] : 0.f;
@@ -65,22 +62,7 @@ __global__ __launch_bounds__(kBlock) void score_kernel(TableList T, int n_models
         }
         if (act && sub == 0) pred[j] = acc;
     }
-    if (last && sse) {
-        // one partial per workgroup, no atomics: thousands of waves adding to ONE address serialise
-        // at ~12 ns each (measured: 69 us for this kernel); the partials are summed in a fixed
-        // order by ure_eval_reduce or by the host
-        __shared__ float part[kWavesPerBlock];
-        sq = wave_sum(sq);
-        if (lane == 0) part[threadIdx.x >> 6] = sq;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < kWavesPerBlock; ++k) t += (double)part[k];
-            sse[blockIdx.x] = t;
-        }
-        for (int t = gridDim.x + threadIdx.x; blockIdx.x == 0 && t < URE_SCORE_PARTIALS; t += kBlock) sse[t] = 0.0;
-    }
+    if (last && sse) sq_partials(sq, sse);
 }
 
 // One launch for a SERIES of ensembles that differ in their last model only (scratch.py:83-97 over
@@ -96,29 +78,22 @@ __global__ __launch_bounds__(kBlock) void score_series_kernel(const float *__res
                                                                const float *__restrict__ base, float *__restrict__ pred,
                                                                double *__restrict__ sse)
 {
-    constexpr int D = LPR * 4;
-    constexpr int G = kWave / LPR;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (LPR - 1), grp = lane / LPR;
-    const int64_t wave_id = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    const PairLanes<LPR> L;
+    constexpr int D = L.D, G = L.G;
+    const int sub = L.sub;
     U += (size_t)blockIdx.y * stride_u;
     V += (size_t)blockIdx.y * stride_v;
     pred += (size_t)blockIdx.y * n;
     sse += (size_t)blockIdx.y * URE_SCORE_PARTIALS;
     float sq = 0.f;
-    for (int64_t j0 = wave_id * G; j0 < n; j0 += n_waves * G) {
-        const int64_t j = j0 + grp;
+    for (int64_t j0 = L.wave_id * G; j0 < n; j0 += L.n_waves * G) {
+        const int64_t j = j0 + L.grp;
         const bool act = j < n;
         const int u = act ? uid[j] : 0, i = act ? iid[j] : 0;
         float acc = (act && base) ? base[j] : 0.f;
         const float4 a = *reinterpret_cast<const float4 *>(U + (size_t)u * D + sub * 4);
         const float4 b = *reinterpret_cast<const float4 *>(V + (size_t)i * D + sub * 4);
-        float p = a.x * b.x;
-        p = fmaf(a.y, b.y, p);
-        p = fmaf(a.z, b.z, p);
-        p = fmaf(a.w, b.w, p);
-        acc += group_sum<LPR>(p);
+        acc += pair_dot<LPR>(a, b);
         acc = acc / (float)n_total;
         if (act && sub == 0) {
             const float e = acc - rating[j];
@@ -126,17 +101,7 @@ __global__ __launch_bounds__(kBlock) void score_series_kernel(const float *__res
             pred[j] = acc;
         }
     }
-    __shared__ float part[kWavesPerBlock];
-    sq = wave_sum(sq);
-    if (lane == 0) part[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < kWavesPerBlock; ++k) t += (double)part[k];
-        sse[blockIdx.x] = t;
-    }
-    for (int t = gridDim.x + threadIdx.x; blockIdx.x == 0 && t < URE_SCORE_PARTIALS; t += kBlock) sse[t] = 0.0;
+    sq_partials(sq, sse);
 }
 
 // The scores of a shard's OWN model on a test set for a run of epochs, from compact snapshots (struct ure_shard: snap): member e's
@@ -155,15 +120,12 @@ __global__ __launch_bounds__(kBlock) void score_own_epochs_kernel(const float *_
                                                                    const int32_t *__restrict__ uid, const int32_t *__restrict__ iid, int64_t n,
                                                                    float *__restrict__ own)
 {
-    constexpr int D = LPR * 4;
-    constexpr int G = kWave / LPR;
     constexpr int kE = 4;                 // epochs in flight per pair (8: 61.6 -> 65.7 us per call, measured r5)
-    const int lane = threadIdx.x & 63;
-    const int sub = lane & (LPR - 1), grp = lane / LPR;
-    const int64_t wave_id = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
-    for (int64_t j0 = wave_id * G; j0 < n; j0 += n_waves * G) {
-        const int64_t j = j0 + grp;
+    const PairLanes<LPR> L;
+    constexpr int D = L.D, G = L.G;
+    const int sub = L.sub;
+    for (int64_t j0 = L.wave_id * G; j0 < n; j0 += L.n_waves * G) {
+        const int64_t j = j0 + L.grp;
         const bool act = j < n;
         const int u = act ? uid[j] : 0, i = act ? iid[j] : 0;
         const int su = row_slot[u], si = row_slot[n_user_rows + i];
@@ -188,11 +150,7 @@ __global__ __launch_bounds__(kBlock) void score_own_epochs_kernel(const float *_
                 float4 x = a[k], y = b[k];
                 if (su < 0) x = make_float4(ae * x.x, ae * x.y, ae * x.z, ae * x.w);
                 if (si < 0) y = make_float4(ae * y.x, ae * y.y, ae * y.z, ae * y.w);
-                float p = x.x * y.x;
-                p = fmaf(x.y, y.y, p);
-                p = fmaf(x.z, y.z, p);
-                p = fmaf(x.w, y.w, p);
-                p = group_sum<LPR>(p);
+                const float p = pair_dot<LPR>(x, y);
                 if (act && sub == 0 && e0 + k < n_series) own[(size_t)(e0 + k) * n + j] = p;
             }
         }
@@ -938,29 +896,6 @@ __global__ __launch_bounds__(kBlock) void merge_rows_kernel(T *__restrict__ dst,
     }
 }
 
-template <int LPR>
-static void launch_score(const TableList &T, int nm, int nt, int first, int last, const int32_t *uid, const int32_t *iid,
-                         const float *rating, int64_t n, float *pred, double *sse, hipStream_t st)
-{
-    constexpr int G = kWave / LPR;
-    const int64_t waves = (n + G - 1) / G;
-    const unsigned blocks = (unsigned)std::min<int64_t>((waves + kWavesPerBlock - 1) / kWavesPerBlock, URE_SCORE_PARTIALS);
-    hipLaunchKernelGGL(score_kernel<LPR>, dim3(blocks ? blocks : 1), dim3(kBlock), 0, st, T, nm, nt, first, last, uid, iid,
-                       rating, n, pred, sse);
-}
-
-template <int LPR>
-static void launch_score_series(const float *U, const float *V, int64_t su, int64_t sv, int n_series, int nt, const int32_t *uid,
-                                const int32_t *iid, const float *rating, int64_t n, const float *base, float *pred, double *sse,
-                                hipStream_t st)
-{
-    constexpr int G = kWave / LPR;
-    const int64_t waves = (n + G - 1) / G;
-    const unsigned blocks = (unsigned)std::min<int64_t>((waves + kWavesPerBlock - 1) / kWavesPerBlock, URE_SCORE_PARTIALS);
-    hipLaunchKernelGGL(score_series_kernel<LPR>, dim3(blocks ? blocks : 1, (unsigned)n_series), dim3(kBlock), 0, st, U, V, su, sv, nt,
-                       uid, iid, rating, n, base, pred, sse);
-}
-
 }  // namespace ure
 
 using namespace ure;
@@ -1014,22 +949,14 @@ int ure_score(const float *const *U_tables, const float *const *V_tables, int n_
     URE_ARG(uid && iid && pred && n >= 0 && pow2(d) && d >= 4 && d <= 256 && (!sse || rating));
     if (n == 0) return 0;
     TableList T;
-    for (int m = 0; m < n_models; ++m) {
-        URE_ARG(U_tables[m] && V_tables[m]);
-        T.U[m] = U_tables[m];
-        T.V[m] = V_tables[m];
-    }
+    if (int rc = fill_tables(T, U_tables, V_tables, n_models)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (d / 4) {
-        case 1: launch_score<1>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        case 2: launch_score<2>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        case 4: launch_score<4>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        case 8: launch_score<8>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        case 16: launch_score<16>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        case 32: launch_score<32>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        case 64: launch_score<64>(T, n_models, n_models_total, first, last, uid, iid, rating, n, pred, sse, st); break;
-        default: return fail(-1, "ure_score: unsupported d=%d", d);
-    }
+    const bool known = dispatch_group_width(d / 4, [&](auto W) {
+        constexpr int LPR = decltype(W)::value;
+        hipLaunchKernelGGL(score_kernel<LPR>, dim3(pair_blocks(n, kWave / LPR, URE_SCORE_PARTIALS)), dim3(kBlock), 0, st, T, n_models,
+                           n_models_total, first, last, uid, iid, rating, n, pred, sse);
+    });
+    if (!known) return fail(-1, "ure_score: unsupported d=%d", d);
     URE_HIP(hipGetLastError());
     return 0;
 }
@@ -1088,6 +1015,29 @@ int ure_eval_reduce(const int32_t *hits, const double *ndcg, int32_t n_users, co
     return 0;
 }
 
+// The fixed models' running sum, in list order, once for a whole series (U_fixed == NULL: `base` holds it already).
+static int score_fixed_base(const float *const *U_fixed, const float *const *V_fixed, int n_fixed, const int32_t *uid, const int32_t *iid,
+                            const float *rating, int64_t n, int d, float *base, void *stream)
+{
+    for (int c0 = 0; U_fixed && c0 < n_fixed; c0 += URE_MAX_MODELS_PER_CALL) {
+        const int c = std::min(n_fixed - c0, URE_MAX_MODELS_PER_CALL);
+        if (int rc = ure_score(U_fixed + c0, V_fixed + c0, c, n_fixed + 1, c0 == 0, 0, uid, iid, rating, n, d, base, nullptr, stream)) return rc;
+    }
+    return 0;
+}
+
+// The tail of a series: every member's users ranked, then its three figures.
+static int rank_and_reduce(const int32_t *off, int32_t n_users, int32_t n_wide, int32_t n_half, const float *pred, const float *rating,
+                           const int32_t *top_rating, const double *log2_tab, int32_t *hits, double *ndcg, const double *sse, int64_t n,
+                           int n_series, double *out, hipStream_t st)
+{
+    if (n_users > 0)
+        launch_eval_users(off, n_users, n_wide, n_half, pred, rating, top_rating, log2_tab, hits, ndcg, n, n_series, st);
+    hipLaunchKernelGGL(eval_reduce_kernel, dim3((unsigned)n_series), dim3(1024), 0, st, hits, ndcg, n_users, sse, n, out);
+    URE_HIP(hipGetLastError());
+    return 0;
+}
+
 int ure_eval_series(const float *const *U_fixed, const float *const *V_fixed, int n_fixed, const float *U_series,
                     const float *V_series, int64_t stride_u, int64_t stride_v, int n_series, const int32_t *uid, const int32_t *iid,
                     const float *rating, int64_t n, int d, const int32_t *off, int32_t n_users, const double *log2_tab, float *base,
@@ -1099,28 +1049,14 @@ int ure_eval_series(const float *const *U_fixed, const float *const *V_fixed, in
     URE_ARG(uid && iid && rating && n > 0 && pow2(d) && d >= 4 && d <= 256 && off && n_users >= 0 && log2_tab && pred && sse && hits &&
             ndcg && out);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // the fixed models' running sum, in list order, once for the whole series (U_fixed == NULL: `base` holds it already)
-    for (int c0 = 0; U_fixed && c0 < n_fixed; c0 += URE_MAX_MODELS_PER_CALL) {
-        const int c = std::min(n_fixed - c0, URE_MAX_MODELS_PER_CALL);
-        if (int rc = ure_score(U_fixed + c0, V_fixed + c0, c, n_fixed + 1, c0 == 0, 0, uid, iid, rating, n, d, base, nullptr, stream)) return rc;
-    }
-    const float *b = n_fixed ? base : nullptr;
-    const int nt = n_fixed + 1;
-    switch (d / 4) {
-        case 1: launch_score_series<1>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        case 2: launch_score_series<2>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        case 4: launch_score_series<4>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        case 8: launch_score_series<8>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        case 16: launch_score_series<16>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        case 32: launch_score_series<32>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        case 64: launch_score_series<64>(U_series, V_series, stride_u, stride_v, n_series, nt, uid, iid, rating, n, b, pred, sse, st); break;
-        default: return fail(-1, "ure_eval_series: unsupported d=%d", d);
-    }
-    if (n_users > 0)
-        launch_eval_users(off, n_users, n_wide, n_half, pred, rating, top_rating, log2_tab, hits, ndcg, n, n_series, st);
-    hipLaunchKernelGGL(eval_reduce_kernel, dim3((unsigned)n_series), dim3(1024), 0, st, hits, ndcg, n_users, sse, n, out);
-    URE_HIP(hipGetLastError());
-    return 0;
+    if (int rc = score_fixed_base(U_fixed, V_fixed, n_fixed, uid, iid, rating, n, d, base, stream)) return rc;
+    const bool known = dispatch_group_width(d / 4, [&](auto W) {
+        constexpr int LPR = decltype(W)::value;
+        hipLaunchKernelGGL(score_series_kernel<LPR>, dim3(pair_blocks(n, kWave / LPR, URE_SCORE_PARTIALS), (unsigned)n_series), dim3(kBlock), 0,
+                           st, U_series, V_series, stride_u, stride_v, n_fixed + 1, uid, iid, rating, n, n_fixed ? base : nullptr, pred, sse);
+    });
+    if (!known) return fail(-1, "ure_eval_series: unsupported d=%d", d);
+    return rank_and_reduce(off, n_users, n_wide, n_half, pred, rating, top_rating, log2_tab, hits, ndcg, sse, n, n_series, out, st);
 }
 
 int ure_eval_series_compact(const float *const *U_fixed, const float *const *V_fixed, int n_fixed, const float *snap, int64_t stride,
@@ -1144,25 +1080,12 @@ int ure_score_own_compact(const float *snap, int64_t stride, const int32_t *row_
     URE_ARG(snap && row_slot && U0 && V0 && snap_a && n_user_rows > 0 && stride >= 0 && n_series > 0 && n_series <= 65535);
     URE_ARG(uid && iid && own && n > 0 && pow2(d) && d >= 4 && d <= 256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define URE_OWN(L)                                                                                                                      \
-    do {                                                                                                                                \
-        constexpr int G = kWave / L;                                                                                                    \
-        const int64_t waves = (n + G - 1) / G;                                                                                          \
-        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + kWavesPerBlock - 1) / kWavesPerBlock, 16384)); \
-        hipLaunchKernelGGL(score_own_epochs_kernel<L>, dim3(blocks), dim3(kBlock), 0, st, snap, stride, row_slot, U0, V0, snap_a, n_user_rows,          \
-                           n_series, uid, iid, n, own);                                                                                 \
-    } while (0)
-    switch (d / 4) {
-        case 1: URE_OWN(1); break;
-        case 2: URE_OWN(2); break;
-        case 4: URE_OWN(4); break;
-        case 8: URE_OWN(8); break;
-        case 16: URE_OWN(16); break;
-        case 32: URE_OWN(32); break;
-        case 64: URE_OWN(64); break;
-        default: return fail(-1, "ure_score_own_compact: unsupported d=%d", d);
-    }
-#undef URE_OWN
+    const bool known = dispatch_group_width(d / 4, [&](auto W) {
+        constexpr int LPR = decltype(W)::value;
+        hipLaunchKernelGGL(score_own_epochs_kernel<LPR>, dim3(pair_blocks(n, kWave / LPR, 16384)), dim3(kBlock), 0, st, snap, stride, row_slot,
+                           U0, V0, snap_a, n_user_rows, n_series, uid, iid, n, own);
+    });
+    if (!known) return fail(-1, "ure_score_own_compact: unsupported d=%d", d);
     URE_HIP(hipGetLastError());
     return 0;
 }
@@ -1177,35 +1100,16 @@ int ure_eval_series_own(const float *const *U_fixed, const float *const *V_fixed
     URE_ARG(uid && iid && rating && n > 0 && pow2(d) && d >= 4 && d <= 256 && off && n_users >= 0 && log2_tab && pred && sse && hits &&
             ndcg && out);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int c0 = 0; U_fixed && c0 < n_fixed; c0 += URE_MAX_MODELS_PER_CALL) {
-        const int c = std::min(n_fixed - c0, URE_MAX_MODELS_PER_CALL);
-        if (int rc = ure_score(U_fixed + c0, V_fixed + c0, c, n_fixed + 1, c0 == 0, 0, uid, iid, rating, n, d, base, nullptr, stream)) return rc;
-    }
-#define URE_COMBINE(L)                                                                                                                  \
-    do {                                                                                                                                \
-        constexpr int G = kWave / L;                                                                                                    \
-        const int64_t waves = (n + G - 1) / G;                                                                                          \
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((waves + kWavesPerBlock - 1) / kWavesPerBlock, URE_SCORE_PARTIALS));   \
-        const unsigned phys = (unsigned)(((int64_t)blocks * kWavesPerBlock * G + kBlock - 1) / kBlock);                                 \
-        hipLaunchKernelGGL(series_combine_kernel<L>, dim3(phys, (unsigned)n_series), dim3(kBlock), 0, st, own, n_fixed + 1, rating, n,  \
-                           n_fixed ? base : nullptr, pred, sse, blocks);                                                                \
-    } while (0)
-    switch (d / 4) {
-        case 1: URE_COMBINE(1); break;
-        case 2: URE_COMBINE(2); break;
-        case 4: URE_COMBINE(4); break;
-        case 8: URE_COMBINE(8); break;
-        case 16: URE_COMBINE(16); break;
-        case 32: URE_COMBINE(32); break;
-        case 64: URE_COMBINE(64); break;
-        default: return fail(-1, "ure_eval_series_own: unsupported d=%d", d);
-    }
-#undef URE_COMBINE
-    if (n_users > 0)
-        launch_eval_users(off, n_users, n_wide, n_half, pred, rating, top_rating, log2_tab, hits, ndcg, n, n_series, st);
-    hipLaunchKernelGGL(eval_reduce_kernel, dim3((unsigned)n_series), dim3(1024), 0, st, hits, ndcg, n_users, sse, n, out);
-    URE_HIP(hipGetLastError());
-    return 0;
+    if (int rc = score_fixed_base(U_fixed, V_fixed, n_fixed, uid, iid, rating, n, d, base, stream)) return rc;
+    const bool known = dispatch_group_width(d / 4, [&](auto W) {
+        constexpr int LPR = decltype(W)::value, G = kWave / LPR;
+        const int blocks = (int)pair_blocks(n, G, URE_SCORE_PARTIALS);          // score_kernel's workgroups: the order of its partials
+        const unsigned phys = (unsigned)(((int64_t)blocks * kWavesPerBlock * G + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(series_combine_kernel<LPR>, dim3(phys, (unsigned)n_series), dim3(kBlock), 0, st, own, n_fixed + 1,
+                           rating, n, n_fixed ? base : nullptr, pred, sse, blocks);
+    });
+    if (!known) return fail(-1, "ure_eval_series_own: unsupported d=%d", d);
+    return rank_and_reduce(off, n_users, n_wide, n_half, pred, rating, top_rating, log2_tab, hits, ndcg, sse, n, n_series, out, st);
 }
 
 int ure_eval_subset(const int32_t *sub_users, int32_t n_sub, const int32_t *sub_pairs, int32_t n_pairs, const float *pred, const float *rating,

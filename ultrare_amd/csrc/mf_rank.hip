@@ -343,15 +343,7 @@ int ure_rank_pairs(const float *const *U_tables, const float *const *V_tables, i
     if (int rc = rec_upload_tables(U_tables, V_tables, n_models, st, &tab)) return rc;
     A.tab = tab;
     int rc = 0;
-    switch (d / 4) {
-        case 1: rc = launch_rank<1>(A, st); break;
-        case 2: rc = launch_rank<2>(A, st); break;
-        case 4: rc = launch_rank<4>(A, st); break;
-        case 8: rc = launch_rank<8>(A, st); break;
-        case 16: rc = launch_rank<16>(A, st); break;
-        case 32: rc = launch_rank<32>(A, st); break;
-        case 64: rc = launch_rank<64>(A, st); break;
-    }
+    dispatch_group_width(d / 4, [&](auto W) { rc = launch_rank<decltype(W)::value>(A, st); });
     URE_HIP(hipFreeAsync(tab, st));
     return rc;
 }

@@ -378,15 +378,7 @@ int ure_recommend_topk(const float *const *U_tables, const float *const *V_table
     if (int rc = rec_upload_tables(U_tables, V_tables, n_models, st, &tab)) return rc;
     A.tab = tab;
     int rc = 0;
-    switch (d / 4) {
-        case 1: rc = launch_rec<1>(A, st); break;
-        case 2: rc = launch_rec<2>(A, st); break;
-        case 4: rc = launch_rec<4>(A, st); break;
-        case 8: rc = launch_rec<8>(A, st); break;
-        case 16: rc = launch_rec<16>(A, st); break;
-        case 32: rc = launch_rec<32>(A, st); break;
-        case 64: rc = launch_rec<64>(A, st); break;
-    }
+    dispatch_group_width(d / 4, [&](auto W) { rc = launch_rec<decltype(W)::value>(A, st); });
     if (rc == 0 && A.splits > 1) {
         const unsigned blocks = (unsigned)((n_query + kWavesPerBlock - 1) / kWavesPerBlock);
         hipLaunchKernelGGL(rec_merge_splits_kernel, dim3(blocks), dim3(kBlock), 0, st, A.pkey, A.pscore, n_query, A.splits, k, scores, items);

@@ -9,6 +9,7 @@
 // Key order: score descending (NaN below -inf, -0.0 == +0.0), then item id ascending.  The 64-bit key
 // (order_bits(score) << 32 | ~item) is larger for the better item and 0 only for padding (item -1, NaN).
 #pragma once
+#include "group_width.h"
 #include "ure_internal.h"
 
 namespace ure {
