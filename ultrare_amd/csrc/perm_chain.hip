@@ -23,11 +23,13 @@
 //                           twice), the raw words into t[].
 //   shuffle_targets_kernel  one workgroup per (permutation, tile of 16,384 swaps): t[j] = j + temper(word) % (n - j) in place, and the
 //                           swaps counted per BUCKET = range of 1,024 targets (2,048 / 4,096 / 16,384 beyond 2^24 / 2^25 / 2^26 rows;
-//                           ranges of 2,048 / 4,096 targets measured 4-12 % / 35 % slower on a request's shapes).
+//                           ranges of 2,048 / 4,096 targets measured 4-12 % / 35 % slower on a request's shapes).  A launch of records
+//                           (below) only counts: t[] keeps the raw words.
 //   shuffle_bucket_kernel   one workgroup per (permutation, tile of 16,384 swaps): the swaps go to their bucket's stretch of `pairs` as
 //                           (j, t_j) -- the stretch from the prefix of the counts, a tile's place in it from one returning global
 //                           add per bucket it touches, the rest from LDS cursors.  The order inside a bucket is whatever the atomics
-//                           made it; nothing below depends on it.
+//                           made it; nothing below depends on it.  A launch of records works t_j out again from the raw word
+//                           (swap_target: the function the targets pass counted by) and stores ONE word per swap.
 //   shuffle_link_kernel     one workgroup per (permutation, bucket): counts its swaps per target (LDS), prefix, places them per target --
 //                           in LDS when they fit (6,144 swaps; a permutation's last eight buckets, launched apart: 16,384 -- a target has
 //                           ln(n / (n - q)) members on average), else in memory, read back 256 targets at a time (consecutive targets, consecutive lists: one
@@ -35,6 +37,23 @@
 //                           or "go on at q") and the target's own value (Minv: the smallest member of all).
 //   shuffle_resolve_kernel  one lane per row: Minv or the chase through H, divided by the batch size, stored as uint16.
 // A permutation's workgroups sit on ONE XCD (workgroup id mod 8 = permutation mod 8): its 20 bytes per row stay in that L2 while it fits.
+//
+// RECORDS.  A launch whose permutations all have at most 2^20 rows (ranges of at most 2^12 targets; every shard of a request) keeps a
+// swap as ONE word, j | (t_j - q0) << 20 with q0 the first target of the swap's bucket: j < 2^20 below, the target's place in its range
+// above (t_j - q0 = t_j & (range - 1): a range starts at a multiple of its size).  The link workgroup of bucket b knows q0 = b << RL.
+// Beyond 2^20 rows, and at forced ranges of 2^14 targets, a swap stays the pair (j, t_j) and the targets pass writes t[] back.
+// Bytes per row and pass, records (pairs): words W 4; targets R 4 (R 4, W 4); bucket R 4, W 4 (R 4, W 8); link R 4 (R 8), W 4 (H,
+// scattered), W 4 (Minv); resolve R 4 + R 4 + the chase, W 2 -- 38 (52) in all.
+//
+// SCRATCH, per permutation: t [n_al] | H [n_al] | Minv [n_al] | pairs [2 n_al] | totals, cursors, bases [b_al each]; per launch the
+// flag word, the segments' start blocks and the (tile, bucket) count matrices behind.  Who touches what:
+//   words    writes t (raw words); clears totals and cursors.
+//   targets  reads t; pairs: writes the targets back into t.  Writes the count matrix (beyond 1,024 buckets: adds to totals).
+//   bucket   reads t (records: raw words; pairs: targets) and the count matrix; writes the swaps into pairs -- records fill its first
+//            n - 1 WORDS and leave the rest unused, pairs its first n - 1 uint2 --, totals and bases (beyond 1,024 buckets: cursors).
+//   link     reads pairs, totals, bases; writes H and Minv.  A bucket too big for the LDS stage places its members in t + bases[b]: t is
+//            dead by then (the bucket pass, its last reader, is a launch behind), and the stretches of two buckets do not overlap.
+//   resolve  reads Minv and H, writes the tags and, on a broken link, the flag.
 //
 // MEMORY MODEL.  Between launches: stream order.  Inside shuffle_link_kernel's in-memory path the members a workgroup placed are read back
 // by other waves of the SAME workgroup: workgroup-scope release (fence + barrier) / acquire (fence), as the language defines them -- no
@@ -56,7 +75,7 @@ constexpr int kTileBlock = 1024;
 constexpr int kTileLoads = 4;                    // 16-byte loads per lane: a tile of the bucket pass is 16,384 swaps
 constexpr int kTile = kTileBlock * 4 * kTileLoads;
 constexpr int kLinkBlock = 512;
-constexpr int kLinkLoads = 8;                    // pairs a lane of the link pass has in flight
+constexpr int kLinkLoads = 8;                    // swaps a lane of the link pass has in flight
 constexpr int kStage = 6144;                     // members a link workgroup keeps in LDS: three per target of its range (24 KB at 2,048 targets) ...
 constexpr int kStage10 = 3072, kStage12 = 12288; // ... 12 KB at 1,024 targets (eight workgroups per CU), 48 KB at 4,096 and beyond
 constexpr int kStageHeavy = 16384;               // ... and one of a permutation's last kHeavyParts buckets (64 KB)
@@ -65,6 +84,9 @@ constexpr int kResolveBlock = 1024;
 constexpr int kResolveRows = 4096;               // rows per workgroup of the resolve pass
 constexpr unsigned kNone = 0xffffffffu;
 constexpr unsigned kGoOn = 0x80000000u;          // H[j] = kGoOn | q: "what swap q fetched"
+constexpr int64_t kRecordRows = 1 << 20;         // launches of permutations up to here keep a swap as ONE word (RECORDS, in the header)
+constexpr int kRecordShift = 20;                 // ... j below, the target's place in its range above: ranges of at most 2^12 targets
+constexpr int kRecordRangeLog2 = 32 - kRecordShift;
 
 // A barrier that orders LDS traffic only: __syncthreads() also waits for the wave's GLOBAL stores (its fence covers every address space),
 // and a words-kernel step ends with one -- ~700 cycles of an L2 round trip per step that nothing depends on.
@@ -84,8 +106,32 @@ __device__ __forceinline__ unsigned mt_temper(unsigned x)
     return x;
 }
 
-// a permutation's scratch: t [n_al] (the link pass places its members there once the bucket pass has read it) | H [n_al] | Minv [n_al] |
-// pairs [2 n_al] | totals [b_al] | cursors [b_al] | bases [b_al]
+// Swap j's target from the generator's raw word.  The targets pass counts by it and the bucket pass of a launch of records places by it:
+// ONE function, so the two cannot disagree on where a swap goes.
+__device__ __forceinline__ unsigned swap_target(unsigned j, unsigned word, unsigned n) { return j + mt_temper(word) % (n - j); }
+
+// A swap in its bucket's stretch of `pairs`: (j, t_j), or -- a launch of records -- the word j | (t_j - q0) << 20, q0 the bucket's first target.
+template <bool Rec>
+struct swap_fmt;
+template <>
+struct swap_fmt<false> {
+    using type = uint2;
+    static __device__ __forceinline__ type make(unsigned j, unsigned q, unsigned) { return make_uint2(j, q); }
+    static __device__ __forceinline__ type none() { return make_uint2(0u, 0u); }
+    static __device__ __forceinline__ unsigned index(type r) { return r.x; }
+    static __device__ __forceinline__ unsigned place(type r, unsigned q0) { return r.y - q0; }
+};
+template <>
+struct swap_fmt<true> {
+    using type = unsigned;
+    static __device__ __forceinline__ type make(unsigned j, unsigned q, unsigned in_range) { return j | (q & in_range) << kRecordShift; }
+    static __device__ __forceinline__ type none() { return 0u; }
+    static __device__ __forceinline__ unsigned index(type r) { return r & ((1u << kRecordShift) - 1u); }
+    static __device__ __forceinline__ unsigned place(type r, unsigned) { return r >> kRecordShift; }
+};
+
+// a permutation's scratch: t [n_al] | H [n_al] | Minv [n_al] | pairs [2 n_al] | totals [b_al] | cursors [b_al] | bases [b_al]  (who reads and
+// writes which region in which pass: SCRATCH, in the header)
 struct perm_view {
     unsigned *t, *H, *minv;
     uint2 *pairs;
@@ -131,7 +177,7 @@ __global__ __launch_bounds__(kDrawBlock) void shuffle_seed_kernel(const ure_perm
 }
 
 // One workgroup per (permutation, segment): the generator's raw words, in order, into t[] (the targets pass turns them into targets in
-// place); the words live in a ring of 8,192 in LDS.  states == nullptr: ONE segment, from the permutation's seed (at::mt19937(seed):
+// place, unless the launch is one of records); the words live in a ring of 8,192 in LDS.  states == nullptr: ONE segment, from the permutation's seed (at::mt19937(seed):
 // init_genrand; the first draw regenerates); else segment `seg` starts behind the block states[perm][seg].  Segment 0 also clears the
 // permutation's bucket counters.
 __global__ __launch_bounds__(kDrawBlock) void shuffle_words_kernel(const ure_perm_t *__restrict__ perms, int n_perms, unsigned *__restrict__ scratch, int64_t n_al,
@@ -188,8 +234,9 @@ __global__ __launch_bounds__(kDrawBlock) void shuffle_words_kernel(const ure_per
 }
 
 // One workgroup per (permutation, tile of 16,384 swaps): raw word -> target, t[j] = j + temper(word) % (n - j), in place, and the swaps
-// per BUCKET (range of 2^range_log2 targets) added to the permutation's counters -- one global add per bucket the tile touches.
-template <int CAP>
+// per BUCKET (range of 2^range_log2 targets) added to the permutation's counters -- one global add per bucket the tile touches.  A launch of
+// records (Rec) only counts: t[] keeps the raw words, the bucket pass works the targets out again.
+template <int CAP, bool Rec>
 __global__ __launch_bounds__(kTileBlock) void shuffle_targets_kernel(const ure_perm_t *__restrict__ perms, int n_perms, int parts_max, unsigned *__restrict__ scratch,
                                                                       int64_t n_al, int64_t b_al, int range_log2, unsigned *__restrict__ mat)
 {
@@ -216,7 +263,7 @@ __global__ __launch_bounds__(kTileBlock) void shuffle_targets_kernel(const ure_p
     }
     auto target = [&](unsigned j, unsigned word) {
         if (j >= j_end) return word;                            // (beyond the last swap: left as it is)
-        const unsigned q = j + mt_temper(word) % ((unsigned)n - j);
+        const unsigned q = swap_target(j, word, (unsigned)n);
         atomicAdd(&cnt[q >> range_log2], 1u);
         return q;
     };
@@ -228,7 +275,7 @@ __global__ __launch_bounds__(kTileBlock) void shuffle_targets_kernel(const ure_p
             v[u].y = target(j + 1, v[u].y);
             v[u].z = target(j + 2, v[u].z);
             v[u].w = target(j + 3, v[u].w);
-            t4[j >> 2] = v[u];
+            if (!Rec) t4[j >> 2] = v[u];
         }
     }
     __syncthreads();
@@ -281,7 +328,9 @@ __device__ __forceinline__ unsigned prefix_in_place(unsigned *v, int n, unsigned
     return *carry_word;
 }
 
-template <int CAP>
+// One workgroup per (permutation, tile of 16,384 swaps): the tile's swaps into their buckets' stretches of `pairs`.  A launch of records (Rec)
+// finds the raw words in t[] and stores one word per swap, else t[] holds the targets and a swap is stored as (j, t_j).
+template <int CAP, bool Rec>
 __global__ __launch_bounds__(kTileBlock) void shuffle_bucket_kernel(const ure_perm_t *__restrict__ perms, int n_perms, int parts_max, unsigned *__restrict__ scratch,
                                                                      int64_t n_al, int64_t b_al, int range_log2, const unsigned *__restrict__ mat)
 {
@@ -315,10 +364,17 @@ __global__ __launch_bounds__(kTileBlock) void shuffle_bucket_kernel(const ure_pe
         const unsigned *m = mat + (size_t)perm * parts_max * kFewBuckets;
         for (int b = tid; b < n_buckets; b += kTileBlock) {
             unsigned all = 0u, before = 0u;
-            for (int t = 0; t < n_tiles; ++t) {
-                const unsigned c = m[(size_t)t * kFewBuckets + b];
-                before += t < part ? c : 0u;
-                all += c;
+            constexpr int kAtOnce = 8;                          // loads in flight (a tile past the last reads the last again and counts as 0)
+            for (int t0 = 0; t0 < n_tiles; t0 += kAtOnce) {
+                unsigned c[kAtOnce];
+#pragma unroll
+                for (int k = 0; k < kAtOnce; ++k) c[k] = m[(size_t)min(t0 + k, n_tiles - 1) * kFewBuckets + b];
+#pragma unroll
+                for (int k = 0; k < kAtOnce; ++k) {
+                    const unsigned ck = t0 + k < n_tiles ? c[k] : 0u;
+                    before += t0 + k < part ? ck : 0u;
+                    all += ck;
+                }
             }
             base[b] = all;
             cur[b] = before;
@@ -353,7 +409,18 @@ __global__ __launch_bounds__(kTileBlock) void shuffle_bucket_kernel(const ure_pe
         }
         __syncthreads();
     }
-    auto put = [&](unsigned j, unsigned q) { P.pairs[atomicAdd(&cur[q >> range_log2], 1u)] = make_uint2(j, q); };
+    static_assert(!Rec || CAP == kFewBuckets, "records: the count matrix's launches only");
+    using fmt = swap_fmt<Rec>;
+    typename fmt::type *stretches = reinterpret_cast<typename fmt::type *>(P.pairs);
+    const unsigned in_range = (1u << range_log2) - 1u;
+    auto put = [&](unsigned j, unsigned w) {
+        const unsigned q = Rec ? swap_target(j, w, (unsigned)n) : w;
+        stretches[atomicAdd(&cur[q >> range_log2], 1u)] = fmt::make(j, q, in_range);
+    };
+    // The tile's words have arrived -- said ONCE, where every lane passes.  A put stands behind its own lane test, and the compiler cannot
+    // tell at a test's far side whether the loads are in; left to itself it sets vmcnt(0) in front of every put of records, which also
+    // waits for the store of the put before: sixteen scattered stores per lane, one in flight.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
 #pragma unroll
     for (int u = 0; u < kTileLoads; ++u) {
         const unsigned j = j0 + 4u * (unsigned)(tid + u * kTileBlock);
@@ -405,10 +472,13 @@ __device__ __forceinline__ unsigned prefix_by_lane(unsigned *v, unsigned *wave_s
 // Stage: the members a workgroup keeps in LDS.  The last kHeavyParts buckets of a permutation hold several times the average (a target
 // near the end has ln(n / (n - q)) members): they are launched apart with a big stage, the others with a small one -- five workgroups
 // per compute unit instead of two.
-template <int RL, int Stage>
+template <int RL, int Stage, bool Rec>
 __global__ __launch_bounds__(kLinkBlock) void shuffle_link_kernel(const ure_perm_t *__restrict__ perms, int n_perms, int parts_max, unsigned *__restrict__ scratch,
                                                                    int64_t n_al, int64_t b_al, int heavy)
 {
+    static_assert(!Rec || RL <= kRecordRangeLog2, "a record has 12 bits for the target's place in its range");
+    using fmt = swap_fmt<Rec>;
+    using swap_t = typename fmt::type;
     constexpr int kRange = 1 << RL, kPer = kRange / kLinkBlock;
     __shared__ unsigned off[kRange];
     __shared__ unsigned stage[Stage];
@@ -425,52 +495,52 @@ __global__ __launch_bounds__(kLinkBlock) void shuffle_link_kernel(const ure_perm
     const int R = (int)(q1 - q0);
     const perm_view P = view_of(scratch, perm, n_al, b_al);
     const unsigned count = P.totals[part], at = P.bases[part];
-    const uint2 *mine = P.pairs + at;
+    const swap_t *mine = reinterpret_cast<const swap_t *>(P.pairs) + at;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) off[k * kLinkBlock + tid] = 0u;
     __syncthreads();
-    // ---- members per target (kLinkLoads pairs per lane in flight; a bucket of up to 2,048 swaps stays in registers for the second pass)
-    uint2 first[kLinkLoads];
+    // ---- members per target (kLinkLoads swaps per lane in flight; a bucket of up to 2,048 swaps stays in registers for the second pass)
+    swap_t first[kLinkLoads];
 #pragma unroll
     for (int u = 0; u < kLinkLoads; ++u) {
         const unsigned e = (unsigned)(u * kLinkBlock + tid);
-        first[u] = e < count ? mine[e] : make_uint2(0u, 0u);
+        first[u] = e < count ? mine[e] : fmt::none();
     }
 #pragma unroll
     for (int u = 0; u < kLinkLoads; ++u)
-        if ((unsigned)(u * kLinkBlock + tid) < count) atomicAdd(&off[first[u].y - q0], 1u);
+        if ((unsigned)(u * kLinkBlock + tid) < count) atomicAdd(&off[fmt::place(first[u], q0)], 1u);
     for (unsigned e0 = kLinkBlock * kLinkLoads; e0 < count; e0 += kLinkBlock * kLinkLoads) {
-        uint2 m[kLinkLoads];
+        swap_t m[kLinkLoads];
 #pragma unroll
         for (int u = 0; u < kLinkLoads; ++u) {
             const unsigned e = e0 + (unsigned)(u * kLinkBlock + tid);
-            m[u] = e < count ? mine[e] : make_uint2(0u, 0u);
+            m[u] = mine[min(e, count - 1u)];                    // (past the end: the last swap again, left unused -- no test around the load)
         }
 #pragma unroll
         for (int u = 0; u < kLinkLoads; ++u)
-            if (e0 + (unsigned)(u * kLinkBlock + tid) < count) atomicAdd(&off[m[u].y - q0], 1u);
+            if (e0 + (unsigned)(u * kLinkBlock + tid) < count) atomicAdd(&off[fmt::place(m[u], q0)], 1u);
     }
     __syncthreads();
     prefix_by_lane<kLinkBlock, kPer>(off, wave_sum);
     // ---- the members, target by target (off[x] becomes the END of target x's list; its start is off[x - 1])
     const bool in_lds = count <= (unsigned)Stage;               // (uniform)
-    unsigned *placed = P.t + at;                                // (the bucket pass is done with t; a bucket's members take the stretch its pairs have)
-    auto place = [&](const uint2 m) {
-        const unsigned pos = atomicAdd(&off[m.y - q0], 1u);
+    unsigned *placed = P.t + at;                                // (the bucket pass is done with t; a bucket's members take the stretch its swaps have in `pairs`)
+    auto place = [&](const swap_t m) {
+        const unsigned pos = atomicAdd(&off[fmt::place(m, q0)], 1u);
         if (in_lds)
-            stage[pos] = m.x;
+            stage[pos] = fmt::index(m);
         else
-            placed[pos] = m.x;
+            placed[pos] = fmt::index(m);
     };
 #pragma unroll
     for (int u = 0; u < kLinkLoads; ++u)
         if ((unsigned)(u * kLinkBlock + tid) < count) place(first[u]);
     for (unsigned e0 = kLinkBlock * kLinkLoads; e0 < count; e0 += kLinkBlock * kLinkLoads) {
-        uint2 m[kLinkLoads];
+        swap_t m[kLinkLoads];
 #pragma unroll
         for (int u = 0; u < kLinkLoads; ++u) {
             const unsigned e = e0 + (unsigned)(u * kLinkBlock + tid);
-            m[u] = e < count ? mine[e] : make_uint2(0u, 0u);
+            m[u] = mine[min(e, count - 1u)];                    // (past the end: the last swap again, left unused -- no test around the load)
         }
 #pragma unroll
         for (int u = 0; u < kLinkLoads; ++u)
@@ -502,18 +572,27 @@ __global__ __launch_bounds__(kLinkBlock) void shuffle_link_kernel(const ure_perm
         if (x < R) {
             const unsigned e1 = off[x], e0 = x ? off[x - 1] : 0u;
             const unsigned q = q0 + (unsigned)x;
-            unsigned least = kNone;
-            for (unsigned i = e0; i < e1; ++i) {
-                const unsigned a = staged ? stage[i - seg0] : placed[i];
-                least = min(least, a);
-                unsigned succ = kNone;
-                for (unsigned m = e0; m < e1; ++m) {
-                    const unsigned o = staged ? stage[m - seg0] : placed[m];
-                    if (o > a) succ = min(succ, o);
+            // Two copies of the walk, chosen where every lane agrees.  With the members in LDS no load from memory stands between two
+            // stores of H, and a lane's stores follow each other without waiting; ONE loop reading `staged ? stage[] : placed[]` waits
+            // for memory at every member -- and with it for the store before (loads and stores share the counter).
+            auto walk = [&](auto member) {
+                unsigned least = kNone;
+                for (unsigned i = e0; i < e1; ++i) {
+                    const unsigned a = member(i);
+                    least = min(least, a);
+                    unsigned succ = kNone;
+                    for (unsigned m = e0; m < e1; ++m) {
+                        const unsigned o = member(m);
+                        if (o > a) succ = min(succ, o);
+                    }
+                    P.H[a] = succ != kNone ? succ : (a == q ? a : (q == last ? last : (kGoOn | q)));
                 }
-                P.H[a] = succ != kNone ? succ : (a == q ? a : (q == last ? last : (kGoOn | q)));
-            }
-            P.minv[q] = least;
+                P.minv[q] = least;
+            };
+            if (staged)
+                walk([&](unsigned i) { return stage[i - seg0]; });
+            else
+                walk([&](unsigned i) { return placed[i]; });
         }
         if (!in_lds) __syncthreads();
     }
@@ -574,6 +653,29 @@ __global__ __launch_bounds__(kResolveBlock) void shuffle_resolve_kernel(const ur
         }
     }
 }
+
+// one launch of the link pass: the kernel of the launch's swap format (a range of 2^14 targets has no records)
+struct link_launch {
+    bool records;
+    dim3 grid;
+    hipStream_t st;
+    const ure_perm_t *perms;
+    int n_perms, ranges;
+    unsigned *scratch;
+    int64_t n_al, b_al;
+    int heavy;
+    template <int RL, int Stage>
+    void go() const
+    {
+        if constexpr (RL <= kRecordRangeLog2) {
+            if (records) {
+                hipLaunchKernelGGL((shuffle_link_kernel<RL, Stage, true>), grid, dim3(kLinkBlock), 0, st, perms, n_perms, ranges, scratch, n_al, b_al, heavy);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((shuffle_link_kernel<RL, Stage, false>), grid, dim3(kLinkBlock), 0, st, perms, n_perms, ranges, scratch, n_al, b_al, heavy);
+    }
+};
 
 int range_log2_of(int64_t n_max, int32_t wanted)
 {
@@ -637,24 +739,29 @@ extern "C" int ure_device_shuffle_tags(const ure_perm_t *perms, int32_t n_perms,
     const bool few = ranges <= kFewBuckets;                     // (buckets per permutation: small LDS tables, a count matrix instead of global atomics)
     const int64_t J_all = n_max > kSegmentedRows ? (n_max - 1 + jmp::kSegWords - 1) / jmp::kSegWords : 0;
     uint32_t *mat = broken + 64 + (int64_t)n_perms * J_all * kMtN;
-    if (few)
-        hipLaunchKernelGGL(shuffle_targets_kernel<kFewBuckets>, dim3((unsigned)(8 * slots * tiles)), dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
-    else
-        hipLaunchKernelGGL(shuffle_targets_kernel<kMaxBuckets>, dim3((unsigned)(8 * slots * tiles)), dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
-    if (few)
-        hipLaunchKernelGGL(shuffle_bucket_kernel<kFewBuckets>, dim3((unsigned)(8 * slots * tiles)), dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
-    else
-        hipLaunchKernelGGL(shuffle_bucket_kernel<kMaxBuckets>, dim3((unsigned)(8 * slots * tiles)), dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+    // RECORDS: every j fits 20 bits and a target's place in its range the other 12
+    const bool records = few && n_max <= kRecordRows && rl <= kRecordRangeLog2;
+    const dim3 tile_grid((unsigned)(8 * slots * tiles));
+    if (records) {
+        hipLaunchKernelGGL((shuffle_targets_kernel<kFewBuckets, true>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+        hipLaunchKernelGGL((shuffle_bucket_kernel<kFewBuckets, true>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+    } else if (few) {
+        hipLaunchKernelGGL((shuffle_targets_kernel<kFewBuckets, false>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+        hipLaunchKernelGGL((shuffle_bucket_kernel<kFewBuckets, false>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+    } else {
+        hipLaunchKernelGGL((shuffle_targets_kernel<kMaxBuckets, false>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+        hipLaunchKernelGGL((shuffle_bucket_kernel<kMaxBuckets, false>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
+    }
     for (int heavy = 0; heavy < 2; ++heavy) {
-        const dim3 grid((unsigned)(8 * slots * ranges)), block(kLinkBlock);
-        if (rl == 10 && !heavy) hipLaunchKernelGGL((shuffle_link_kernel<10, kStage10>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 10 && heavy) hipLaunchKernelGGL((shuffle_link_kernel<10, kStageHeavy>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 11 && !heavy) hipLaunchKernelGGL((shuffle_link_kernel<11, kStage>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 11 && heavy) hipLaunchKernelGGL((shuffle_link_kernel<11, kStageHeavy>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 12 && !heavy) hipLaunchKernelGGL((shuffle_link_kernel<12, kStage12>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 12 && heavy) hipLaunchKernelGGL((shuffle_link_kernel<12, kStageHeavy>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 14 && !heavy) hipLaunchKernelGGL((shuffle_link_kernel<14, kStage12>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
-        if (rl == 14 && heavy) hipLaunchKernelGGL((shuffle_link_kernel<14, kStageHeavy>), grid, block, 0, st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy);
+        const link_launch at{records, dim3((unsigned)(8 * slots * ranges)), st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy};
+        if (rl == 10 && !heavy) at.go<10, kStage10>();
+        if (rl == 10 && heavy) at.go<10, kStageHeavy>();
+        if (rl == 11 && !heavy) at.go<11, kStage>();
+        if (rl == 11 && heavy) at.go<11, kStageHeavy>();
+        if (rl == 12 && !heavy) at.go<12, kStage12>();
+        if (rl == 12 && heavy) at.go<12, kStageHeavy>();
+        if (rl == 14 && !heavy) at.go<14, kStage12>();
+        if (rl == 14 && heavy) at.go<14, kStageHeavy>();
     }
     hipLaunchKernelGGL(shuffle_resolve_kernel, dim3((unsigned)(8 * slots * rows)), dim3(kResolveBlock), 0, st, perms, (int)n_perms, (int)rows, scratch, n_al, b_al, broken);
     URE_HIP(hipGetLastError());
