@@ -771,4 +771,8 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #ifdef __cplusplus
 }
 #endif
+
+/* The ure_pair_* reductions on a sparse matrix (csrc/pair_dist.hip's CSR tile producer), declared in a header of their own. */
+#include "ultrare_csr_pair.h"
+
 #endif /* ULTRARE_HIP_H */

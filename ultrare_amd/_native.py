@@ -161,6 +161,20 @@ _PROTOTYPES = {
 }
 EXPORTS = tuple(_PROTOTYPES)
 
+# include/ultrare_csr_pair.h (the ure_pair_* reductions on a CSR): a table of its own, as the header is; the memory
+# classes of these names and their guard-zone cases are in tests/test_gpu_sparse_pair.py (tests/test_cpu_sparse_pair.py
+# fails for a name here that has none).
+_CSR = [_vp, _vp, _vp, _i64, _i64, _i32]             # row_off, col, val, n, n_item, metric
+_CSR_PAIR_PROTOTYPES = {
+    'ure_csr_pair_window': (_i32, []),
+    'ure_csr_pair_knn_scratch': (_i64, [_i64, _i64, _i32, _i32]),
+    'ure_csr_pair_knn': (ctypes.c_int, _CSR + [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'ure_csr_pair_rowsum': (ctypes.c_int, _CSR + [_vp, _vp]),
+    'ure_csr_pair_cols': (ctypes.c_int, _CSR + [_vp, _i32, _vp, _vp]),
+    'ure_csr_pair_label_expsum': (ctypes.c_int, _CSR + [_vp, _i32, _vp, _vp]),
+}
+CSR_PAIR_EXPORTS = tuple(_CSR_PAIR_PROTOTYPES)
+
 _lib = None
 
 
@@ -176,7 +190,7 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOTYPES.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

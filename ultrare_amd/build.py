@@ -44,7 +44,8 @@ def source_hash(extra=()):
     identity of the code a library, a profile or a counter file belongs to."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.startswith('.')) + [os.path.join(ROOT, 'include', 'ultrare_hip.h')]
+    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.startswith('.')) + \
+        [os.path.join(ROOT, 'include', h) for h in ('ultrare_hip.h', 'ultrare_csr_pair.h')]
     for path in files:
         h.update(os.path.basename(path).encode() + b'\0')
         with open(path, 'rb') as f:

@@ -15,6 +15,9 @@
 // (|x|^2 the same way), whatever the tile: D[u, v] is a pure function of rows u and v, D[u, v] == D[v, u] bit for bit
 // (t^2 and |t| do not see the sign of t, x.y's products commute) and D[u, u] == 0.
 //
+// The three streamed sources also come from a sparse matrix (csr_pair_tile: the rows of a canonical CSR, the same D bit for
+// bit, the n x d array never formed); the four reductions are written once, over the tile source (DenseSrc / CsrSrc).
+//
 // Nothing is accumulated with atomics, and every reduction takes its terms in an order fixed by n alone, so each
 // result is bitwise reproducible and independent of the grid, the tile and how the query rows are batched.
 #include "ure_internal.h"
@@ -128,6 +131,176 @@ __device__ __forceinline__ void pair_tile(const float *__restrict__ src, int64_t
     __syncthreads();
 }
 
+// ---- the CSR tile producer ------------------------------------------------------------------------------------------
+// The same tile from a canonical CSR (ascending columns inside a row, no repeats, stored zeros kept), the n x n_item array
+// never formed.  A dense term whose two operands are implicit zeros leaves its accumulator as it was (fmaf(0, 0, acc) ==
+// acc, acc + |0 - 0| == acc, and the same for x.y and both |x|^2), so walking the UNION of the stored columns of rows u and
+// v in ascending column, a column stored in one row only paired with 0.f, with the dense producer's own operation per term
+// and its finishing step, gives the dense producer's bits.
+//
+// The tile's 2 kTile lists (kTile rows, then kTile columns) are staged in LDS one item-id window at a time: every list
+// brings its next kCsrPairWindow entries, and the window ends below `hi`, the smallest column id that some list could not
+// bring (INT32_MAX: every list is through).  Entries at or above `hi` wait for a later window; the list that set `hi`
+// spends all it brought, so every window moves on, and the windows ascend, so each pair still sees its union in order.
+// Thread (ty, tx) two-pointer-merges its 4 x 4 pairs inside the window; the accumulators live in registers across
+// windows.  The squared norms of cosine are per list, summed by the thread that owns the list as its entries are spent.
+constexpr int kCsrPairWindow = 32;              // entries a list stages per window (sparse_pair.WINDOW)
+constexpr int kLdW = kCsrPairWindow + 1;        // LDS stride of a staged list
+constexpr int kLists = 2 * kTile;
+
+struct CsrTileLds {
+    float d[kTile * kLdD];          // the tile of D
+    int64_t row[kTile];             // source rows of the tile (-1: none)
+    int64_t col[kTile];             // source columns (-1: none)
+    int64_t cur[kLists];            // first entry of each list that no window has spent
+    int64_t end[kLists];
+    int32_t id[kLists * kLdW];      // the staged column ids
+    float v[kLists * kLdW];         // ... and values
+    float norm[kLists];             // cosine: |x|^2 over the spent entries
+    int32_t cnt[kLists];            // staged entries below hi
+    int32_t hi[2];                  // the window's end, of even and odd windows
+};
+
+template <int MET>
+__device__ __forceinline__ void csr_pair_tile(const int64_t *__restrict__ row_off, const int32_t *__restrict__ col, const float *__restrict__ val,
+                                              CsrTileLds &t)
+{
+    const int tid = threadIdx.x;
+    const int ty = tid >> 4, tx = tid & 15;
+    __syncthreads();
+    if (tid < kLists) {
+        const int64_t u = tid < kTile ? t.row[tid] : t.col[tid - kTile];
+        t.cur[tid] = u >= 0 ? ldg(row_off + u) : 0;
+        t.end[tid] = u >= 0 ? ldg(row_off + u + 1) : 0;
+        t.norm[tid] = 0.f;
+    }
+    if (tid < 2) t.hi[tid] = INT32_MAX;
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    __syncthreads();
+    for (int w = 0;; w ^= 1) {
+        // stage: entry p of list l; the owner of a list that has more than a window left bids its next id for hi
+        for (int e = tid; e < kLists * kCsrPairWindow; e += kBlock) {
+            const int l = e / kCsrPairWindow, p = e % kCsrPairWindow;
+            const int64_t at = t.cur[l] + p;
+            if (at < t.end[l]) {
+                t.id[l * kLdW + p] = ldg(col + at);
+                t.v[l * kLdW + p] = ldg(val + at);
+            }
+        }
+        if (tid < kLists && t.cur[tid] + kCsrPairWindow < t.end[tid]) atomicMin(&t.hi[w], ldg(col + t.cur[tid] + kCsrPairWindow));
+        __syncthreads();
+        const int hi = t.hi[w];
+        if (tid < kLists) {
+            const int staged = (int)min<int64_t>(kCsrPairWindow, t.end[tid] - t.cur[tid]);
+            int c = 0;
+            float nn = t.norm[tid];
+            while (c < staged && t.id[tid * kLdW + c] < hi) {
+                if (MET == URE_DIST_COSINE) {
+                    const float x = t.v[tid * kLdW + c];
+                    nn = fmaf(x, x, nn);
+                }
+                ++c;
+            }
+            t.cnt[tid] = c;
+            t.cur[tid] += c;
+            t.norm[tid] = nn;
+        }
+        if (tid == 0) t.hi[w ^ 1] = INT32_MAX;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int la = (ty + 16 * i) * kLdW, ca = t.cnt[ty + 16 * i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int lb = (kTile + tx + 16 * j) * kLdW, cb = t.cnt[kTile + tx + 16 * j];
+                int pa = 0, pb = 0;
+                int ia = pa < ca ? t.id[la] : INT32_MAX, ib = pb < cb ? t.id[lb] : INT32_MAX;
+                float r = acc[i][j];
+                while (pa < ca || pb < cb) {
+                    const int m = min(ia, ib);
+                    float a = 0.f, b = 0.f;
+                    if (ia == m) {
+                        a = t.v[la + pa];
+                        ++pa;
+                        ia = pa < ca ? t.id[la + pa] : INT32_MAX;
+                    }
+                    if (ib == m) {
+                        b = t.v[lb + pb];
+                        ++pb;
+                        ib = pb < cb ? t.id[lb + pb] : INT32_MAX;
+                    }
+                    if (MET == URE_DIST_EUCLIDEAN) {
+                        const float s = __fsub_rn(a, b);
+                        r = fmaf(s, s, r);
+                    } else if (MET == URE_DIST_MANHATTAN) {
+                        r = __fadd_rn(r, fabsf(__fsub_rn(a, b)));
+                    } else {
+                        r = fmaf(a, b, r);
+                    }
+                }
+                acc[i][j] = r;
+            }
+        }
+        __syncthreads();
+        if (hi == INT32_MAX) break;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = ty + 16 * i, c = tx + 16 * j;
+            float v = acc[i][j];
+            if (MET == URE_DIST_EUCLIDEAN) {
+                // the correctly rounded root, which is what pair_tile's sixteen __fsqrt_rn compile to (np.sqrt's bits, as
+                // tests/test_gpu_cluster.py holds them); spelled sqrtf here so that it does not hang on how this loop is
+                // vectorized.  The norms of cosine take __fsqrt_rn as pair_tile's do: the hardware root in both.
+                v = sqrtf(v);
+            } else if (MET == URE_DIST_COSINE) {
+                const float den = __fmul_rn(__fsqrt_rn(t.norm[r]), __fsqrt_rn(t.norm[kTile + c]));
+                v = den == 0.f ? 1.f : __fsub_rn(1.f, __fdiv_rn(v, den));
+                v = fminf(fmaxf(v, 0.f), 2.f);
+                if (t.row[r] == t.col[c]) v = 0.f;
+            }
+            t.d[r * kLdD + c] = v;
+        }
+    }
+    __syncthreads();
+}
+
+// The tile sources the reductions below are written over: Lds (d, row, col as TileLds names them) and tile<TRANS>(lds).
+struct DenseArgs {
+    const float *src;
+    int64_t n;
+    int d;
+};
+template <int MET>
+struct DenseSrc {
+    static constexpr int kMetric = MET;
+    static constexpr bool kTakesGiven = true;
+    using Lds = TileLds;
+    DenseArgs a;
+    template <bool TRANS>
+    __device__ __forceinline__ void tile(Lds &t) const { pair_tile<MET, TRANS>(a.src, a.n, a.d, t); }
+};
+struct CsrArgs {
+    const int64_t *row_off;
+    const int32_t *col;
+    const float *val;
+};
+template <int MET>
+struct CsrSrc {
+    static constexpr int kMetric = MET;
+    static constexpr bool kTakesGiven = false;
+    using Lds = CsrTileLds;
+    CsrArgs a;
+    template <bool TRANS>
+    __device__ __forceinline__ void tile(Lds &t) const { csr_pair_tile<MET>(a.row_off, a.col, a.val, t); }
+};
+
 // Order-preserving 64-bit key of (distance, column): smaller distance first, then the smaller column; NaN above +inf.
 __device__ __forceinline__ uint64_t pair_key(float v, int64_t col)
 {
@@ -145,13 +318,14 @@ __device__ __forceinline__ float pair_key_dist(uint64_t key)
 // Workgroup (blockIdx.x, blockIdx.y) = kTile query rows x the column span of split blockIdx.y.  Lane r of wave 0 keeps
 // row r's n_nb smallest keys, ascending, in LDS (list[j * kTile + r]); a column enters only when its key is below the
 // current n_nb-th, by insertion.  The list goes to keys[(split * n_query + q) * n_nb ...], unused places as ~0.
-template <int MET>
-__global__ __launch_bounds__(kBlock) void pair_knn_kernel(const float *__restrict__ src, int64_t n, int d, const int32_t *__restrict__ query,
-                                                          int64_t n_query, int n_nb, int64_t span, uint64_t *__restrict__ keys)
+template <class SRC>
+__global__ __launch_bounds__(kBlock) void pair_knn_kernel(const SRC s, int64_t n, const int32_t *__restrict__ query, int64_t n_query, int n_nb,
+                                                          int64_t span, uint64_t *__restrict__ keys)
 {
+    using Lds = typename SRC::Lds;
     extern __shared__ uint64_t knn_lds[];
-    TileLds &t = *reinterpret_cast<TileLds *>(knn_lds);
-    uint64_t *list = knn_lds + (sizeof(TileLds) + 7) / 8;
+    Lds &t = *reinterpret_cast<Lds *>(knn_lds);
+    uint64_t *list = knn_lds + (sizeof(Lds) + 7) / 8;
     const int tid = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.x * kTile;
     const int64_t c_begin = (int64_t)blockIdx.y * span, c_end = min(n, c_begin + span);
@@ -160,7 +334,7 @@ __global__ __launch_bounds__(kBlock) void pair_knn_kernel(const float *__restric
     uint64_t thr = ~(uint64_t)0;
     for (int64_t v0 = c_begin; v0 < c_end; v0 += kTile) {
         if (tid < kTile) t.col[tid] = v0 + tid < c_end ? v0 + tid : -1;
-        pair_tile<MET, false>(src, n, d, t);
+        s.template tile<false>(t);
         if (tid < kTile && t.row[tid] >= 0) {
             const int cn = (int)min<int64_t>(kTile, c_end - v0);
             for (int c = 0; c < cn; ++c) {
@@ -246,10 +420,10 @@ __device__ void rowsum_leaf_table(int64_t m, uint32_t *table, int64_t *stack)
     }
 }
 
-template <int MET>
-__global__ __launch_bounds__(kBlock) void pair_rowsum_kernel(const float *__restrict__ src, int64_t n, int d, float *__restrict__ R)
+template <class SRC>
+__global__ __launch_bounds__(kBlock) void pair_rowsum_kernel(const SRC s, int64_t n, float *__restrict__ R)
 {
-    __shared__ TileLds t;
+    __shared__ typename SRC::Lds t;
     __shared__ float stk[kStackDepth * kTile];
     __shared__ int64_t build[kStackDepth];
     __shared__ uint32_t table[2][kLeafCap];                 // a full buffer, the last buffer
@@ -267,7 +441,7 @@ __global__ __launch_bounds__(kBlock) void pair_rowsum_kernel(const float *__rest
     float r[8], res = 0.f, total = 0.f;
     for (int64_t v0 = 0; v0 < n; v0 += kTile) {
         if (tid < kTile) t.col[tid] = v0 + tid < n ? v0 + tid : -1;
-        pair_tile<MET, false>(src, n, d, t);          // (its first barrier also publishes the tables)
+        s.template tile<false>(t);                    // (its first barrier also publishes the tables)
         if (tid < kTile) {
             const float *row = t.d + tid * kLdD;
             for (int g = 0; g < kTile && v0 + g < n; g += 8) {
@@ -306,11 +480,10 @@ __global__ __launch_bounds__(kBlock) void pair_rowsum_kernel(const float *__rest
 }
 
 // ---- columns --------------------------------------------------------------------------------------------------------
-template <int MET>
-__global__ __launch_bounds__(kBlock) void pair_cols_kernel(const float *__restrict__ src, int64_t n, int d, const int32_t *__restrict__ cols,
-                                                           int m, float *__restrict__ out)
+template <class SRC>
+__global__ __launch_bounds__(kBlock) void pair_cols_kernel(const SRC s, int64_t n, const int32_t *__restrict__ cols, int m, float *__restrict__ out)
 {
-    __shared__ TileLds t;
+    __shared__ typename SRC::Lds t;
     const int tid = threadIdx.x;
     const int64_t u0 = (int64_t)blockIdx.x * kTile;
     const int c0 = blockIdx.y * kTile;
@@ -318,7 +491,7 @@ __global__ __launch_bounds__(kBlock) void pair_cols_kernel(const float *__restri
         t.row[tid] = u0 + tid < n ? u0 + tid : -1;
         t.col[tid] = c0 + tid < m ? (int64_t)cols[c0 + tid] : -1;
     }
-    pair_tile<MET, false>(src, n, d, t);
+    s.template tile<false>(t);
     for (int e = tid; e < kTile * kTile; e += kBlock) {
         const int r = e / kTile, c = e % kTile;
         if (u0 + r < n && c0 + c < m) out[(u0 + r) * m + c0 + c] = t.d[r * kLdD + c];
@@ -328,13 +501,14 @@ __global__ __launch_bounds__(kBlock) void pair_cols_kernel(const float *__restri
 // ---- label-grouped kernel sums (LPA, utils.py:471-475) ---------------------------------------------------------------
 // W[u, g] = sum over i with label[i] = g of exp(-D[i, u]): float32 exp of each term, float64 sums over i = 0, 1, ...
 // in order.  Lane r of wave 0 owns row u0 + r and its k sums (LDS acc[g * kTile + r]).
-template <int MET>
-__global__ __launch_bounds__(kBlock) void pair_label_expsum_kernel(const float *__restrict__ src, int64_t n, int d, const int32_t *__restrict__ label,
-                                                                   int k, double *__restrict__ W)
+template <class SRC>
+__global__ __launch_bounds__(kBlock) void pair_label_expsum_kernel(const SRC s, int64_t n, const int32_t *__restrict__ label, int k,
+                                                                   double *__restrict__ W)
 {
+    using Lds = typename SRC::Lds;
     extern __shared__ uint64_t lp_lds[];
-    TileLds &t = *reinterpret_cast<TileLds *>(lp_lds);
-    double *acc = reinterpret_cast<double *>(lp_lds + (sizeof(TileLds) + 7) / 8);   // [k][kTile]
+    Lds &t = *reinterpret_cast<Lds *>(lp_lds);
+    double *acc = reinterpret_cast<double *>(lp_lds + (sizeof(Lds) + 7) / 8);       // [k][kTile]
     int32_t *lab = reinterpret_cast<int32_t *>(acc + (int64_t)k * kTile);           // [kTile]
     const int tid = threadIdx.x;
     const int64_t u0 = (int64_t)blockIdx.x * kTile;
@@ -345,7 +519,7 @@ __global__ __launch_bounds__(kBlock) void pair_label_expsum_kernel(const float *
             t.col[tid] = v0 + tid < n ? v0 + tid : -1;
             lab[tid] = v0 + tid < n ? label[v0 + tid] : -1;
         }
-        pair_tile<MET, MET == URE_DIST_GIVEN>(src, n, d, t);
+        s.template tile<SRC::kMetric == URE_DIST_GIVEN>(t);
         if (tid < kTile) {
             const int cn = (int)min<int64_t>(kTile, n - v0);
             for (int c = 0; c < cn; ++c) {
@@ -388,15 +562,72 @@ static std::pair<int, int64_t> knn_splits(int64_t n_query, int64_t n, int32_t wa
     return {(int)((col_tiles + per - 1) / per), per * kTile};
 }
 
-static size_t tile_lds() { return (sizeof(TileLds) + 7) / 8 * 8; }
+static int check_csr(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, int32_t metric)
+{
+    URE_ARG(metric == URE_DIST_EUCLIDEAN || metric == URE_DIST_COSINE || metric == URE_DIST_MANHATTAN);      // (no given matrix on a CSR)
+    URE_ARG(row_off && col && val);
+    URE_ARG(n >= 1 && n <= INT32_MAX);
+    URE_ARG(n_item >= 1 && n_item <= INT32_MAX);
+    return 0;
+}
 
-#define URE_PAIR_DISPATCH(metric, KERNEL, grid, lds, st, ...)                                                   \
-    switch (metric) {                                                                                            \
-        case URE_DIST_GIVEN: KERNEL<URE_DIST_GIVEN><<<grid, kBlock, lds, st>>>(__VA_ARGS__); break;              \
-        case URE_DIST_EUCLIDEAN: KERNEL<URE_DIST_EUCLIDEAN><<<grid, kBlock, lds, st>>>(__VA_ARGS__); break;      \
-        case URE_DIST_COSINE: KERNEL<URE_DIST_COSINE><<<grid, kBlock, lds, st>>>(__VA_ARGS__); break;            \
-        default: KERNEL<URE_DIST_MANHATTAN><<<grid, kBlock, lds, st>>>(__VA_ARGS__); break;                      \
-    }
+template <class LDS>
+static size_t tile_lds() { return (sizeof(LDS) + 7) / 8 * 8; }
+
+// KERNEL<SRC<metric>>(SRC<metric>{args}, ...) for the metric of the call (checked before: one SRC serves)
+#define URE_PAIR_DISPATCH(SRC, args, metric, KERNEL, grid, lds, st, ...)                                                                \
+    if (metric == URE_DIST_EUCLIDEAN) KERNEL<SRC<URE_DIST_EUCLIDEAN>><<<grid, kBlock, lds, st>>>(SRC<URE_DIST_EUCLIDEAN>{args}, __VA_ARGS__);   \
+    else if (metric == URE_DIST_COSINE) KERNEL<SRC<URE_DIST_COSINE>><<<grid, kBlock, lds, st>>>(SRC<URE_DIST_COSINE>{args}, __VA_ARGS__);       \
+    else if (metric == URE_DIST_MANHATTAN) KERNEL<SRC<URE_DIST_MANHATTAN>><<<grid, kBlock, lds, st>>>(SRC<URE_DIST_MANHATTAN>{args}, __VA_ARGS__); \
+    else if constexpr (SRC<URE_DIST_GIVEN>::kTakesGiven) KERNEL<SRC<URE_DIST_GIVEN>><<<grid, kBlock, lds, st>>>(SRC<URE_DIST_GIVEN>{args}, __VA_ARGS__);
+
+// The four launches, shared by the dense / given entries and the CSR ones (the arguments are checked by the entry).
+template <template <int> class SRC, class ARGS>
+static int launch_knn(const ARGS &a, int64_t n, int32_t metric, const int32_t *query, int64_t n_query, int32_t n_nb, int32_t splits, float *dist,
+                      int32_t *idx, void *scratch, hipStream_t st)
+{
+    using Lds = typename SRC<URE_DIST_EUCLIDEAN>::Lds;
+    const auto sp = knn_splits(n_query, n, splits);
+    const size_t lds = tile_lds<Lds>() + (size_t)n_nb * kTile * sizeof(uint64_t);
+    const dim3 grid((unsigned)((n_query + kTile - 1) / kTile), (unsigned)sp.first);
+    uint64_t *keys = static_cast<uint64_t *>(scratch);
+    URE_PAIR_DISPATCH(SRC, a, metric, pair_knn_kernel, grid, lds, st, n, query, n_query, n_nb, sp.second, keys);
+    URE_HIP(hipGetLastError());
+    const int64_t total = n_query * n_nb * sp.first;
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 8192);
+    pair_knn_merge_kernel<<<blocks, kBlock, 0, st>>>(keys, n_query, n_nb, sp.first, dist, idx);
+    URE_HIP(hipGetLastError());
+    return 0;
+}
+
+template <template <int> class SRC, class ARGS>
+static int launch_rowsum(const ARGS &a, int64_t n, int32_t metric, float *R, hipStream_t st)
+{
+    const unsigned blocks = (unsigned)((n + kTile - 1) / kTile);
+    URE_PAIR_DISPATCH(SRC, a, metric, pair_rowsum_kernel, blocks, 0, st, n, R);
+    URE_HIP(hipGetLastError());
+    return 0;
+}
+
+template <template <int> class SRC, class ARGS>
+static int launch_cols(const ARGS &a, int64_t n, int32_t metric, const int32_t *cols, int32_t m, float *out, hipStream_t st)
+{
+    const dim3 grid((unsigned)((n + kTile - 1) / kTile), (unsigned)((m + kTile - 1) / kTile));
+    URE_PAIR_DISPATCH(SRC, a, metric, pair_cols_kernel, grid, 0, st, n, cols, m, out);
+    URE_HIP(hipGetLastError());
+    return 0;
+}
+
+template <template <int> class SRC, class ARGS>
+static int launch_label_expsum(const ARGS &a, int64_t n, int32_t metric, const int32_t *label, int32_t k, double *W, hipStream_t st)
+{
+    using Lds = typename SRC<URE_DIST_EUCLIDEAN>::Lds;
+    const size_t lds = tile_lds<Lds>() + (size_t)k * kTile * sizeof(double) + kTile * sizeof(int32_t);
+    const unsigned blocks = (unsigned)((n + kTile - 1) / kTile);
+    URE_PAIR_DISPATCH(SRC, a, metric, pair_label_expsum_kernel, blocks, lds, st, n, label, k, W);
+    URE_HIP(hipGetLastError());
+    return 0;
+}
 
 // numpy pairwise_sum over float64
 static double np_pairwise_f64(const double *a, int64_t m)
@@ -451,29 +682,14 @@ int ure_pair_knn(const float *src, int64_t n, int32_t d, int32_t metric, const i
     URE_ARG(splits >= 0);
     URE_ARG(dist && idx);
     URE_ARG(scratch && scratch_bytes >= ure_pair_knn_scratch(n_query, n, n_nb, splits));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const auto sp = knn_splits(n_query, n, splits);
-    const size_t lds = tile_lds() + (size_t)n_nb * kTile * sizeof(uint64_t);
-    const dim3 grid((unsigned)((n_query + kTile - 1) / kTile), (unsigned)sp.first);
-    uint64_t *keys = static_cast<uint64_t *>(scratch);
-    URE_PAIR_DISPATCH(metric, pair_knn_kernel, grid, lds, st, src, n, d, query, n_query, n_nb, sp.second, keys);
-    URE_HIP(hipGetLastError());
-    const int64_t total = n_query * n_nb * sp.first;
-    const unsigned blocks = (unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 8192);
-    pair_knn_merge_kernel<<<blocks, kBlock, 0, st>>>(keys, n_query, n_nb, sp.first, dist, idx);
-    URE_HIP(hipGetLastError());
-    return 0;
+    return launch_knn<DenseSrc>(DenseArgs{src, n, d}, n, metric, query, n_query, n_nb, splits, dist, idx, scratch, static_cast<hipStream_t>(stream));
 }
 
 int ure_pair_rowsum(const float *src, int64_t n, int32_t d, int32_t metric, float *R, void *stream)
 {
     if (int rc = check_source(src, n, d, metric)) return rc;
     URE_ARG(R);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned blocks = (unsigned)((n + kTile - 1) / kTile);
-    URE_PAIR_DISPATCH(metric, pair_rowsum_kernel, blocks, 0, st, src, n, d, R);
-    URE_HIP(hipGetLastError());
-    return 0;
+    return launch_rowsum<DenseSrc>(DenseArgs{src, n, d}, n, metric, R, static_cast<hipStream_t>(stream));
 }
 
 int ure_pair_cols(const float *src, int64_t n, int32_t d, int32_t metric, const int32_t *cols, int32_t m, float *out, void *stream)
@@ -481,11 +697,7 @@ int ure_pair_cols(const float *src, int64_t n, int32_t d, int32_t metric, const 
     if (int rc = check_source(src, n, d, metric)) return rc;
     URE_ARG(cols && m >= 1);
     URE_ARG(out);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((n + kTile - 1) / kTile), (unsigned)((m + kTile - 1) / kTile));
-    URE_PAIR_DISPATCH(metric, pair_cols_kernel, grid, 0, st, src, n, d, cols, m, out);
-    URE_HIP(hipGetLastError());
-    return 0;
+    return launch_cols<DenseSrc>(DenseArgs{src, n, d}, n, metric, cols, m, out, static_cast<hipStream_t>(stream));
 }
 
 int ure_pair_label_expsum(const float *src, int64_t n, int32_t d, int32_t metric, const int32_t *label, int32_t k, double *W, void *stream)
@@ -494,12 +706,53 @@ int ure_pair_label_expsum(const float *src, int64_t n, int32_t d, int32_t metric
     URE_ARG(label);
     URE_ARG(k >= 1 && k <= kPairMaxGroups);
     URE_ARG(W);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = tile_lds() + (size_t)k * kTile * sizeof(double) + kTile * sizeof(int32_t);
-    const unsigned blocks = (unsigned)((n + kTile - 1) / kTile);
-    URE_PAIR_DISPATCH(metric, pair_label_expsum_kernel, blocks, lds, st, src, n, d, label, k, W);
-    URE_HIP(hipGetLastError());
-    return 0;
+    return launch_label_expsum<DenseSrc>(DenseArgs{src, n, d}, n, metric, label, k, W, static_cast<hipStream_t>(stream));
+}
+
+int32_t ure_csr_pair_window(void) { return kCsrPairWindow; }
+
+int64_t ure_csr_pair_knn_scratch(int64_t n_query, int64_t n, int32_t n_nb, int32_t splits)
+{
+    return ure_pair_knn_scratch(n_query, n, n_nb, splits);
+}
+
+int ure_csr_pair_knn(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, int32_t metric, const int32_t *query,
+                     int64_t n_query, int32_t n_nb, int32_t splits, float *dist, int32_t *idx, void *scratch, int64_t scratch_bytes, void *stream)
+{
+    if (int rc = check_csr(row_off, col, val, n, n_item, metric)) return rc;
+    URE_ARG(n_query >= 1 && n_query <= INT32_MAX);
+    URE_ARG(n_nb >= 1 && n_nb <= kPairMaxNb);
+    URE_ARG(n_nb <= n);
+    URE_ARG(splits >= 0);
+    URE_ARG(dist && idx);
+    URE_ARG(scratch && scratch_bytes >= ure_csr_pair_knn_scratch(n_query, n, n_nb, splits));
+    return launch_knn<CsrSrc>(CsrArgs{row_off, col, val}, n, metric, query, n_query, n_nb, splits, dist, idx, scratch, static_cast<hipStream_t>(stream));
+}
+
+int ure_csr_pair_rowsum(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, int32_t metric, float *R, void *stream)
+{
+    if (int rc = check_csr(row_off, col, val, n, n_item, metric)) return rc;
+    URE_ARG(R);
+    return launch_rowsum<CsrSrc>(CsrArgs{row_off, col, val}, n, metric, R, static_cast<hipStream_t>(stream));
+}
+
+int ure_csr_pair_cols(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, int32_t metric, const int32_t *cols,
+                      int32_t m, float *out, void *stream)
+{
+    if (int rc = check_csr(row_off, col, val, n, n_item, metric)) return rc;
+    URE_ARG(cols && m >= 1);
+    URE_ARG(out);
+    return launch_cols<CsrSrc>(CsrArgs{row_off, col, val}, n, metric, cols, m, out, static_cast<hipStream_t>(stream));
+}
+
+int ure_csr_pair_label_expsum(const int64_t *row_off, const int32_t *col, const float *val, int64_t n, int64_t n_item, int32_t metric,
+                              const int32_t *label, int32_t k, double *W, void *stream)
+{
+    if (int rc = check_csr(row_off, col, val, n, n_item, metric)) return rc;
+    URE_ARG(label);
+    URE_ARG(k >= 1 && k <= kPairMaxGroups);
+    URE_ARG(W);
+    return launch_label_expsum<CsrSrc>(CsrArgs{row_off, col, val}, n, metric, label, k, W, static_cast<hipStream_t>(stream));
 }
 
 int ure_host_assign_desc_f64(const double *w, int64_t n, int32_t k, int64_t capacity, int32_t *label, double *inertia)

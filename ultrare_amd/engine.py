@@ -1232,9 +1232,34 @@ def rank_pairs(tables, d, users, targets, excl=None, stream=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # Reductions of a user-by-user distance matrix (csrc/pair_dist.hip): the k-medoids, LPA and kNN comparison clusterers.
 # metric None / 'given': src is the float32 n x n array D itself; 'euclidean' / 'cosine' / 'manhattan': src is X [n x d]
-# and D is streamed from it, never materialised.
+# and D is streamed from it, never materialised.  src may also be a CsrSet (below) with one of the three streamed metrics:
+# the same D, bit for bit, from the sparse matrix (the CSR tile producer; the contract is sparse_pair.py), X never formed.
 # ---------------------------------------------------------------------------------------------------------------------
 PAIR_METRICS = {'given': 0, 'euclidean': 1, 'cosine': 2, 'manhattan': 3}
+
+
+class _PairCall:
+    """One source of D for the four reductions: the entry-name prefix, the leading arguments of the C call, n, the device."""
+
+    def __init__(self, src, metric):
+        if isinstance(src, CsrSet):
+            from .sparse_pair import check_pair_metric
+            code = PAIR_METRICS[check_pair_metric(metric)]
+            _csr_has(src, 'CSR')
+            if not src.row_off.is_cuda:
+                raise nv.NativeError('pair distances run on the HIP device only (no CPU fallback)')
+            for t, what in ((src.col, 'col'), (src.val, 'val')):
+                _csr_same_device(src.row_off, t, what)
+            self.prefix, self.n, self.device, self.keep = 'ure_csr_pair_', src.n, src.row_off.device, src
+            self.head = (nv.ptr(src.row_off), nv.ptr(src.col), nv.ptr(src.val), src.n, src.n_item, code)
+        else:
+            t, n, d, code = pair_source(src, metric)
+            self.prefix, self.n, self.device, self.keep = 'ure_pair_', n, t.device, t
+            self.head = (nv.ptr(t), n, d, code)
+
+    def __call__(self, name, *args, stream=None):
+        entry = self.prefix + name
+        nv.check(getattr(nv.lib(), entry)(*self.head, *args, nv.stream_handle(stream)), entry)
 
 
 def pair_source(src, metric=None):
@@ -1271,46 +1296,50 @@ def _index_tensor(ids, dev, hi, what):
 
 
 def pair_knn(src, n_nb, metric=None, query=None, splits=0, stream=None):
-    """The n_nb nearest columns of each query row of D (ure_pair_knn): query None = every row.  Returns (dist [n_q, n_nb]
-    float32, idx [n_q, n_nb] int64) on the device, ascending by (distance, column); the row itself is in its own list."""
-    t, n, d, code = pair_source(src, metric)
+    """The n_nb nearest columns of each query row of D (ure_pair_knn; ure_csr_pair_knn for a CsrSet): query None = every row.
+    Returns (dist [n_q, n_nb] float32, idx [n_q, n_nb] int64) on the device, ascending by (distance, column); the row itself
+    is in its own list."""
+    call = _PairCall(src, metric)
+    n, dev = call.n, call.device
     n_nb = int(n_nb)
     if not 1 <= n_nb <= min(n, 128):
         raise ValueError(f'n_nb must be in [1, min(n, 128)] = [1, {min(n, 128)}], not {n_nb}')
-    q = None if query is None else _index_tensor(query, t.device, n, 'query rows')
+    q = None if query is None else _index_tensor(query, dev, n, 'query rows')
     nq = n if q is None else int(q.numel())
-    L = nv.lib()
-    nbytes = int(L.ure_pair_knn_scratch(nq, n, n_nb, int(splits)))
+    sizer = call.prefix + 'knn_scratch'
+    nbytes = int(getattr(nv.lib(), sizer)(nq, n, n_nb, int(splits)))
     if nbytes < 0:
-        raise ValueError(f'ure_pair_knn_scratch refused n_query = {nq}, n = {n}, n_nb = {n_nb}, splits = {splits}')
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
-    dist = torch.empty(nq, n_nb, dtype=torch.float32, device=t.device)
-    idx = torch.empty(nq, n_nb, dtype=torch.int32, device=t.device)
-    nv.check(L.ure_pair_knn(nv.ptr(t), n, d, code, nv.ptr(q), nq, n_nb, int(splits), nv.ptr(dist), nv.ptr(idx), nv.ptr(scratch), nbytes,
-                            nv.stream_handle(stream)), 'ure_pair_knn')
+        raise ValueError(f'{sizer} refused n_query = {nq}, n = {n}, n_nb = {n_nb}, splits = {splits}')
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(nq, n_nb, dtype=torch.float32, device=dev)
+    idx = torch.empty(nq, n_nb, dtype=torch.int32, device=dev)
+    call('knn', nv.ptr(q), nq, n_nb, int(splits), nv.ptr(dist), nv.ptr(idx), nv.ptr(scratch), nbytes, stream=stream)
     return dist, idx.long()
 
 
 def pair_rowsum(src, metric=None, stream=None):
-    """R[u] = sum_v D[u, v] [n] float32 on the device (ure_pair_rowsum), in np.sum(D, axis=1)'s pairwise order."""
-    t, n, d, code = pair_source(src, metric)
-    R = torch.empty(n, dtype=torch.float32, device=t.device)
-    nv.check(nv.lib().ure_pair_rowsum(nv.ptr(t), n, d, code, nv.ptr(R), nv.stream_handle(stream)), 'ure_pair_rowsum')
+    """R[u] = sum_v D[u, v] [n] float32 on the device (ure_pair_rowsum / ure_csr_pair_rowsum), in np.sum(D, axis=1)'s
+    pairwise order."""
+    call = _PairCall(src, metric)
+    R = torch.empty(call.n, dtype=torch.float32, device=call.device)
+    call('rowsum', nv.ptr(R), stream=stream)
     return R
 
 
 def pair_cols(src, cols, metric=None, stream=None):
-    """D[:, cols] [n, m] float32 on the device (ure_pair_cols)."""
-    t, n, d, code = pair_source(src, metric)
-    c = _index_tensor(cols, t.device, n, 'columns')
-    out = torch.empty(n, int(c.numel()), dtype=torch.float32, device=t.device)
-    nv.check(nv.lib().ure_pair_cols(nv.ptr(t), n, d, code, nv.ptr(c), int(c.numel()), nv.ptr(out), nv.stream_handle(stream)), 'ure_pair_cols')
+    """D[:, cols] [n, m] float32 on the device (ure_pair_cols / ure_csr_pair_cols)."""
+    call = _PairCall(src, metric)
+    c = _index_tensor(cols, call.device, call.n, 'columns')
+    out = torch.empty(call.n, int(c.numel()), dtype=torch.float32, device=call.device)
+    call('cols', nv.ptr(c), int(c.numel()), nv.ptr(out), stream=stream)
     return out
 
 
 def pair_label_expsum(src, label, k, metric=None, stream=None):
-    """W[u, g] = sum over i with label[i] == g of exp(-D[i, u]) [n, k] float64 on the device (ure_pair_label_expsum)."""
-    t, n, d, code = pair_source(src, metric)
+    """W[u, g] = sum over i with label[i] == g of exp(-D[i, u]) [n, k] float64 on the device (ure_pair_label_expsum /
+    ure_csr_pair_label_expsum)."""
+    call = _PairCall(src, metric)
+    n = call.n
     k = int(k)
     if not 1 <= k <= 128:
         raise ValueError(f'k must be in [1, 128], not {k}')
@@ -1318,10 +1347,9 @@ def pair_label_expsum(src, label, k, metric=None, stream=None):
     lab = lab.astype(np.int64).reshape(-1)
     if lab.shape != (n,) or lab.min() < 0 or lab.max() >= k:
         raise ValueError(f'label must be n = {n} values in [0, {k})')
-    lab_d = to_device_async(lab.astype(np.int32), t.device)
-    W = torch.empty(n, k, dtype=torch.float64, device=t.device)
-    nv.check(nv.lib().ure_pair_label_expsum(nv.ptr(t), n, d, code, nv.ptr(lab_d), k, nv.ptr(W), nv.stream_handle(stream)),
-             'ure_pair_label_expsum')
+    lab_d = to_device_async(lab.astype(np.int32), call.device)
+    W = torch.empty(n, k, dtype=torch.float64, device=call.device)
+    call('label_expsum', nv.ptr(lab_d), k, nv.ptr(W), stream=stream)
     return W
 
 

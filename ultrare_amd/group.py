@@ -55,6 +55,10 @@ class Group(object):
                 # likewise: kmeans runs its cost, fill and centroid update on the sparse matrix (csrc/csr_kmeans.hip)
                 from .sparse_kmeans import check_kmeans_args
                 embedding = check_kmeans_args(self.rating, n_group)
+            elif cluster_var in ('kmedoids', 'bkmedoids', 'lpa', 'blpa') and self.n_item > DENSE_MAX_ITEMS:
+                # likewise: the pair distances are streamed from the sparse rows (the CSR tile producer of csrc/pair_dist.hip)
+                from .sparse_pair import check_pair_args
+                embedding = check_pair_args(self.rating, 'euclidean', self.n_user, n_group, 128 if cluster_var in ('lpa', 'blpa') else None)
             else:
                 embedding = np.asarray(self.rating.todense(), dtype=np.float32)
         elif trans_var == 'emb':
@@ -68,11 +72,11 @@ class Group(object):
         elif cluster_var in ('kmeans', 'bkmeans'):
             label = kmeans(n_group, self.n_user if isinstance(embedding, tuple) else len(embedding), embedding, balanced=cluster_var == 'bkmeans')
         elif cluster_var in ('kmedoids', 'bkmedoids'):
-            X = _dense_f32(embedding)
-            label = kmedoids(n_group, len(X), X, balanced=cluster_var == 'bkmedoids', metric='euclidean')
+            X = embedding if isinstance(embedding, tuple) else _dense_f32(embedding)
+            label = kmedoids(n_group, self.n_user if isinstance(X, tuple) else len(X), X, balanced=cluster_var == 'bkmedoids', metric='euclidean')
         else:
-            X = _dense_f32(embedding)
-            label = lpa(n_group, len(X), X, balanced=cluster_var == 'blpa', metric='euclidean')
+            X = embedding if isinstance(embedding, tuple) else _dense_f32(embedding)
+            label = lpa(n_group, self.n_user if isinstance(X, tuple) else len(X), X, balanced=cluster_var == 'blpa', metric='euclidean')
 
         if verbose:
             print(''.join(str(i) + ': ' + str(int((label == i).sum())) + ', ' for i in range(n_group)))

@@ -15,7 +15,9 @@ Same flags, defaults and assertions; additions are optional:
   --group-type   'emb-ot' (the reference's only route), 'uniform', or 'rating-ot': the reference's documented alternative, OT groups on
                  the sparse rating matrix (csrc/csr_group.hip, DESIGN 4.17), which needs no user matrix of an earlier --group 0 run;
                  'rating-bkmeans': the balanced k-means the reference compares OT grouping against, on the same sparse matrix
-                 (csrc/csr_kmeans.hip).  Plain 'rating-kmeans' stays with Group.grouping: its shards are not balanced
+                 (csrc/csr_kmeans.hip); 'rating-bkmedoids' / 'rating-blpa': balanced k-medoids / label propagation on
+                 the euclidean distances of the sparse rows, streamed (the CSR tile producer of csrc/pair_dist.hip).
+                 The plain 'rating-kmeans' / '-kmedoids' / '-lpa' stay with Group.grouping: their shards are not balanced
   --optimizer    'sgd' (default: the reference's SGD with momentum 0.9) or 'adam' (torch.optim.Adam with weight_decay, fused into the step
                  kernel: DESIGN 4.21) -- the one that trains wide tables (--k 128) the reference's summed-loss SGD diverges on
   --lr           learning rate (default 0.001, config.py:27)
@@ -36,7 +38,7 @@ parser.add_argument('--delper', type=int, default=2, help='deleted user proporti
 parser.add_argument('--deltype', type=str, default='rand', help='deletion type')
 parser.add_argument('--k', type=int, default=16, help='embedding width')
 parser.add_argument('--parallel', type=int, default=1, help='1 (default): shards side by side / across GPUs; 0: one after the other')
-parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', 'rating-ot' (OT groups) or 'rating-bkmeans' (balanced k-means groups) on the sparse rating matrix, no --group 0 run needed")
+parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', or 'rating-ot' (OT groups), 'rating-bkmeans', 'rating-bkmedoids', 'rating-blpa' (balanced k-means / k-medoids / label propagation groups) on the sparse rating matrix, no --group 0 run needed")
 parser.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adam'], help="'sgd' (reference) or 'adam'")
 parser.add_argument('--lr', type=float, default=None, help='learning rate (default 0.001)')
 parser.add_argument('--data-dir', type=str, default=None)
@@ -56,7 +58,7 @@ def main(argv=None):
     assert args.learn in ['sisa']
     assert args.delper in [2, 5]
     assert args.deltype in ['rand']
-    assert args.group_type in ['emb-ot', 'uniform', 'rating-ot', 'rating-bkmeans']
+    assert args.group_type in ['emb-ot', 'uniform', 'rating-ot', 'rating-bkmeans', 'rating-bkmedoids', 'rating-blpa']
 
     import torch
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:

@@ -706,11 +706,23 @@ def kmeans(n_group, n_user, sp_mat, balanced=False, n_init=5, max_iter=10):
 # reference builds a dense n x n array for them (146 MB at ml-1m, 105 GB at n = 162,000); here each needs only a
 # reduction of that matrix -- a row's nearest columns, the row sums and the medoid columns, or per-row sums of exp(-D)
 # grouped by label -- which csrc/pair_dist.hip computes from tiles that never leave the chip.  `metric=None` takes the
-# reference's own contract, a float32 n x n array; 'euclidean' / 'cosine' / 'manhattan' take X [n x d] and stream D.
+# reference's own contract, a float32 n x n array; 'euclidean' / 'cosine' / 'manhattan' take X [n x d] and stream D, or
+# the sparse rating matrix itself (_pair_input), the input the reference documents for these functions.
 # The assignments (argmin / argmax, or the balanced greedy fill over a global sort) run on the host.
 # ---------------------------------------------------------------------------
+def _pair_csr_set(sp_mat, metric, n_user, k=None, k_max=None):
+    """The checked sparse matrix on the device (sparse_pair.check_pair_args); every refusal comes before any device work."""
+    from ..sparse_pair import check_pair_args
+    return engine.CsrSet(check_pair_args(sp_mat, metric, n_user, k, k_max))
+
+
 def _pair_input(k, n_user, arr, metric, k_max=None):
-    """The device distance source of a clusterer call, after the checks that need no device."""
+    """The device distance source of a clusterer call, after the checks that need no device.  A (csr, csc) pair of
+    sparse_group.Compressed, and a SciPy sparse matrix wider than group.DENSE_MAX_ITEMS (the rule of _kmeans_takes_csr), go
+    through as an engine.CsrSet: D is then streamed from the sparse rows (the CSR tile producer of csrc/pair_dist.hip), bit
+    for bit the dense route's D, and n_user x n_item is never formed.  Narrower matrices and arrays keep the dense route."""
+    if _kmeans_takes_csr(arr):
+        return _pair_csr_set(arr, metric, n_user, k, k_max)
     if not torch.is_tensor(arr):
         arr = _dense_f32(arr) if metric is not None else np.asarray(arr)
     n = int(arr.shape[0]) if len(arr.shape) else 0
@@ -728,12 +740,17 @@ def findNeighbor(cache_dir, sp_mat, n_user, var='euclidean', n_neighbor=10):
     'manhattan'; ascending distance, exact ties by ascending id, the user itself included), and nei_val float16 = -distance.
     sp_mat: csr_matrix or array [n_user, n_embedding].  Saves np.save(cache_dir + var, [nei_idx, nei_val]) as the reference does.
     As shipped, the reference never reads that cache (`if cache_dir == True` is false for any path), so this always computes
-    and then saves.  The distances are the difference form in float32 (csrc/pair_dist.hip), not sklearn's; n_neighbor <= 128."""
+    and then saves.  The distances are the difference form in float32 (csrc/pair_dist.hip), not sklearn's; n_neighbor <= 128.
+    A (csr, csc) pair, and a SciPy sparse matrix wider than group.DENSE_MAX_ITEMS, are read as sparse rows and never densified:
+    the same lists, and the same cache file, bit for bit."""
     if var not in ('euclidean', 'cosine', 'manhattan'):
         raise ValueError(f"var must be 'euclidean', 'cosine' or 'manhattan', not {var!r}")
-    X = _dense_f32(sp_mat)
-    if X.shape[0] != n_user:
-        raise ValueError(f'n_user = {n_user} but sp_mat has {X.shape[0]} rows')
+    if _kmeans_takes_csr(sp_mat):                  # (the sparse rows themselves: _pair_input's rule)
+        X = _pair_csr_set(sp_mat, var, n_user)
+    else:
+        X = _dense_f32(sp_mat)
+        if X.shape[0] != n_user:
+            raise ValueError(f'n_user = {n_user} but sp_mat has {X.shape[0]} rows')
     dist, idx = engine.pair_knn(X, n_neighbor, var)
     nei_idx = idx.cpu().numpy().astype(int)
     nei_val = (-dist).cpu().numpy().astype(np.float16)

@@ -16,6 +16,8 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.rank_pairs(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items)
                                                         (new)             exact full-catalogue rank of each target pair
     torch.ops.ultrare.pair_knn(X, query, n_nb, metric)  utils.py:422-455  the n_nb nearest users of each query row, D streamed
+    torch.ops.ultrare.csr_pair_knn(row_off, col, val, n_item, query, n_nb, metric)
+                                                        utils.py:422-455  the same from the rows of a device CSR, bit for bit
     torch.ops.ultrare.ot_sinkhorn(dist, reg, num_iter_max, stop_thr)
                                                         (new)             log-domain Sinkhorn on a [k, n] cost matrix ->
                                                                           (label, u, v, err, iters)
@@ -164,6 +166,24 @@ def pair_knn(X: torch.Tensor, query: Optional[torch.Tensor], n_nb: int, metric: 
 def _(X, query, n_nb, metric):
     n_q = X.shape[0] if query is None else query.numel()
     return X.new_empty(n_q, n_nb), X.new_empty(n_q, n_nb, dtype=torch.int64)
+
+
+@torch.library.custom_op('ultrare::csr_pair_knn', mutates_args=())
+def csr_pair_knn(row_off: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n_item: int, query: Optional[torch.Tensor], n_nb: int,
+                 metric: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pair_knn on the rows of a device CSR of n_item columns (ascending columns inside a row, no repeats; the ids are checked
+    against n_item, the order is the caller's word)."""
+    _dev(row_off, col, val, *([query] if query is not None else []))
+    row_off, col, val = _csr_half(row_off, col, val)
+    if n_item < 1 or int(col.max()) >= n_item or int(col.min()) < 0:
+        raise ValueError(f'column indices outside [0, {n_item})')
+    return engine.pair_knn(engine.CsrSet.from_device(row_off.numel() - 1, n_item, row_off, col, val), n_nb, metric, query)
+
+
+@csr_pair_knn.register_fake
+def _(row_off, col, val, n_item, query, n_nb, metric):
+    n_q = row_off.numel() - 1 if query is None else query.numel()
+    return val.new_empty(n_q, n_nb), val.new_empty(n_q, n_nb, dtype=torch.int64)
 
 
 @torch.library.custom_op('ultrare::ot_sinkhorn', mutates_args=())
