@@ -774,5 +774,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 
 /* The ure_pair_* reductions on a sparse matrix (csrc/pair_dist.hip's CSR tile producer), declared in a header of their own. */
 #include "ultrare_csr_pair.h"
+/* The LightGCN backbone (csrc/gcn.hip): propagation over a shard's CSR / CSC, the loss-gradient walks and the SGD update. */
+#include "ultrare_gcn.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -175,6 +175,19 @@ _CSR_PAIR_PROTOTYPES = {
 }
 CSR_PAIR_EXPORTS = tuple(_CSR_PAIR_PROTOTYPES)
 
+# include/ultrare_gcn.h (the LightGCN backbone, csrc/gcn.hip): a table of its own, as the header is; tests/test_cpu_lightgcn.py
+# holds the table, the header and the library to each other, tests/test_gpu_lightgcn.py runs every entry in guard zones.
+_GCN_PROTOTYPES = {
+    'ure_gcn_propagate': (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'ure_gcn_scale': (ctypes.c_int, [_vp, _i64, ctypes.c_float, _vp, _vp]),
+    'ure_gcn_gather_tags': (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'ure_gcn_residual': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'ure_gcn_grad': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
+    'ure_gcn_step_loss': (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    'ure_gcn_sgd_step': (ctypes.c_int, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32, _vp]),
+}
+GCN_EXPORTS = tuple(_GCN_PROTOTYPES)
+
 _lib = None
 
 
@@ -190,7 +203,7 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -7,6 +7,7 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
   D5  data / result roots are configurable   ($ULTRARE_DATA_DIR, $ULTRARE_SAVE_DIR, default ./data, ./result)
   +   InsParam(..., k=16, parallel=False)    optional embedding width and shard-parallel mode
   +   InsParam(..., optimizer='sgd', lr=None) optional optimizer ('adam': engine.TrainJob) and learning rate (None: 0.001)
+  +   InsParam(..., model='mf', gcn_layers=2) optional backbone ('lightgcn': engine.GcnJob, artifacts under LightGCN_*) and its layers
   +   dataset 'toy' is usable end to end     (the reference only has its batch size)
 """
 import os
@@ -31,7 +32,7 @@ DATASETS = {
 
 class InsParam(object):
     def __init__(self, dataset='toy', epochs=50, n_worker=24, layers=[32], n_group=2, del_per=2, del_type='test',
-                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None):
+                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2):
         # model param
         self.k = k  # dimension of embedding (config.py:19 hard-codes 16)
         self.lam = 0.1  # regularization coefficient
@@ -54,6 +55,13 @@ class InsParam(object):
         self.optimizer = optimizer  # 'adam': momentum is not used; betas / eps are torch.optim.Adam's defaults
         self.betas = (0.9, 0.999)
         self.eps = 1e-8
+        if model not in ('mf', 'lightgcn'):
+            raise ValueError(f"model {model!r}: 'mf' or 'lightgcn'")
+        if model == 'lightgcn' and optimizer != 'sgd':
+            raise ValueError(f"model='lightgcn' trains with optimizer='sgd' only, not {optimizer!r}")
+        from .lightgcn import check_layers
+        self.model = model                      # the backbone: 'mf', or 'lightgcn' (ultrare_amd/lightgcn.py)
+        self.gcn_layers = check_layers(gcn_layers)   # propagations per side of the 'lightgcn' backbone (`layers` above is the DMF flag)
 
         # dataset-varied param
         self.del_rating = []  # 2d array/list [[uid, iid], ...]
@@ -200,18 +208,25 @@ class Instance(object):
     #########################
     # runFull, runGroup
     #########################
+    def _model(self):
+        """(model_type, artifact prefix) of the backbone the parameters name."""
+        model = getattr(self.param, 'model', 'mf')
+        return model, {'mf': 'MF_', 'lightgcn': 'LightGCN_'}[model]
+
     def runFull(self, is_save=True, verbose=1):
-        '''model MF'''
+        '''model MF (or the backbone of param.model)'''
+        model, prefix = self._model()
         # full train without deletion
-        self._full(is_save, 'MF_full_train', 'mf', False, verbose)
+        self._full(is_save, prefix + 'full_train', model, False, verbose)
         # retrain from scratch after deletion
-        self._full(is_save, 'MF_retrain', 'mf', True, verbose)
+        self._full(is_save, prefix + 'retrain', model, True, verbose)
 
     def runGroup(self, is_save=True, learn_type='seq', group_type='uniform', n_group=5, verbose=1):
-        '''model MF'''
+        '''model MF (or the backbone of param.model)'''
         if learn_type == 'seq':
             learn_type = 'sisa'      # the published tree only ships the SISA learner (main.py:45)
-        saving_name = 'MF_' + group_type + '_' + learn_type + '_learn'
-        model_list = self._group([], is_save, learn_type, saving_name, 'mf', False, group_type, n_group, verbose)
-        saving_name = 'MF_' + group_type + '_' + learn_type + '_unlearn'
-        return self._group(model_list, is_save, learn_type, saving_name, 'mf', True, group_type, n_group, verbose)
+        model, prefix = self._model()
+        saving_name = prefix + group_type + '_' + learn_type + '_learn'
+        model_list = self._group([], is_save, learn_type, saving_name, model, False, group_type, n_group, verbose)
+        saving_name = prefix + group_type + '_' + learn_type + '_unlearn'
+        return self._group(model_list, is_save, learn_type, saving_name, model, True, group_type, n_group, verbose)

@@ -1893,3 +1893,279 @@ def mmd_matrix(X, groups, bandwidth, kernel_mul=2.0, kernel_num=5, stream=None):
                                      nv.stream_handle(stream)), 'ure_mmd_matrix')
     _csr_held_for(stream, K)
     return K
+
+
+# ---------------------------------------------------------------------------
+# The LightGCN backbone (csrc/gcn.hip, include/ultrare_gcn.h; the contract is lightgcn.py)
+# ---------------------------------------------------------------------------
+class GcnGraph:
+    """A shard's training triples as the bipartite graph LightGCN propagates over, resident on the device: the CSR (a user's
+    items) and the CSC (an item's users) of lightgcn.Graph, s = 1 / sqrt(deg) of both sides, the ratings in CSR order and the
+    position maps (pos: CSR entry -> file position, to_csr: CSC entry -> CSR position).  An index out of range, or no triple at
+    all, raises ValueError before any device work."""
+
+    def __init__(self, uid, iid, rating, n_user, n_item, device=None):
+        from . import lightgcn
+        rating = np.asarray(rating)
+        if rating.shape != np.shape(uid):
+            raise ValueError(f'rating has shape {rating.shape}, uid {np.shape(uid)}')
+        self.host = g = lightgcn.Graph(uid, iid, n_user, n_item)
+        if g.N == 0:
+            raise ValueError('a graph needs at least one triple')
+        self.n_user, self.n_item, self.N, self.nnz = g.n_user, g.n_item, g.N, g.N
+        self.device = device or _device()
+        names = ('off_u', 'col', 'row_u', 'pos', 'off_i', 'row', 'to_csr', 's_u', 's_i')
+        arrays = [getattr(g, n) for n in names] + [rating.astype(np.float32)[g.pos]]
+        # (plain copies, as CsrSet's: 28 bytes per rating)
+        for n, a in zip(names + ('rating',), arrays):
+            setattr(self, n, torch.from_numpy(np.ascontiguousarray(a)).to(self.device))
+
+    def side(self, side):
+        """(off, idx, s_src, s_dst, n_dst, n_src) device tensors of 'csr' (items -> users) or 'csc' (users -> items)."""
+        if side == 'csr':
+            return self.off_u, self.col, self.s_i, self.s_u, self.n_user, self.n_item
+        if side == 'csc':
+            return self.off_i, self.row, self.s_u, self.s_i, self.n_item, self.n_user
+        raise ValueError(f"side {side!r}: 'csr' or 'csc'")
+
+
+def _gcn_table(t, rows, d, what, dev):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise nv.NativeError('gcn_propagate runs on the HIP device only (no CPU fallback)')
+    if not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, d)):
+        raise ValueError(f'{what} must be a contiguous float32 [{rows}, {d}] tensor, not {tuple(t.shape)} {t.dtype}')
+    if t.device != dev:
+        raise ValueError(f'{what} is on {t.device} but the graph was uploaded to {dev}')
+    return t
+
+
+def _gcn_propagate(graph, side, X, add, sum, out, d, stream):
+    """ure_gcn_propagate on checked tensors."""
+    off, idx, s_src, s_dst, n_dst, n_src = graph.side(side)
+    nv.check(nv.lib().ure_gcn_propagate(nv.ptr(off), nv.ptr(idx), n_dst, n_src, nv.ptr(s_src), nv.ptr(s_dst), nv.ptr(X), d, nv.ptr(add), nv.ptr(sum),
+                                        nv.ptr(out), nv.stream_handle(stream)), 'ure_gcn_propagate')
+    return out
+
+
+def gcn_propagate(graph, side, X, add=None, sum=None, out=None, stream=None):
+    """One LightGCN propagation (lightgcn.propagate_ref bit for bit): side 'csr' takes an item table X [n_item, d] to the users,
+    'csc' a user table to the items.  out[r] = [add[r] +] s_dst[r] sum_j s_src[j] X[j]; sum (optional) is advanced in place by
+    the rows stored; out (default: a new tensor) may be add, and must not overlap X.  d is a power of two in 4 .. 256.
+    Nothing synchronises."""
+    from . import lightgcn
+    if not (torch.is_tensor(X) and X.is_cuda):
+        raise nv.NativeError('gcn_propagate runs on the HIP device only (no CPU fallback)')
+    _, _, _, _, n_dst, n_src = graph.side(side)
+    d = lightgcn.check_width(int(X.shape[1]) if X.dim() == 2 else 0)
+    _gcn_table(X, n_src, d, 'X', graph.device)
+    for name, t in (('add', add), ('sum', sum), ('out', out)):
+        if t is not None:
+            _gcn_table(t, n_dst, d, name, graph.device)
+    if out is None:
+        out = torch.empty(n_dst, d, dtype=torch.float32, device=X.device)
+        _csr_held_for(stream, out)
+    return _gcn_propagate(graph, side, X, add, sum, out, d, stream)
+
+
+def gcn_step_tags(graph, order, batch, stream=None):
+    """The step of every CSR entry under one epoch's order (file positions in training order, batch t = order[t B : (t + 1) B]):
+    the file-order tags are made on the host, the CSR-order tags by ure_gcn_gather_tags.  -> int32 [nnz] on the device."""
+    order = np.asarray(order.cpu() if torch.is_tensor(order) else order).astype(np.int64)
+    if order.shape != (graph.N,) or order.min() < 0 or order.max() >= graph.N or (np.bincount(order, minlength=graph.N) != 1).any():
+        raise ValueError(f'the order is not a permutation of 0 .. {graph.N - 1}')
+    file_tag = np.empty(graph.N, dtype=np.int32)
+    file_tag[order] = np.arange(graph.N) // int(batch)
+    file_tag = torch.from_numpy(file_tag).to(graph.device)
+    tag = torch.empty(graph.nnz, dtype=torch.int32, device=graph.device)
+    nv.check(nv.lib().ure_gcn_gather_tags(nv.ptr(file_tag), nv.ptr(graph.pos), graph.nnz, nv.ptr(tag), nv.stream_handle(stream)), 'ure_gcn_gather_tags')
+    _csr_held_for(stream, file_tag, tag)
+    return tag
+
+
+def gcn_loss_grad(graph, tag, step, U, V, want_pred=False, stream=None):
+    """lightgcn.loss_grad_ref of the batch {CSR entries with tag == step} under the final tables (U, V) [rows, d]:
+    -> (G_u [n_user, d], G_i [n_item, d], loss float64 [1] on the device, err [nnz], pred [nnz] or None -- both in CSR order, +0.0
+    outside the batch).  Three launches and the loss fold; nothing synchronises."""
+    from . import lightgcn
+    if not (torch.is_tensor(U) and U.is_cuda and torch.is_tensor(V) and V.is_cuda):
+        raise nv.NativeError('gcn_loss_grad runs on the HIP device only (no CPU fallback)')
+    d = lightgcn.check_width(int(U.shape[1]) if U.dim() == 2 else 0)
+    _gcn_table(U, graph.n_user, d, 'U', graph.device)
+    _gcn_table(V, graph.n_item, d, 'V', graph.device)
+    if not (torch.is_tensor(tag) and tag.dtype == torch.int32 and tag.shape == (graph.nnz,) and tag.device == graph.device and tag.is_contiguous()):
+        raise ValueError(f'tag must be a contiguous int32 [{graph.nnz}] tensor on {graph.device}')
+    g, L, dev, st = graph, nv.lib(), graph.device, nv.stream_handle(stream)
+    err = torch.empty(g.nnz, dtype=torch.float32, device=dev)
+    pred = torch.empty(g.nnz, dtype=torch.float32, device=dev) if want_pred else None
+    Gu, Gi = torch.empty_like(U), torch.empty_like(V)
+    row_loss, loss = torch.empty(g.n_user, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float64, device=dev)
+    nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(tag), g.nnz, int(step), nv.ptr(U), nv.ptr(V), g.n_user,
+                                g.n_item, d, nv.ptr(err), nv.ptr(pred), st), 'ure_gcn_residual')
+    nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(tag), nv.ptr(err), g.n_user, g.n_item, g.nnz, int(step), nv.ptr(V), d,
+                            nv.ptr(Gu), nv.ptr(row_loss), st), 'ure_gcn_grad')
+    nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(tag), nv.ptr(err), g.n_item, g.n_user, g.nnz, int(step), nv.ptr(U),
+                            d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
+    nv.check(L.ure_gcn_step_loss(nv.ptr(row_loss), g.n_user, 1, nv.ptr(loss), st), 'ure_gcn_step_loss')
+    _csr_held_for(stream, err, Gu, Gi, row_loss, loss, *([pred] if want_pred else []))
+    return Gu, Gi, loss, err, pred
+
+
+def gcn_sgd_step(w, m, g, lr, lam, mu, first, gscale=1.0, stream=None):
+    """lightgcn.sgd_update_ref in place on the device tensors w and m (float32, contiguous, a multiple of 4 elements), with the
+    gradient g * gscale.  Nothing synchronises."""
+    for t in (w, m, g):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise nv.NativeError('gcn_sgd_step runs on the HIP device only (no CPU fallback)')
+        if not (t.dtype == torch.float32 and t.is_contiguous() and t.shape == w.shape and t.numel() % 4 == 0 and t.numel() > 0):
+            raise ValueError('w, m and g must be contiguous float32 tensors of one shape, a multiple of 4 elements')
+    nv.check(nv.lib().ure_gcn_sgd_step(nv.ptr(w), nv.ptr(m), nv.ptr(g), w.numel(), float(gscale), float(np.float32(lr)), float(np.float32(lam)),
+                                       float(np.float32(mu)), int(bool(first)), nv.stream_handle(stream)), 'ure_gcn_sgd_step')
+
+
+class GcnJob:
+    """One shard trained with the LightGCN backbone (lightgcn.train_ref in float32, bit for bit): per step a forward of `layers`
+    propagations per side, the residual pass and the two masked gradient walks, `layers` more propagations back, and one SGD
+    update of every row of the parameters.  What Scratch._train uses of a TrainJob is here under the same names.
+
+    graph  : GcnGraph
+    init   : (P0 [n_user, k], Q0 [n_item, k]) float32 numpy arrays or tensors
+    orders : int32 [epochs, N] -- per epoch the file positions in training order (batch t = orders[e][t B : (t + 1) B])"""
+
+    _TABLES = ('W', 'M', 'G', 'S', 'Xa', 'Xb', 'Star')
+
+    def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50):
+        from . import lightgcn
+        self.layers = lightgcn.check_layers(layers)
+        self.graph, self.k, self.d = graph, int(k), pad_dim(int(k))
+        self.batch, self.epochs, self.device = int(batch), int(epochs), graph.device
+        if self.batch < 1 or self.epochs < 0:
+            raise ValueError(f'batch {batch!r} must be positive and epochs {epochs!r} not negative')
+        P0, Q0 = (np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32) for t in init)
+        if P0.shape != (graph.n_user, self.k) or Q0.shape != (graph.n_item, self.k):
+            raise ValueError(f'init tables have shapes {P0.shape}, {Q0.shape}: ({graph.n_user}, {self.k}) and ({graph.n_item}, {self.k}) are needed')
+        orders = np.asarray(orders.cpu() if torch.is_tensor(orders) else orders)
+        if orders.shape != (self.epochs, graph.N) or orders.dtype.kind not in 'iu':
+            raise ValueError(f'orders must be integers of shape ({self.epochs}, {graph.N}), not {orders.dtype} {orders.shape}')
+        step_of = (np.arange(graph.N) // self.batch).astype(np.int32)
+        file_tags = np.empty((self.epochs, graph.N), dtype=np.int32)
+        for e in range(self.epochs):
+            o = orders[e].astype(np.int64)
+            if o.min() < 0 or o.max() >= graph.N or (np.bincount(o, minlength=graph.N) != 1).any():
+                raise ValueError(f'orders[{e}] is not a permutation of 0 .. {graph.N - 1}')
+            file_tags[e, o] = step_of
+        # StepLR as engine.TrainJob makes it: float32 values
+        self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
+        self._lam, self._mu = float(np.float32(lam)), float(np.float32(momentum))
+        self._c = float(lightgcn.layer_scale(self.layers))
+        self.steps = (graph.N + self.batch - 1) // self.batch
+        dev, R = self.device, graph.n_user + graph.n_item
+        self.rows = R
+        self._pool = torch.zeros(len(self._TABLES), R, self.d, dtype=torch.float32, device=dev)
+        self._t = dict(zip(self._TABLES, self._pool))
+        start = np.zeros((R, self.d), dtype=np.float32)
+        start[:graph.n_user, :self.k], start[graph.n_user:, :self.k] = P0, Q0
+        self._t['W'].copy_(torch.from_numpy(start))
+        self._file_tags = torch.from_numpy(file_tags).to(dev)
+        self._tag = torch.zeros(graph.nnz, dtype=torch.int32, device=dev)
+        self._err = torch.zeros(graph.nnz, dtype=torch.float32, device=dev)
+        self._row_loss = torch.zeros(graph.n_user, dtype=torch.float64, device=dev)
+        self._sse = torch.zeros(max(self.epochs, 1), dtype=torch.float64, device=dev)
+        self.done = 0            # optimizer steps run
+        self._star_at = -1       # the step count Star belongs to
+        self.ticks = self.epochs * self.steps
+
+    # ---- launches ------------------------------------------------------------------------------------------------------
+    def _sides(self, t):
+        n = self.graph.n_user
+        return t[:n], t[n:]
+
+    def _copy(self, src, c, dst, st):
+        nv.check(nv.lib().ure_gcn_scale(nv.ptr(src), src.numel(), c, nv.ptr(dst), st), 'ure_gcn_scale')
+
+    def _layer(self, src, dst, add, sum, stream):
+        """dst = [add +] A src, both sides; sum += dst."""
+        (src_u, src_i), (dst_u, dst_i) = self._sides(src), self._sides(dst)
+        add_u, add_i = self._sides(add) if add is not None else (None, None)
+        sum_u, sum_i = self._sides(sum) if sum is not None else (None, None)
+        _gcn_propagate(self.graph, 'csr', src_i, add_u, sum_u, dst_u, self.d, stream)
+        _gcn_propagate(self.graph, 'csc', src_u, add_i, sum_i, dst_i, self.d, stream)
+
+    def _forward(self, stream=None):
+        """Star = the layer mean of W and its propagations (skipped when Star is that of the current parameters)."""
+        if self._star_at == self.done:
+            return
+        t, st = self._t, nv.stream_handle(stream)
+        if self.layers:
+            self._copy(t['W'], 1.0, t['S'], st)             # (x * 1.0f is x)
+            src = t['W']
+            for l in range(self.layers):
+                dst = t['Xa'] if l % 2 == 0 else t['Xb']
+                self._layer(src, dst, None, t['S'], stream)
+                src = dst
+        self._copy(t['S'] if self.layers else t['W'], self._c, t['Star'], st)
+        self._star_at = self.done
+
+    def _step(self, e, s, stream=None):
+        g, t, L, st = self.graph, self._t, nv.lib(), nv.stream_handle(stream)
+        if s == 0:
+            nv.check(L.ure_gcn_gather_tags(nv.ptr(self._file_tags[e]), nv.ptr(g.pos), g.nnz, nv.ptr(self._tag), st), 'ure_gcn_gather_tags')
+        self._forward(stream)
+        U, V = self._sides(t['Star'])
+        Gu, Gi = self._sides(t['G'])
+        nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
+                                    g.n_item, self.d, nv.ptr(self._err), None, st), 'ure_gcn_residual')
+        nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(self._tag), nv.ptr(self._err), g.n_user, g.n_item, g.nnz, s, nv.ptr(V),
+                                self.d, nv.ptr(Gu), nv.ptr(self._row_loss), st), 'ure_gcn_grad')
+        nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(self._tag), nv.ptr(self._err), g.n_item, g.n_user, g.nnz, s,
+                                nv.ptr(U), self.d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
+        nv.check(L.ure_gcn_step_loss(nv.ptr(self._row_loss), g.n_user, int(s == 0), self._sse[e:].data_ptr(), st), 'ure_gcn_step_loss')
+        src = t['G']
+        for l in range(self.layers):                        # Horner: H^l = G + A H^(l-1)
+            dst = t['Xa'] if l % 2 == 0 else t['Xb']
+            self._layer(src, dst, t['G'], None, stream)
+            src = dst
+        nv.check(L.ure_gcn_sgd_step(nv.ptr(t['W']), nv.ptr(t['M']), nv.ptr(src), src.numel(), self._c, float(self._lr_host[e]), self._lam, self._mu,
+                                    int(self.done == 0), st), 'ure_gcn_sgd_step')
+        self.done += 1
+
+    # ---- what Scratch._train uses of a job -----------------------------------------------------------------------------
+    def steps_per_epoch(self, s=0):
+        return self.steps
+
+    def run_epochs(self, n_epochs, stream=None):
+        """Advance by whole epochs on `stream` (default: the current one).  Nothing synchronises."""
+        assert self._pool is not None, 'the job is closed'
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(self.device))          # (the uploads and fills of __init__)
+        e0 = self.done // self.steps
+        assert self.done % self.steps == 0 and e0 + n_epochs <= self.epochs
+        for e in range(e0, e0 + n_epochs):
+            for s in range(self.steps):
+                self._step(e, s, stream)
+        return self.done
+
+    def run(self, stream=None):
+        return self.run_epochs(self.epochs - self.done // self.steps, stream)
+
+    def padded_tables(self, s=0, stream=None):
+        """The final tables (U*, V*) of the current parameters at the padded width: recomputed by a forward pass when read."""
+        assert s == 0
+        self._forward(stream)
+        return self._sides(self._t['Star'])
+
+    def tables(self, s=0, stream=None):
+        U, V = self.padded_tables(s, stream)
+        return U[:, :self.k], V[:, :self.k]
+
+    def base_tables(self, padded=False):
+        """The parameters (P, Q): layer 0."""
+        P, Q = self._sides(self._t['W'])
+        return (P, Q) if padded else (P[:, :self.k], Q[:, :self.k])
+
+    def epoch_sse(self, s=0):
+        """Per-epoch sum of squared training errors (host float64 array; synchronises)."""
+        assert s == 0
+        return self._sse[:self.epochs].cpu().numpy()
+
+    def close(self):
+        self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = None

@@ -21,6 +21,9 @@ Same flags, defaults and assertions; additions are optional:
   --optimizer    'sgd' (default: the reference's SGD with momentum 0.9) or 'adam' (torch.optim.Adam with weight_decay, fused into the step
                  kernel: DESIGN 4.21) -- the one that trains wide tables (--k 128) the reference's summed-loss SGD diverges on
   --lr           learning rate (default 0.001, config.py:27)
+  --model        'mf' (default) or 'lightgcn': the graph backbone (ultrare_amd/lightgcn.py, csrc/gcn.hip), trained shard after
+                 shard whatever --parallel says, artifacts under LightGCN_* with the parameters as base_user_mat / base_item_mat
+  --gcn-layers   propagations per side of the 'lightgcn' backbone, 0 .. 8 (default 2).  --layer stays the reference's unused DMF flag
   --data-dir / --save-dir   roots of data/ and result/ (default: ./data, ./result)
 """
 import argparse
@@ -41,6 +44,8 @@ parser.add_argument('--parallel', type=int, default=1, help='1 (default): shards
 parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', or 'rating-ot' (OT groups), 'rating-bkmeans', 'rating-bkmedoids', 'rating-blpa' (balanced k-means / k-medoids / label propagation groups) on the sparse rating matrix, no --group 0 run needed")
 parser.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adam'], help="'sgd' (reference) or 'adam'")
 parser.add_argument('--lr', type=float, default=None, help='learning rate (default 0.001)')
+parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn'], help="'mf' (reference) or 'lightgcn'")
+parser.add_argument('--gcn-layers', type=int, default=2, help="propagations per side of the 'lightgcn' backbone (0 .. 8)")
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -78,7 +83,8 @@ def main(argv=None):
 
     torch.manual_seed(42)   # the reference never seeds the CPU generator; a fixed run needs it
     param = InsParam(args.dataset, args.epoch, args.worker, args.layer, args.group, args.delper, args.deltype,
-                     k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr)
+                     k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr,
+                     model=args.model, gcn_layers=args.gcn_layers)
     ins = Instance(param, save_dir=args.save_dir)
 
     if args.group == 0:

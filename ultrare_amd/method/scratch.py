@@ -118,8 +118,14 @@ class Scratch(object):
                     'total_hr': [],
                     'time': []}
 
-        if self.model_type != 'mf':
-            raise NotImplementedError("model_type is always 'mf' on the published path (config.py:185-199)")
+        if self.model_type not in ('mf', 'lightgcn'):
+            raise NotImplementedError("model_type is 'mf' on the published path (config.py:185-199), or 'lightgcn' (ultrare_amd/lightgcn.py)")
+        if self.model_type == 'lightgcn':
+            # the graph backbone (engine.GcnJob): SGD only, gcn_layers propagations per side
+            from ..lightgcn import check_layers
+            if self.optimizer != 'sgd':
+                raise ValueError(f"model_type='lightgcn' trains with optimizer='sgd' only, not {self.optimizer!r}")
+            self.gcn_layers = check_layers(getattr(param, 'gcn_layers', 2))
         self.loss_fn = nn.MSELoss(reduction='sum')
         self.is_rmse = True
 
@@ -142,29 +148,33 @@ class Scratch(object):
         print('Using device:', self.device)
         seed_all(self.seed)                                 # scratch.py:54
         has_total = not _is_empty(test_total)
-        shard, init, perms = prepare_shard(train_data, self.n_user, self.n_item, self.k, self.epochs, has_total, given_model)
-        batch = as_loader(train_data).batch_size
         # verbose 0: nothing is printed per epoch, so the epochs run back to back, every epoch end is kept
         # on the device (snapshots) and the two test series of scratch.py:83-97 are computed afterwards
         # in four launches each (ure_eval_series); otherwise each epoch synchronises to print
         queued = verbose == 0
-        snap_mode = self._snap_mode()
-        series = queued and engine.TrainJob.snapshot_bytes([shard], self.epochs, self.k, snap_mode) <= snapshot_limit()
-        job = engine.TrainJob([shard], [init], [perms], self.k, batch, self.epochs, self.lr, self.lam, self.momentum,
-                              self.lr_decay, snapshots=snap_mode if series else False, final_only=series, epoch_reads=True,       # (tables are read at epoch ends only)
-                              **self._optimizer_args())
-        rng.release(perms)                                  # uploaded: the host buffer goes back to the pool
+        if self.model_type == 'lightgcn':
+            job, series = self._gcn_job(train_data, has_total, given_model), False     # (the per-epoch branch: no queued series)
+            n_train, device = job.graph.N, job.device
+        else:
+            shard, init, perms = prepare_shard(train_data, self.n_user, self.n_item, self.k, self.epochs, has_total, given_model)
+            batch = as_loader(train_data).batch_size
+            snap_mode = self._snap_mode()
+            series = queued and engine.TrainJob.snapshot_bytes([shard], self.epochs, self.k, snap_mode) <= snapshot_limit()
+            job = engine.TrainJob([shard], [init], [perms], self.k, batch, self.epochs, self.lr, self.lam, self.momentum,
+                                  self.lr_decay, snapshots=snap_mode if series else False, final_only=series, epoch_reads=True,       # (tables are read at epoch ends only)
+                                  **self._optimizer_args())
+            rng.release(perms)                                  # uploaded: the host buffer goes back to the pool
+            n_train, device = shard.N, shard.device
         test_ev = as_loader(test_data).eval_set()
         total_ev = as_loader(test_total).eval_set() if has_total else None
         before = [padded_tables(m)[:2] for m in self._models_before()]
-        n_train = shard.N
 
-        res = torch.zeros(self.epochs, 2, 3, dtype=torch.float64, device=shard.device) if queued else None
+        res = torch.zeros(self.epochs, 2, 3, dtype=torch.float64, device=device) if queued else None
         times = []
         if series:
             sets = (test_ev, total_ev if has_total else test_ev)
             job.run()
-            res = torch.zeros(2, self.epochs, 3, dtype=torch.float64, device=shard.device)
+            res = torch.zeros(2, self.epochs, 3, dtype=torch.float64, device=device)
             if has_total:
                 job.evaluate_series_pair(0, sets[0], sets[1], before, res[0], res[1])
             else:
@@ -212,15 +222,35 @@ class Scratch(object):
 
         U, V = job.tables(0)
         model = MF.from_tables(U.clone().contiguous(), V.clone().contiguous())
+        if self.model_type == 'lightgcn':                   # the tables above are the layer mean; the parameters travel with the model
+            model.base = tuple(t.clone().contiguous() for t in job.base_tables())
         job.close()
         self.save(model, save_dir, id)
         return model
 
+    def _gcn_job(self, train_data, has_total, given_model):
+        """prepare_shard and the job of a LightGCN request: the RNG stream is the MF request's (rng.mf_init, then the epochs' seeds),
+        the orders are the epochs' permutations as file positions."""
+        if not (_is_empty(given_model) or given_model == ''):
+            raise ValueError("given_model is not supported with model_type='lightgcn': the job starts from rng.mf_init")
+        loader = as_loader(train_data)
+        init = rng.mf_init(self.n_user, self.n_item, self.k, device=engine._device())
+        seeds = rng.epoch_seeds(self.epochs, has_total)
+        n = len(loader.dataset)
+        orders = rng.epoch_perms(seeds, n, threads=PERM_THREADS) if loader.shuffle else torch.arange(n, dtype=torch.int32).repeat(self.epochs, 1)
+        graph = engine.GcnGraph(*loader.dataset.triples(), self.n_user, self.n_item)
+        return engine.GcnJob(graph, init, orders, self.k, self.gcn_layers, loader.batch_size, self.epochs, self.lr, self.lam, self.momentum,
+                             self.lr_decay)
+
     def save(self, model, save_dir, id):
-        """scratch.py:131-144: model{id}.pth, user_mat{id}.npy, item_mat{id}.npy, log{id}.npy."""
+        """scratch.py:131-144: model{id}.pth, user_mat{id}.npy, item_mat{id}.npy, log{id}.npy; a LightGCN model's parameters beside
+        them as base_user_mat{id}.npy and base_item_mat{id}.npy."""
         from .utils import dist_rank
         if len(save_dir) > 0 and dist_rank()[0] == 0:       # several ranks running the same call: one set of files
             torch.save(model.state_dict(), save_dir + '/model' + str(id) + '.pth')
             np.save(save_dir + '/user_mat' + str(id), model.user_mat.weight.detach().cpu().numpy())
             np.save(save_dir + '/item_mat' + str(id), model.item_mat.weight.detach().cpu().numpy())
             np.save(save_dir + '/log' + str(id), self.log)
+            if getattr(model, 'base', None) is not None:
+                np.save(save_dir + '/base_user_mat' + str(id), model.base[0].cpu().numpy())
+                np.save(save_dir + '/base_item_mat' + str(id), model.base[1].cpu().numpy())

@@ -198,10 +198,21 @@ class Sisa(Scratch):
         self.n_group = n_group
         self.group_index = group_index
         self.parallel = bool(getattr(param, 'parallel', False))
+        if self.model_type == 'lightgcn':
+            self._gcn_one_rank()
+            if self.parallel:           # a GcnJob holds one shard: the shards train one after the other
+                import warnings
+                warnings.warn("model_type='lightgcn' trains its shards one after the other: parallel is ignored")
+                self.parallel = False
         self.epoch_logs = bool(getattr(param, 'epoch_logs', True))   # parallel mode: rebuild the per-epoch test logs
         self.model_list = []
         self.combiner = None
         self.folded = {}                # user -> group of the users fold_in added since the last learn
+
+    def _gcn_one_rank(self):
+        dist = _dist()
+        if self.model_type == 'lightgcn' and dist is not None and dist.get_world_size() > 1:
+            raise ValueError(f"model_type='lightgcn' runs on one rank, not {dist.get_world_size()}")
 
     def test(self, test_data, verbose, save_dir):
         dist = _dist()
@@ -467,6 +478,7 @@ class Sisa(Scratch):
         '''
         train_dlist:   list of dataloader[n_group]
         '''
+        self._gcn_one_rank()
         self.combiner = None            # fitted on the models this call replaces
         self.folded = {}                # the folded rows are replaced with the tables
         assert len(train_dlist) == self.n_group
@@ -649,6 +661,7 @@ class Sisa(Scratch):
         home shard like any other user; the folded users of every retrained shard leave self.folded, since their rows now
         come from that shard's training.
         '''
+        self._gcn_one_rank()
         self.combiner = None            # fitted on the deleted users' ratings: refit on the post-deletion loaders
         self.model_list = model_list
 

@@ -42,6 +42,9 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         utils.py:223-267  (block sums [4], grad [m, d], bandwidth) of the MMD
                                                                           loss on the rows `rows` of X, the first n1 the source
     torch.ops.ultrare.u2u_grad(X, rows, n1)             utils.py:75-78    (value, grad [m, d]) of trace(U^T Lap U), S - T bipartite
+    torch.ops.ultrare.gcn_propagate(off, idx, s_src, s_dst, X, add)
+                                                        (new)             one LightGCN propagation over a device CSR / CSC:
+                                                                          out[r] = [add[r] +] s_dst[r] sum_j s_src[j] X[j]
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -359,3 +362,31 @@ def u2u_grad(X: torch.Tensor, rows: torch.Tensor, n1: int) -> Tuple[torch.Tensor
 @u2u_grad.register_fake
 def _(X, rows, n1):
     return X.new_empty((), dtype=torch.float64), X.new_empty(rows.numel(), X.shape[1])
+
+
+@torch.library.custom_op('ultrare::gcn_propagate', mutates_args=())
+def gcn_propagate(off: torch.Tensor, idx: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor, X: torch.Tensor,
+                  add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """engine.gcn_propagate on the halves of a graph that are on the device already: off int64 [n_dst + 1], idx int32 [nnz],
+    s_src float32 [n_src], s_dst float32 [n_dst], X float32 [n_src, d] (the caller vouches for the index ranges)."""
+    from . import lightgcn
+    _dev(off, idx, s_src, s_dst, X, *([] if add is None else [add]))
+    if [off.dtype, idx.dtype, s_src.dtype, s_dst.dtype, X.dtype] != [torch.int64, torch.int32, torch.float32, torch.float32, torch.float32]:
+        raise ValueError('gcn_propagate takes (int64 offsets, int32 indices, float32 s_src, float32 s_dst, float32 X)')
+    n_dst, n_src = off.numel() - 1, s_src.numel()
+    if X.dim() != 2 or X.shape[0] != n_src or s_dst.numel() != n_dst or n_dst < 1 or idx.numel() < 1:
+        raise ValueError(f'gcn_propagate: {n_dst} rows over {n_src} sources do not fit X {tuple(X.shape)} and s_dst [{s_dst.numel()}]')
+    d = lightgcn.check_width(int(X.shape[1]))
+    X = X.contiguous()
+    if add is not None:
+        engine._gcn_table(add, n_dst, d, 'add', X.device)
+    out = torch.empty(n_dst, d, dtype=torch.float32, device=X.device)
+    nv.check(nv.lib().ure_gcn_propagate(nv.ptr(off.contiguous()), nv.ptr(idx.contiguous()), n_dst, n_src, nv.ptr(s_src.contiguous()),
+                                        nv.ptr(s_dst.contiguous()), nv.ptr(X), d, nv.ptr(add), None, nv.ptr(out), nv.stream_handle()),
+             'ure_gcn_propagate')
+    return out
+
+
+@gcn_propagate.register_fake
+def _(off, idx, s_src, s_dst, X, add=None):
+    return X.new_empty(off.numel() - 1, X.shape[1])
