@@ -20,7 +20,9 @@
 // targets pass leaves a (tile, bucket) count matrix, the bucket pass sums its columns -- every swap's place is fixed.  Beyond: one global add per
 // (tile, bucket) to count and one to reserve space:
 //   shuffle_words_kernel    one workgroup per permutation walks MT19937, 623 new words per barrier (the recurrence substituted into itself
-//                           twice), the raw words into t[].
+//                           twice, its three twist terms folded into one: the twist is linear), the raw words into t[].  The first step
+//                           is peeled (its words lack terms); every other reads its seven words at fixed offsets from one address of
+//                           a ring of 8,192 words in LDS whose first 512 are kept a second time behind its end, so no window wraps.
 //   shuffle_targets_kernel  one workgroup per (permutation, tile of 16,384 swaps): t[j] = j + temper(word) % (n - j) in place, and the
 //                           swaps counted per BUCKET = range of 1,024 targets (2,048 / 4,096 / 16,384 beyond 2^24 / 2^25 / 2^26 rows;
 //                           ranges of 2,048 / 4,096 targets measured 4-12 % / 35 % slower on a request's shapes).  A launch of records
@@ -34,7 +36,9 @@
 //                           in LDS when they fit (6,144 swaps; a permutation's last eight buckets, launched apart: 16,384 -- a target has
 //                           ln(n / (n - q)) members on average), else in memory, read back 256 targets at a time (consecutive targets, consecutive lists: one
 //                           coalesced stretch) -- and lane = target stores every member's link H[j] (the smallest member above it, a value,
-//                           or "go on at q") and the target's own value (Minv: the smallest member of all).
+//                           or "go on at q") and the target's own value (Minv: the smallest member of all).  Two launches: the light
+//                           buckets on a grid of a workgroup per bucket, the last eight of every permutation on a grid of EIGHT
+//                           workgroups per permutation (workgroup h takes bucket n_buckets - 8 + h).
 //   shuffle_resolve_kernel  one lane per row: Minv or the chase through H, divided by the batch size, stored as uint16.
 // A permutation's workgroups sit on ONE XCD (workgroup id mod 8 = permutation mod 8): its 20 bytes per row stay in that L2 while it fits.
 //
@@ -65,9 +69,13 @@ namespace ure {
 namespace {
 
 constexpr int kMtN = 624, kMtLag = 227;
-constexpr int kDrawBlock = 640;                  // ten wavefronts: lanes 0..622 own a word of the step
+constexpr int kDrawBlock = 640;                  // ten wavefronts: lanes 0..622 own a word of the step (five with two words each: measured slower)
 constexpr int kDrawWide = 623;                   // words per dependent step
-constexpr int kDrawRing = 8192;                  // the generator's words kept in LDS (a step reads 1,305 back)
+constexpr int kDrawRing = 8192;                  // the generator's words kept in LDS (a step reads 1,078 back and writes 623 ahead)
+constexpr int kDrawBack = 2 * kMtLag + kMtN;     // 1,078: a word's window starts this far behind it ...
+constexpr int kDrawMirror = 512;                 // ... and is 456 words long: the ring's first words are kept a second time behind its end
+static_assert(kDrawMirror >= 2 * kMtLag + 2, "a lane's window must not wrap");
+static_assert(kDrawRing - kMtN >= kDrawMirror, "the start block lies outside the mirrored head");
 constexpr int64_t kSegmentedRows = 1 << 21;      // permutations beyond this: the generator's stream in segments (mt_jump_dev.h)
 constexpr int kFewBuckets = 1024;                // ... of a launch whose permutations have at most 2^20 rows
 constexpr int kMaxBuckets = 16384;               // per permutation (LDS counters of the draw and bucket passes)
@@ -151,7 +159,9 @@ __device__ __forceinline__ perm_view view_of(unsigned *scratch, int perm, int64_
 // dependent step.  Substituted into itself twice,
 //     x[p] = x[p - 681] ^ F(p - 454) ^ F(p - 227) ^ F(p),
 // a step may be as wide as F(p) itself allows: 623 words (x[p - 623] must exist) -- 289 barriers per 180 k outputs instead of 793.  (The
-// first 454 words behind the seed block have no x[p - 681]: they take the form with one / two terms.)
+// first 454 words behind the seed block have no x[p - 681]: they take the form with one / two terms.)  f is linear over GF(2) in both of its
+// words -- a mask, a shift and a constant chosen by one bit --, so the three terms are ONE: f(a0, a1) ^ f(b0, b1) ^ f(c0, c1) =
+// f(a0 ^ b0 ^ c0, a1 ^ b1 ^ c1).
 __device__ __forceinline__ unsigned mt_mix(unsigned a, unsigned b)
 {
     const unsigned y = (a & 0x80000000u) | (b & 0x7fffffffu);
@@ -184,7 +194,7 @@ __global__ __launch_bounds__(kDrawBlock) void shuffle_words_kernel(const ure_per
                                                                    int64_t b_al, int range_log2, const unsigned *__restrict__ states, int J)
 {
     constexpr unsigned M = kDrawRing - 1;
-    __shared__ unsigned ring[kDrawRing];
+    __shared__ unsigned ring[kDrawRing + kDrawMirror];
     const int tid = threadIdx.x;
     const int perm = blockIdx.x / J, seg = blockIdx.x % J;
     if (perm >= n_perms) return;
@@ -202,33 +212,69 @@ __global__ __launch_bounds__(kDrawBlock) void shuffle_words_kernel(const ure_per
     const int64_t total_all = (int64_t)n - 1;
     if (w_lo >= total_all) return;
     const int total = (int)min<int64_t>(states ? jmp::kSegWords : total_all, total_all - w_lo);       // this segment's words
+    // (the start block takes the ring's LAST 624 places, none of them mirrored: see the static_assert at kDrawMirror)
     if (states) {
         const unsigned *blk = states + ((size_t)perm * J + seg) * kMtN;
-        for (int k = tid; k < kMtN; k += kDrawBlock) ring[((unsigned)k - kMtN) & M] = blk[k];
-    } else if (tid == 0) {
-        unsigned v = (unsigned)((unsigned long long)perms[perm].seed & 0xffffffffull);
-        ring[(0u - kMtN) & M] = v;
-        for (int j = 1; j < kMtN; ++j) {
-            v = 1812433253u * (v ^ (v >> 30)) + (unsigned)j;
-            ring[((unsigned)j - kMtN) & M] = v;
+        for (int k = tid; k < kMtN; k += kDrawBlock) ring[kDrawRing - kMtN + k] = blk[k];
+    } else if (tid < 64) {
+        // init_genrand is one dependent chain of 623 multiplies, ~8 us of the kernel whatever the permutation's size: the first wave walks
+        // it on the SCALAR unit (the seed is the same for every lane), hands word j to lane j % 16 and stores sixteen words at once --
+        // 2 us less than lane 0 walking it with vector instructions and a store per word
+        unsigned v = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)perms[perm].seed & 0xffffffffull));
+        constexpr int kAtOnce = 16;                             // (words held in scalar registers at a time: 32 and more spill)
+#pragma unroll 1
+        for (int j0 = 0; j0 < kMtN; j0 += kAtOnce) {
+            unsigned mine = 0u;
+#pragma unroll
+            for (int l = 0; l < kAtOnce; ++l) {
+                if (j0 + l > 0) v = 1812433253u * (v ^ (v >> 30)) + (unsigned)(j0 + l);
+                mine = tid == l ? v : mine;
+            }
+            if (tid < kAtOnce && j0 + tid < kMtN) ring[kDrawRing - kMtN + j0 + tid] = mine;
         }
     }
     __syncthreads();
+    // word g lives at ring[g & M], and once more at ring[kDrawRing + (g & M)] when that is inside the mirror
+    auto keep = [&](unsigned at, unsigned v) {
+        ring[at] = v;
+        if (at < (unsigned)kDrawMirror) ring[kDrawRing + at] = v;
+    };
     unsigned *out = P.t + w_lo;
+    // ---- the first step, peeled: the only one whose words lack terms (the first 227 have one, the next 227 two)
+    if (tid < kDrawWide && tid < total) {
+        const unsigned g = (unsigned)tid;
+        const bool two = g >= (unsigned)kMtLag, three = g >= 2u * kMtLag;
+        const unsigned a0 = ring[(g - kMtN) & M], a1 = ring[(g - kMtN + 1) & M];
+        const unsigned b0 = ring[(g - kMtLag - kMtN) & M], b1 = ring[(g - kMtLag - kMtN + 1) & M];
+        const unsigned c0 = ring[(g - 2 * kMtLag - kMtN) & M], c1 = ring[(g - 2 * kMtLag - kMtN + 1) & M];
+        const unsigned x = ring[(g - (three ? 3u * kMtLag : two ? 2u * kMtLag : (unsigned)kMtLag)) & M];
+        const unsigned v = x ^ mt_mix(a0 ^ (two ? b0 : 0u) ^ (three ? c0 : 0u), a1 ^ (two ? b1 : 0u) ^ (three ? c1 : 0u));
+        keep(g, v);
+        out[g] = v;
+    }
+    lds_barrier();
+    // ---- every other step: all three terms, the seven words of x[g] at FIXED offsets from ONE address -- x[g - 1078], x[g - 1077] |
+    // x[g - 851], x[g - 850] | x[g - 681] | x[g - 624], x[g - 623] are w[0], w[1] | w[227], w[228] | w[397] | w[454], w[455] of
+    // w = ring + ((g - 1078) & M); the mirror behind the ring's end is what keeps w[455] inside.  Window start, place, output pointer and
+    // the count of words left all advance by 623 per step.
+    unsigned rd = (unsigned)(kDrawWide + tid - kDrawBack) & M, wr = (unsigned)(kDrawWide + tid) & M;
+    unsigned *o = out + kDrawWide + tid;
+    int left = tid < kDrawWide ? total - kDrawWide - tid : 0;  // words from the lane's own of this step to the segment's end
 #pragma unroll 1
-    for (int g0 = 0; g0 < total; g0 += kDrawWide) {
-        const unsigned g = (unsigned)(g0 + tid);
-        if (tid < kDrawWide && (int)g < total) {
-            // (all seven reads at once -- one LDS round trip per step; the first 454 words behind the start block leave the terms they do not have out)
-            const bool two = g >= (unsigned)kMtLag, three = g >= 2u * kMtLag;
-            const unsigned a0 = ring[(g - kMtN) & M], a1 = ring[(g - kMtN + 1) & M];
-            const unsigned b0 = ring[(g - kMtLag - kMtN) & M], b1 = ring[(g - kMtLag - kMtN + 1) & M];
-            const unsigned c0 = ring[(g - 2 * kMtLag - kMtN) & M], c1 = ring[(g - 2 * kMtLag - kMtN + 1) & M];
-            const unsigned x = ring[(g - (three ? 3u * kMtLag : two ? 2u * kMtLag : (unsigned)kMtLag)) & M];
-            const unsigned v = x ^ mt_mix(a0, a1) ^ (two ? mt_mix(b0, b1) : 0u) ^ (three ? mt_mix(c0, c1) : 0u);
-            ring[g & M] = v;
-            out[g] = v;
+    for (int g0 = kDrawWide; g0 < total; g0 += kDrawWide) {
+        if (left > 0) {
+            const unsigned *w = ring + rd;
+            const unsigned c0 = w[0], c1 = w[1], b0 = w[kMtLag], b1 = w[kMtLag + 1];
+            const unsigned x = w[kDrawBack - 3 * kMtLag], a0 = w[kDrawBack - kMtN], a1 = w[kDrawBack - kMtN + 1];
+            __builtin_amdgcn_sched_barrier(0);                  // (all seven reads issued before the first is waited for: ONE LDS round trip per step)
+            const unsigned v = x ^ mt_mix(a0 ^ b0 ^ c0, a1 ^ b1 ^ c1);
+            keep(wr, v);
+            *o = v;
         }
+        rd = (rd + (unsigned)kDrawWide) & M;
+        wr = (wr + (unsigned)kDrawWide) & M;
+        o += kDrawWide;
+        left -= kDrawWide;
         lds_barrier();
     }
 }
@@ -487,10 +533,13 @@ __global__ __launch_bounds__(kLinkBlock) void shuffle_link_kernel(const ure_perm
     int perm, part;
     if (!place_of(parts_max, n_perms, &perm, &part)) return;
     const int n = perms[perm].n;
-    const int64_t q0l = (int64_t)part << RL;
-    if (q0l >= n) return;
+    if (n <= 0) return;
     const int n_buckets = (int)((((int64_t)n - 1) >> RL) + 1);
-    if ((part >= n_buckets - kHeavyParts) != (heavy != 0)) return;
+    // the light launch has a workgroup per bucket and leaves the last kHeavyParts alone; the heavy one has kHeavyParts workgroups per
+    // permutation (parts_max = kHeavyParts), workgroup h taking bucket n_buckets - kHeavyParts + h
+    if (heavy) part += n_buckets - kHeavyParts;
+    if (part < 0 || part >= n_buckets || (part >= n_buckets - kHeavyParts) != (heavy != 0)) return;
+    const int64_t q0l = (int64_t)part << RL;
     const unsigned q0 = (unsigned)q0l, q1 = (unsigned)min<int64_t>(n, q0l + kRange);
     const int R = (int)(q1 - q0);
     const perm_view P = view_of(scratch, perm, n_al, b_al);
@@ -660,7 +709,7 @@ struct link_launch {
     dim3 grid;
     hipStream_t st;
     const ure_perm_t *perms;
-    int n_perms, ranges;
+    int n_perms, parts;                                         // (parts: workgroups per permutation -- its buckets, or kHeavyParts)
     unsigned *scratch;
     int64_t n_al, b_al;
     int heavy;
@@ -669,11 +718,11 @@ struct link_launch {
     {
         if constexpr (RL <= kRecordRangeLog2) {
             if (records) {
-                hipLaunchKernelGGL((shuffle_link_kernel<RL, Stage, true>), grid, dim3(kLinkBlock), 0, st, perms, n_perms, ranges, scratch, n_al, b_al, heavy);
+                hipLaunchKernelGGL((shuffle_link_kernel<RL, Stage, true>), grid, dim3(kLinkBlock), 0, st, perms, n_perms, parts, scratch, n_al, b_al, heavy);
                 return;
             }
         }
-        hipLaunchKernelGGL((shuffle_link_kernel<RL, Stage, false>), grid, dim3(kLinkBlock), 0, st, perms, n_perms, ranges, scratch, n_al, b_al, heavy);
+        hipLaunchKernelGGL((shuffle_link_kernel<RL, Stage, false>), grid, dim3(kLinkBlock), 0, st, perms, n_perms, parts, scratch, n_al, b_al, heavy);
     }
 };
 
@@ -720,7 +769,7 @@ extern "C" int ure_device_shuffle_tags(const ure_perm_t *perms, int32_t n_perms,
     uint32_t *broken = scratch + ure_device_shuffle_tags_flag(n_max, n_perms);     // (never cleared here: the caller that reads it clears it when it makes the scratch)
     const int64_t slots = ((int64_t)n_perms + 7) / 8;
     const int64_t tiles = std::max<int64_t>(1, (n_max - 1 + kTile - 1) / kTile), ranges = ((n_max - 1) >> rl) + 1, rows = (n_max + kResolveRows - 1) / kResolveRows;
-    if (8 * slots * std::max(ranges, rows) > 0x7fffffffll)
+    if (8 * slots * std::max<int64_t>({ranges, rows, kHeavyParts}) > 0x7fffffffll)
         return fail(-1, "ure_device_shuffle_tags: %d permutations of up to %lld rows are too many for one launch", (int)n_perms, (long long)n_max);
     if (n_max > kSegmentedRows) {
         // millions of rows: the generator's stream in segments of 1,024 blocks, their start blocks by the jump tree -- one workgroup walking
@@ -752,8 +801,10 @@ extern "C" int ure_device_shuffle_tags(const ure_perm_t *perms, int32_t n_perms,
         hipLaunchKernelGGL((shuffle_targets_kernel<kMaxBuckets, false>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
         hipLaunchKernelGGL((shuffle_bucket_kernel<kMaxBuckets, false>), tile_grid, dim3(kTileBlock), 0, st, perms, (int)n_perms, (int)tiles, scratch, n_al, b_al, rl, mat);
     }
+    // The link pass: the light buckets with a workgroup per bucket, then the heavy ones with kHeavyParts workgroups per permutation
     for (int heavy = 0; heavy < 2; ++heavy) {
-        const link_launch at{records, dim3((unsigned)(8 * slots * ranges)), st, perms, (int)n_perms, (int)ranges, scratch, n_al, b_al, heavy};
+        const int64_t parts = heavy ? kHeavyParts : ranges;
+        const link_launch at{records, dim3((unsigned)(8 * slots * parts)), st, perms, (int)n_perms, (int)parts, scratch, n_al, b_al, heavy};
         if (rl == 10 && !heavy) at.go<10, kStage10>();
         if (rl == 10 && heavy) at.go<10, kStageHeavy>();
         if (rl == 11 && !heavy) at.go<11, kStage>();
