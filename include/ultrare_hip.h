@@ -225,7 +225,10 @@ int ure_job_touch_rows(ure_job_t *job, int64_t *pairs, int64_t *window_steps);
  * (capacity bytes; out == NULL: only *bytes is set).  which: 0 step_begin u32 [steps + 1] (first sorted slot of every step, then
  * their number) | 1 step_item u32 [steps + 1] | 2 items int32 [n][4] {row id | buffer << 31, first sorted slot, end, steps until
  * the row's next own step | class << 16} | 3 sorted slots u32 [n][4] {opposite id | buffer << 31, rating bits, row id,
- * step | class << 16} | 4 W u64 [words][rows] | 5 heavy_cnt u32 [steps] | 6 heavy_cum u32 [steps][257].           */
+ * step | class << 16} | 4 W u64 [words][rows] | 5 heavy_cnt u32 [steps] | 6 heavy_cum u32 [steps][257].
+ * which = 2 and 3 have their lengths in device words that the shard's first epoch start writes: they are refused until
+ * ure_job_train has enqueued tick 0.  The arrays of fixed size are readable at any time; before tick 0 they hold what
+ * ure_job_create left in them (W: zeros; the others: whatever the block came with, URE_BLOCK_FILL's byte when that is set). */
 int ure_job_index_read(ure_job_t *job, int shard, int which, void *out, int64_t capacity, int64_t *bytes);
 /* Measurement aid (bench.py's roofline leg): the same ticks, each kernel launch
  * bracketed by a pair of HIP events on `stream`; synchronises the stream and returns

@@ -134,7 +134,7 @@ def test_every_bound_name_is_classified():
             assert name.startswith(('ure_host_', 'ure_ot_')) or name in ('ure_abi_version', 'ure_source_hash', 'ure_last_error', 'ure_device_info'), name
         if klass == 'stateful':
             assert name.startswith('ure_job_') and '::test_' in note
-        if klass == 'prefilled':
+        if klass in ('prefilled', 'stateful'):
             path, test = note.split('::')
             assert test in open(__file__.rsplit('tests', 1)[0] + path).read(), note
     covered = {c.entry for c in M.CASES}

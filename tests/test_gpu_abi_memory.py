@@ -46,8 +46,8 @@ INVENTORY = {
     'ure_host_assign_desc_f64': ('host', ''), 'ure_host_kmeans_assign': ('host', ''),
     'ure_ot_assign': ('host', 'the exact LP: host memory in and out'), 'ure_ot_assign_warm': ('host', 'the exact LP: host memory in and out'),
     'ure_ot_potentials': ('host', 'reads a device matrix; its outputs are host memory and its device state is its own allocation'),
-    # stateful: the job's memory comes from csrc/block_cache.cpp
-    **{n: ('stateful', 'tests/test_gpu_touch.py::test_touch_memory_from_the_block_cache_is_filled_again') for n in (
+    # stateful: the job's memory comes from csrc/block_cache.cpp and keeps the job's rule of DESIGN 4.20 (whole jobs on poisoned memory)
+    **{n: ('stateful', 'tests/test_gpu_job_memory.py::test_a_job_gives_the_same_bytes_on_memory_of_every_fill') for n in (
         'ure_job_create', 'ure_job_destroy', 'ure_job_shard_steps', 'ure_job_ticks', 'ure_job_train', 'ure_job_materialize',
         'ure_job_touch_rows', 'ure_job_index_read', 'ure_job_train_profiled')},
     # sizers: host code, run by tests/test_cpu_abi_arena.py on the shapes of the cases below

@@ -104,6 +104,11 @@ def check_sisa_against_reference(S, E, parallel, tmp_path):
     for key in ('train_loss', 'test_rmse', 'test_ndcg', 'test_hr', 'total_rmse', 'total_ndcg', 'total_hr'):
         np.testing.assert_allclose(sisa.log[key], g[f'{tag}_learn_log_{key}'], rtol=RTOL, err_msg=key)
     assert len(np.load(tmp_path / f'log{S}.npy', allow_pickle=True).item()['total_hr']) == S * E      # D8
+    # what the request handed back, as bytes (tests/test_gpu_job_memory.py compares them between runs on differently filled memory)
+    as_bytes = lambda x: (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x, dtype=np.float64)).tobytes()
+    handed_back = {'learn U merged': as_bytes(ml[0].user_mat.weight), 'learn log0': as_bytes([log0['total_rmse'], log0['total_ndcg'], log0['total_hr']])}
+    handed_back.update({f'learn V{i}': as_bytes(ml[i].item_mat.weight) for i in range(S)})
+    handed_back.update({f'learn log {key}': as_bytes(sisa.log[key]) for key in ('train_loss', 'test_rmse', 'test_ndcg', 'test_hr', 'total_rmse', 'total_ndcg', 'total_hr')})
 
     for name in ('A', 'B'):
         t = f'{tag}_un{name}'
@@ -123,6 +128,11 @@ def check_sisa_against_reference(S, E, parallel, tmp_path):
         np.testing.assert_allclose([l0['total_rmse'], l0['total_ndcg'], l0['total_hr']], g[t + '_log0'], rtol=RTOL)
         for key in ('train_loss', 'test_rmse', 'total_rmse', 'total_ndcg', 'total_hr'):
             np.testing.assert_allclose(s2.log[key], g[f'{t}_log_{key}'], rtol=RTOL, err_msg=key)
+            handed_back[f'unlearn {name} log {key}'] = as_bytes(s2.log[key])
+        handed_back[f'unlearn {name} U merged'] = as_bytes(ml2[0].user_mat.weight)
+        handed_back.update({f'unlearn {name} V{i}': as_bytes(ml2[i].item_mat.weight) for i in range(S)})
+        handed_back[f'unlearn {name} log0'] = as_bytes([l0['total_rmse'], l0['total_ndcg'], l0['total_hr']])
+    return handed_back
 
 
 def test_parallel_equals_sequential_bitwise(tmp_path):

@@ -298,6 +298,8 @@ extern "C" int ure_job_create(const ure_shard_t *shards, int n_shards, ure_job_t
     std::unique_ptr<ure_job_t, decltype(&ure_job_destroy)> hold(reinterpret_cast<ure_job_t *>(job), ure_job_destroy);
     ure::plan_job(job, shards, n_shards);
     const hipError_t e = ure::upload_job(job);
+    if (e != hipSuccess && ure::block_fill_setting(nullptr) < 0)
+        return ure::fail(-1, "ure_job_create: URE_BLOCK_FILL='%s' is not a byte (0 .. 255, decimal or 0x..): no block was handed out", std::getenv("URE_BLOCK_FILL"));
     if (e != hipSuccess) return ure::fail((int)e, "ure_job_create: %s", hipGetErrorString(e));
     *out = hold.release();
     return 0;

@@ -986,10 +986,16 @@ int ure_job_index_read(ure_job_t *j, int shard, int which, void *out, int64_t ca
     if (!job->index) return fail(-1, "ure_job_index_read: the job is not in touch_mode 3");
     const ure_shard_t &S = job->host[(size_t)shard];
     const shard_aux &A = job->aux_host[(size_t)shard];
+    // items and sslot are as long as the device words step_item[steps] and step_begin[steps] say, which the shard's first epoch start
+    // writes (every shard's is part of tick 0): before it they hold whatever the block came with.  The arrays of fixed size are readable at any time.
+    if ((which == 2 || which == 3) && job->next_tick == 0)
+        return fail(-1, "ure_job_index_read: which = %d (%s) has no length before the shard's first epoch start has been enqueued (ure_job_train from tick 0)", which, which == 2 ? "items" : "sslot");
     URE_HIP(hipDeviceSynchronize());
     uint32_t n_items = 0, total = 0;
-    URE_HIP(hipMemcpy(&n_items, A.step_item + A.steps, 4, hipMemcpyDeviceToHost));
-    URE_HIP(hipMemcpy(&total, A.step_begin + A.steps, 4, hipMemcpyDeviceToHost));
+    if (job->next_tick > 0) {
+        URE_HIP(hipMemcpy(&n_items, A.step_item + A.steps, 4, hipMemcpyDeviceToHost));
+        URE_HIP(hipMemcpy(&total, A.step_begin + A.steps, 4, hipMemcpyDeviceToHost));
+    }
     const void *src = nullptr;
     size_t n = 0;
     switch (which) {

@@ -82,6 +82,8 @@ void launch_tag_prep(const ure_job *job, int64_t tick, hipStream_t st, int pass)
 // block_cache.cpp: device memory the library owns, recycled from job to job (rounded up to 256 KiB; the caller fills it)
 hipError_t block_malloc(void **out, size_t bytes);
 void block_free(void *p);
+// URE_BLOCK_FILL: 0 = unset or empty, 1 = a byte (-> *byte; block_malloc fills every block it hands out with it), -1 = anything else (block_malloc fails)
+int block_fill_setting(int *byte);
 
 // Global-memory accessors.  A pointer that a kernel reads out of a descriptor in memory (struct
 // ure_shard) has no address space the compiler can see, so a plain dereference becomes a flat_*
