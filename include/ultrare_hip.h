@@ -779,5 +779,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_csr_pair.h"
 /* The LightGCN backbone (csrc/gcn.hip): propagation over a shard's CSR / CSC, the loss-gradient walks and the SGD update. */
 #include "ultrare_gcn.h"
+/* BPR training with device-side negative sampling (csrc/bpr.hip): the per-epoch draw and negative index, the pairwise loss walks. */
+#include "ultrare_bpr.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -188,6 +188,18 @@ _GCN_PROTOTYPES = {
 }
 GCN_EXPORTS = tuple(_GCN_PROTOTYPES)
 
+# include/ultrare_bpr.h (BPR training with device-side negative sampling, csrc/bpr.hip): a table of its own, as the header is;
+# tests/test_cpu_bpr.py holds the table, the header and the library to each other, tests/test_gpu_bpr.py runs every entry in guard zones.
+_BPR_PROTOTYPES = {
+    'ure_bpr_sample': (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint64, _i32, _vp, _vp]),
+    'ure_bpr_index_scratch': (_i64, [_i64, _i64]),
+    'ure_bpr_index': (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'ure_bpr_coef': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'ure_bpr_grad_user': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
+    'ure_bpr_grad_item': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i32, _vp, _vp]),
+}
+BPR_EXPORTS = tuple(_BPR_PROTOTYPES)
+
 _lib = None
 
 
@@ -203,7 +215,7 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

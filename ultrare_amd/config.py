@@ -8,6 +8,8 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
   +   InsParam(..., k=16, parallel=False)    optional embedding width and shard-parallel mode
   +   InsParam(..., optimizer='sgd', lr=None) optional optimizer ('adam': engine.TrainJob) and learning rate (None: 0.001)
   +   InsParam(..., model='mf', gcn_layers=2) optional backbone ('lightgcn': engine.GcnJob, artifacts under LightGCN_*) and its layers
+  +   InsParam(..., loss='mse')              optional training loss ('bpr': pairwise, negatives drawn on the device; needs model='lightgcn';
+                                             artifacts under LightGCN_bpr_*)
   +   dataset 'toy' is usable end to end     (the reference only has its batch size)
 """
 import os
@@ -32,7 +34,7 @@ DATASETS = {
 
 class InsParam(object):
     def __init__(self, dataset='toy', epochs=50, n_worker=24, layers=[32], n_group=2, del_per=2, del_type='test',
-                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2):
+                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2, loss='mse'):
         # model param
         self.k = k  # dimension of embedding (config.py:19 hard-codes 16)
         self.lam = 0.1  # regularization coefficient
@@ -59,6 +61,11 @@ class InsParam(object):
             raise ValueError(f"model {model!r}: 'mf' or 'lightgcn'")
         if model == 'lightgcn' and optimizer != 'sgd':
             raise ValueError(f"model='lightgcn' trains with optimizer='sgd' only, not {optimizer!r}")
+        if loss not in ('mse', 'bpr'):
+            raise ValueError(f"loss {loss!r}: 'mse' or 'bpr'")
+        if loss == 'bpr' and model != 'lightgcn':
+            raise ValueError("loss='bpr' trains with model='lightgcn' only: --model lightgcn --gcn-layers 0 is BPR-MF")
+        self.loss = loss                        # 'mse' (the reference's), or 'bpr' (ultrare_amd/bpr.py)
         from .lightgcn import check_layers
         self.model = model                      # the backbone: 'mf', or 'lightgcn' (ultrare_amd/lightgcn.py)
         self.gcn_layers = check_layers(gcn_layers)   # propagations per side of the 'lightgcn' backbone (`layers` above is the DMF flag)
@@ -211,7 +218,8 @@ class Instance(object):
     def _model(self):
         """(model_type, artifact prefix) of the backbone the parameters name."""
         model = getattr(self.param, 'model', 'mf')
-        return model, {'mf': 'MF_', 'lightgcn': 'LightGCN_'}[model]
+        prefix = {'mf': 'MF_', 'lightgcn': 'LightGCN_'}[model]
+        return model, prefix + ('bpr_' if getattr(self.param, 'loss', 'mse') == 'bpr' else '')
 
     def runFull(self, is_save=True, verbose=1):
         '''model MF (or the backbone of param.model)'''

@@ -4,31 +4,11 @@
 // One shape serves the propagate and the two gradient walks: a group of G = d / 4 lanes owns an output row and holds its d
 // columns as one float4 per lane (1 lane at d = 4, a whole wavefront at d = 256); the row's entries are fetched a tile of G at
 // a time, one per lane, and handed round with group_read (csr_lanes.h); the chain of a (row, column) is one lane's, in
-// ascending entry position.  Every float operation is a rounded one of its own (__fmul_rn / __fadd_rn: never contracted).
-#include "csr_lanes.h"
-#include "score_dot.h"
+// ascending entry position.  Every float operation is a rounded one of its own (gcn_ops.h).
+#include "gcn_ops.h"
 
 namespace ure {
 namespace {
-
-__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-// acc + s * v, the product and the sum rounded separately
-__device__ __forceinline__ float4 f4_mul_add(float4 acc, float s, float4 v)
-{
-    acc.x = __fadd_rn(acc.x, __fmul_rn(s, v.x));
-    acc.y = __fadd_rn(acc.y, __fmul_rn(s, v.y));
-    acc.z = __fadd_rn(acc.z, __fmul_rn(s, v.z));
-    acc.w = __fadd_rn(acc.w, __fmul_rn(s, v.w));
-    return acc;
-}
-__device__ __forceinline__ float4 f4_scale(float s, float4 v)
-{
-    return make_float4(__fmul_rn(s, v.x), __fmul_rn(s, v.y), __fmul_rn(s, v.z), __fmul_rn(s, v.w));
-}
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b)
-{
-    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
-}
 
 // out[r] = [add[r] +] s_dst[r] * sum_j s_src[j] X[j] over row r's entries.  Lane `sub` fetches entry p0 + sub AND that
 // neighbour's s, so the dependent reads of a tile are in flight together, and the next tile's travel while this one is added;
@@ -232,31 +212,10 @@ __global__ __launch_bounds__(256) void gcn_step_loss_kernel(const double *__rest
     if (threadIdx.x == 0) loss[0] = (first ? 0.0 : loss[0]) + part[0];
 }
 
-inline unsigned stream_blocks(int64_t items)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock, 4096));
-}
-
-// [a, a + na) and [b, b + nb) bytes share no byte
-inline bool apart(const void *a, int64_t na, const void *b, int64_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x + (uintptr_t)na <= y || y + (uintptr_t)nb <= x;
-}
-
-inline bool width_ok(int d) { return d >= 4 && d <= 256 && pow2(d); }
-
 }  // namespace
 }  // namespace ure
 
 using namespace ure;
-
-#define URE_GCN_SIZES(n_dst, n_src, d)               \
-    do {                                             \
-        URE_ARG(n_dst >= 1 && n_dst <= INT32_MAX);   \
-        URE_ARG(n_src >= 1 && n_src <= INT32_MAX);   \
-        URE_ARG(width_ok(d));                        \
-    } while (0)
 
 extern "C" int ure_gcn_propagate(const int64_t *off, const int32_t *idx, int64_t n_dst, int64_t n_src, const float *s_src, const float *s_dst,
                                  const float *X, int32_t d, const float *add, float *sum, float *out, void *stream)

@@ -2022,10 +2022,112 @@ def gcn_sgd_step(w, m, g, lr, lam, mu, first, gscale=1.0, stream=None):
                                        float(np.float32(mu)), int(bool(first)), nv.stream_handle(stream)), 'ure_gcn_sgd_step')
 
 
+# ---- BPR (csrc/bpr.hip, include/ultrare_bpr.h; the contract is bpr.py) ---------------------------------------------------------
+def bpr_prepare(graph):
+    """The users' distinct items of a GcnGraph on its device (graph.off_d, graph.col_d), made once per graph on the host.  A user
+    with triples and no item left to draw raises ValueError before any device work."""
+    if getattr(graph, 'off_d', None) is None:
+        from . import bpr
+        off_d, col_d = bpr.distinct_csr(graph.host)
+        bpr.check_negatives(graph.host, off_d)
+        graph.col_d = torch.from_numpy(col_d).to(graph.device)
+        graph.off_d = torch.from_numpy(off_d).to(graph.device)
+    return graph
+
+
+def _bpr_sample(graph, key, epoch, neg, st):
+    g = graph
+    nv.check(nv.lib().ure_bpr_sample(nv.ptr(g.off_d), nv.ptr(g.col_d), g.col_d.numel(), nv.ptr(g.row_u), nv.ptr(g.pos), g.nnz, g.n_user, g.n_item,
+                                     int(key) & 0xFFFFFFFFFFFFFFFF, int(epoch), nv.ptr(neg), st), 'ure_bpr_sample')
+
+
+def _bpr_index(graph, neg, off_n, map_n, usr_n, scratch, st):
+    nv.check(nv.lib().ure_bpr_index(nv.ptr(neg), nv.ptr(graph.row_u), graph.nnz, graph.n_item, nv.ptr(off_n), nv.ptr(map_n), nv.ptr(usr_n),
+                                    nv.ptr(scratch), scratch.numel(), st), 'ure_bpr_index')
+
+
+def _bpr_int_vector(t, graph, what):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise nv.NativeError(f'{what} must be on the HIP device (no CPU fallback)')
+    if not (t.dtype == torch.int32 and t.shape == (graph.nnz,) and t.device == graph.device and t.is_contiguous()):
+        raise ValueError(f'{what} must be a contiguous int32 [{graph.nnz}] tensor on {graph.device}')
+    return t
+
+
+def bpr_negatives(graph, key, epoch, stream=None):
+    """bpr.sample_ref on the device: the negative item of every CSR entry in `epoch` under `key` (bpr.stream_key) -> int32 [nnz].
+    Nothing synchronises."""
+    if isinstance(epoch, bool) or not isinstance(epoch, (int, np.integer)) or not 0 <= epoch < 2 ** 31:
+        raise ValueError(f'epoch must be an integer in 0 .. 2^31 - 1, not {epoch!r}')
+    bpr_prepare(graph)
+    neg = torch.empty(graph.nnz, dtype=torch.int32, device=graph.device)
+    _bpr_sample(graph, key, epoch, neg, nv.stream_handle(stream))
+    _csr_held_for(stream, neg)
+    return neg
+
+
+def bpr_neg_index(graph, neg, stream=None):
+    """bpr.neg_index_ref on the device: -> (off_n int64 [n_item + 1], map_n int32 [nnz], usr_n int32 [nnz]).  Nothing synchronises."""
+    _bpr_int_vector(neg, graph, 'neg')
+    dev = graph.device
+    off_n = torch.empty(graph.n_item + 1, dtype=torch.int64, device=dev)
+    map_n, usr_n = torch.empty_like(neg), torch.empty_like(neg)
+    scratch = torch.empty(int(nv.lib().ure_bpr_index_scratch(graph.nnz, graph.n_item)), dtype=torch.uint8, device=dev)
+    _bpr_index(graph, neg, off_n, map_n, usr_n, scratch, nv.stream_handle(stream))
+    _csr_held_for(stream, off_n, map_n, usr_n, scratch)
+    return off_n, map_n, usr_n
+
+
+def _bpr_walks(graph, tag, step, U, V, neg, index, w, x, d, Gu, Gi, row_loss, st):
+    g, L = graph, nv.lib()
+    off_n, map_n, usr_n = index
+    nv.check(L.ure_bpr_grad_user(nv.ptr(g.off_u), nv.ptr(g.col), nv.ptr(neg), nv.ptr(tag), nv.ptr(w), nv.ptr(x), g.n_user, g.n_item, g.nnz, int(step),
+                                 nv.ptr(V), d, nv.ptr(Gu), nv.ptr(row_loss), st), 'ure_bpr_grad_user')
+    nv.check(L.ure_bpr_grad_item(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(off_n), nv.ptr(map_n), nv.ptr(usr_n), nv.ptr(tag), nv.ptr(w),
+                                 g.n_item, g.n_user, g.nnz, int(step), nv.ptr(U), d, nv.ptr(Gi), st), 'ure_bpr_grad_item')
+
+
+def bpr_loss_grad(graph, tag, step, U, V, neg, index=None, coef=None, stream=None):
+    """bpr.loss_grad_ref of the batch {CSR entries with tag == step} under the final tables (U, V) [rows, d], the epoch's negatives
+    neg and their index (default: made here): -> (G_u, G_i, loss float64 [1] on the device, w, x, s_pos, s_neg -- [nnz] in CSR order,
+    +0.0 outside the batch).  coef = (w, x): the walks run on these given arrays and the coefficient pass is left out (s_pos and
+    s_neg are then None).  Nothing synchronises."""
+    from . import lightgcn
+    if not (torch.is_tensor(U) and U.is_cuda and torch.is_tensor(V) and V.is_cuda):
+        raise nv.NativeError('bpr_loss_grad runs on the HIP device only (no CPU fallback)')
+    d = lightgcn.check_width(int(U.shape[1]) if U.dim() == 2 else 0)
+    _gcn_table(U, graph.n_user, d, 'U', graph.device)
+    _gcn_table(V, graph.n_item, d, 'V', graph.device)
+    _bpr_int_vector(tag, graph, 'tag')
+    _bpr_int_vector(neg, graph, 'neg')
+    g, L, dev, st = graph, nv.lib(), graph.device, nv.stream_handle(stream)
+    if index is None:
+        index = bpr_neg_index(graph, neg, stream)
+    sp = sn = None
+    if coef is None:
+        w, x, sp, sn = (torch.empty(g.nnz, dtype=torch.float32, device=dev) for _ in range(4))
+        nv.check(L.ure_bpr_coef(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(neg), nv.ptr(tag), g.nnz, int(step), nv.ptr(U), nv.ptr(V), g.n_user, g.n_item, d,
+                                nv.ptr(w), nv.ptr(x), nv.ptr(sp), nv.ptr(sn), st), 'ure_bpr_coef')
+    else:
+        w, x = coef
+        for name, t in (('w', w), ('x', x)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.shape == (g.nnz,) and t.device == dev and t.is_contiguous()):
+                raise ValueError(f'{name} must be a contiguous float32 [{g.nnz}] tensor on {dev}')
+    Gu, Gi = torch.empty_like(U), torch.empty_like(V)
+    row_loss, loss = torch.empty(g.n_user, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float64, device=dev)
+    _bpr_walks(g, tag, step, U, V, neg, index, w, x, d, Gu, Gi, row_loss, st)
+    nv.check(L.ure_gcn_step_loss(nv.ptr(row_loss), g.n_user, 1, nv.ptr(loss), st), 'ure_gcn_step_loss')
+    _csr_held_for(stream, Gu, Gi, row_loss, loss, w, x, *index, *([sp, sn] if coef is None else []))
+    return Gu, Gi, loss, w, x, sp, sn
+
+
 class GcnJob:
     """One shard trained with the LightGCN backbone (lightgcn.train_ref in float32, bit for bit): per step a forward of `layers`
     propagations per side, the residual pass and the two masked gradient walks, `layers` more propagations back, and one SGD
     update of every row of the parameters.  What Scratch._train uses of a TrainJob is here under the same names.
+    loss='bpr' (bpr.train_ref in float32; bit for bit but for the coefficient w, which is held to one ulp) trains the pairwise BPR
+    loss instead: the negatives (under `key`, bpr.stream_key) and their index are made on the device at each epoch's first step,
+    and the coefficient pass and the two BPR walks stand where the residual pass and the masked walks stand.
 
     graph  : GcnGraph
     init   : (P0 [n_user, k], Q0 [n_item, k]) float32 numpy arrays or tensors
@@ -2033,8 +2135,13 @@ class GcnJob:
 
     _TABLES = ('W', 'M', 'G', 'S', 'Xa', 'Xb', 'Star')
 
-    def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50):
+    def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50, loss='mse', key=0):
         from . import lightgcn
+        if loss not in ('mse', 'bpr'):
+            raise ValueError(f"loss {loss!r}: 'mse' or 'bpr'")
+        if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= key < 2 ** 64:
+            raise ValueError(f'key must be an integer in 0 .. 2^64 - 1, not {key!r}')
+        self.loss, self.key = loss, int(key)
         self.layers = lightgcn.check_layers(layers)
         self.graph, self.k, self.d = graph, int(k), pad_dim(int(k))
         self.batch, self.epochs, self.device = int(batch), int(epochs), graph.device
@@ -2054,6 +2161,8 @@ class GcnJob:
                 raise ValueError(f'orders[{e}] is not a permutation of 0 .. {graph.N - 1}')
             file_tags[e, o] = step_of
         # StepLR as engine.TrainJob makes it: float32 values
+        if loss == 'bpr':
+            bpr_prepare(graph)                              # (refuses a user without a negative)
         self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
         self._lam, self._mu = float(np.float32(lam)), float(np.float32(momentum))
         self._c = float(lightgcn.layer_scale(self.layers))
@@ -2070,6 +2179,12 @@ class GcnJob:
         self._err = torch.zeros(graph.nnz, dtype=torch.float32, device=dev)
         self._row_loss = torch.zeros(graph.n_user, dtype=torch.float64, device=dev)
         self._sse = torch.zeros(max(self.epochs, 1), dtype=torch.float64, device=dev)
+        self._bpr = None
+        if loss == 'bpr':        # 16 bytes per rating and 8 per item beside the job's own, and the sort's scratch
+            ints = lambda: torch.zeros(graph.nnz, dtype=torch.int32, device=dev)
+            self._bpr = dict(neg=ints(), map_n=ints(), usr_n=ints(), off_n=torch.zeros(graph.n_item + 1, dtype=torch.int64, device=dev),
+                             w=torch.zeros(graph.nnz, dtype=torch.float32, device=dev),
+                             scratch=torch.zeros(int(nv.lib().ure_bpr_index_scratch(graph.nnz, graph.n_item)), dtype=torch.uint8, device=dev))
         self.done = 0            # optimizer steps run
         self._star_at = -1       # the step count Star belongs to
         self.ticks = self.epochs * self.steps
@@ -2112,12 +2227,17 @@ class GcnJob:
         self._forward(stream)
         U, V = self._sides(t['Star'])
         Gu, Gi = self._sides(t['G'])
-        nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
-                                    g.n_item, self.d, nv.ptr(self._err), None, st), 'ure_gcn_residual')
-        nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(self._tag), nv.ptr(self._err), g.n_user, g.n_item, g.nnz, s, nv.ptr(V),
-                                self.d, nv.ptr(Gu), nv.ptr(self._row_loss), st), 'ure_gcn_grad')
-        nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(self._tag), nv.ptr(self._err), g.n_item, g.n_user, g.nnz, s,
-                                nv.ptr(U), self.d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
+        if self._bpr is not None:
+            b = self._bpr
+            index = (b['off_n'], b['map_n'], b['usr_n'])
+            if s == 0:                                      # this epoch's negatives and their index
+                _bpr_sample(g, self.key, e, b['neg'], st)
+                _bpr_index(g, b['neg'], *index, b['scratch'], st)
+            nv.check(L.ure_bpr_coef(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(b['neg']), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
+                                    g.n_item, self.d, nv.ptr(b['w']), nv.ptr(self._err), None, None, st), 'ure_bpr_coef')
+            _bpr_walks(g, self._tag, s, U, V, b['neg'], index, b['w'], self._err, self.d, Gu, Gi, self._row_loss, st)
+        else:
+            self._mse_grad(g, s, U, V, Gu, Gi, st)
         nv.check(L.ure_gcn_step_loss(nv.ptr(self._row_loss), g.n_user, int(s == 0), self._sse[e:].data_ptr(), st), 'ure_gcn_step_loss')
         src = t['G']
         for l in range(self.layers):                        # Horner: H^l = G + A H^(l-1)
@@ -2127,6 +2247,15 @@ class GcnJob:
         nv.check(L.ure_gcn_sgd_step(nv.ptr(t['W']), nv.ptr(t['M']), nv.ptr(src), src.numel(), self._c, float(self._lr_host[e]), self._lam, self._mu,
                                     int(self.done == 0), st), 'ure_gcn_sgd_step')
         self.done += 1
+
+    def _mse_grad(self, g, s, U, V, Gu, Gi, st):
+        L = nv.lib()
+        nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
+                                    g.n_item, self.d, nv.ptr(self._err), None, st), 'ure_gcn_residual')
+        nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(self._tag), nv.ptr(self._err), g.n_user, g.n_item, g.nnz, s, nv.ptr(V),
+                                self.d, nv.ptr(Gu), nv.ptr(self._row_loss), st), 'ure_gcn_grad')
+        nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(self._tag), nv.ptr(self._err), g.n_item, g.n_user, g.nnz, s,
+                                nv.ptr(U), self.d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
 
     # ---- what Scratch._train uses of a job -----------------------------------------------------------------------------
     def steps_per_epoch(self, s=0):
@@ -2165,7 +2294,14 @@ class GcnJob:
     def epoch_sse(self, s=0):
         """Per-epoch sum of squared training errors (host float64 array; synchronises)."""
         assert s == 0
+        if self.loss != 'mse':
+            raise ValueError(f"epoch_sse is the MSE job's: a loss={self.loss!r} job reports epoch_loss()")
+        return self._sse[:self.epochs].cpu().numpy()
+
+    def epoch_loss(self, s=0):
+        """Per-epoch sum of the steps' batch losses, whatever the loss (host float64 array; synchronises)."""
+        assert s == 0
         return self._sse[:self.epochs].cpu().numpy()
 
     def close(self):
-        self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = None
+        self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = self._bpr = None

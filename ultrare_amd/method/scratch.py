@@ -126,6 +126,12 @@ class Scratch(object):
             if self.optimizer != 'sgd':
                 raise ValueError(f"model_type='lightgcn' trains with optimizer='sgd' only, not {self.optimizer!r}")
             self.gcn_layers = check_layers(getattr(param, 'gcn_layers', 2))
+        # the training loss: 'mse' (the reference's), or 'bpr' -- pairwise, negatives drawn on the device (ultrare_amd/bpr.py)
+        self.loss = getattr(param, 'loss', 'mse')
+        if self.loss not in ('mse', 'bpr'):
+            raise ValueError(f"loss {self.loss!r}: 'mse' or 'bpr'")
+        if self.loss == 'bpr' and self.model_type != 'lightgcn':
+            raise ValueError("loss='bpr' trains with model='lightgcn' only: --model lightgcn --gcn-layers 0 is BPR-MF")
         self.loss_fn = nn.MSELoss(reduction='sum')
         self.is_rmse = True
 
@@ -153,7 +159,7 @@ class Scratch(object):
         # in four launches each (ure_eval_series); otherwise each epoch synchronises to print
         queued = verbose == 0
         if self.model_type == 'lightgcn':
-            job, series = self._gcn_job(train_data, has_total, given_model), False     # (the per-epoch branch: no queued series)
+            job, series = self._gcn_job(train_data, has_total, given_model, id), False     # (the per-epoch branch: no queued series)
             n_train, device = job.graph.N, job.device
         else:
             shard, init, perms = prepare_shard(train_data, self.n_user, self.n_item, self.k, self.epochs, has_total, given_model)
@@ -196,7 +202,7 @@ class Scratch(object):
                 total_rmse, total_ndcg, total_hr = total_ev.evaluate(models, job.d)
             else:
                 total_rmse, total_ndcg, total_hr = test_rmse, test_ndcg, test_hr
-            train_loss = float(np.sqrt(job.epoch_sse(0)[t] / n_train))
+            train_loss = float(self._train_loss(job, n_train)[t])
             epoch_time = time.strftime('%H:%M:%S', time.gmtime(time.time() - epoch_start))
             print_epoch(verbose, t, self.epochs, train_loss, (test_rmse, test_ndcg, test_hr), (total_rmse, total_ndcg, total_hr), has_total, epoch_time)
 
@@ -212,7 +218,7 @@ class Scratch(object):
 
         if queued:
             res = res.cpu().numpy()
-            self.log['train_loss'] += [float(x) for x in np.sqrt(job.epoch_sse(0) / n_train)]
+            self.log['train_loss'] += [float(x) for x in self._train_loss(job, n_train)]
             for c, key in enumerate(('test_rmse', 'test_ndcg', 'test_hr')):
                 self.log[key] += [float(x) for x in res[:, 0, c]]
             self.log['time'] += times
@@ -228,9 +234,17 @@ class Scratch(object):
         self.save(model, save_dir, id)
         return model
 
-    def _gcn_job(self, train_data, has_total, given_model):
+    def _train_loss(self, job, n_train):
+        """The train_loss series of a job: sqrt(sse / N) (utils.py:101-103), or under BPR the reference's is_rmse == False
+        reporting, loss_sum / N (utils.py:104-106)."""
+        if self.loss == 'bpr':
+            return job.epoch_loss(0) / n_train
+        return np.sqrt(job.epoch_sse(0) / n_train)
+
+    def _gcn_job(self, train_data, has_total, given_model, id=0):
         """prepare_shard and the job of a LightGCN request: the RNG stream is the MF request's (rng.mf_init, then the epochs' seeds),
-        the orders are the epochs' permutations as file positions."""
+        the orders are the epochs' permutations as file positions.  Under BPR the negatives' key is bpr.stream_key(seed, id): the
+        shard's number, so a retrained shard draws under its own key from its post-deletion graph."""
         if not (_is_empty(given_model) or given_model == ''):
             raise ValueError("given_model is not supported with model_type='lightgcn': the job starts from rng.mf_init")
         loader = as_loader(train_data)
@@ -239,8 +253,12 @@ class Scratch(object):
         n = len(loader.dataset)
         orders = rng.epoch_perms(seeds, n, threads=PERM_THREADS) if loader.shuffle else torch.arange(n, dtype=torch.int32).repeat(self.epochs, 1)
         graph = engine.GcnGraph(*loader.dataset.triples(), self.n_user, self.n_item)
+        extra = {}
+        if self.loss == 'bpr':
+            from ..bpr import stream_key
+            extra = dict(loss='bpr', key=stream_key(self.seed, id))
         return engine.GcnJob(graph, init, orders, self.k, self.gcn_layers, loader.batch_size, self.epochs, self.lr, self.lam, self.momentum,
-                             self.lr_decay)
+                             self.lr_decay, **extra)
 
     def save(self, model, save_dir, id):
         """scratch.py:131-144: model{id}.pth, user_mat{id}.npy, item_mat{id}.npy, log{id}.npy; a LightGCN model's parameters beside

@@ -45,6 +45,9 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.gcn_propagate(off, idx, s_src, s_dst, X, add)
                                                         (new)             one LightGCN propagation over a device CSR / CSC:
                                                                           out[r] = [add[r] +] s_dst[r] sum_j s_src[j] X[j]
+    torch.ops.ultrare.bpr_negatives(off_d, col_d, row_u, pos, n_item, key, epoch)
+                                                        (new)             neg [nnz]: one epoch's BPR negatives, uniform over the
+                                                                          items a CSR entry's user has none of (ultrare_amd/bpr.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -390,3 +393,26 @@ def gcn_propagate(off: torch.Tensor, idx: torch.Tensor, s_src: torch.Tensor, s_d
 @gcn_propagate.register_fake
 def _(off, idx, s_src, s_dst, X, add=None):
     return X.new_empty(off.numel() - 1, X.shape[1])
+
+
+@torch.library.custom_op('ultrare::bpr_negatives', mutates_args=())
+def bpr_negatives(off_d: torch.Tensor, col_d: torch.Tensor, row_u: torch.Tensor, pos: torch.Tensor, n_item: int, key: int, epoch: int) -> torch.Tensor:
+    """engine.bpr_negatives on arrays that are on the device already: off_d int64 [n_user + 1] and col_d int32 (the users' distinct
+    items, bpr.distinct_csr), row_u and pos int32 [nnz] (a CSR entry's user and file position).  key is taken modulo 2^64 (an
+    operator's int is signed: a key of 2^63 or more is passed as key - 2^64).  -> neg int32 [nnz]."""
+    _dev(off_d, col_d, row_u, pos)
+    if [off_d.dtype, col_d.dtype, row_u.dtype, pos.dtype] != [torch.int64, torch.int32, torch.int32, torch.int32]:
+        raise ValueError('bpr_negatives takes (int64 offsets, int32 distinct items, int32 users, int32 file positions)')
+    n_user, nnz = off_d.numel() - 1, row_u.numel()
+    if n_user < 1 or nnz < 1 or pos.numel() != nnz or not 1 <= col_d.numel() <= nnz or n_item < 1 or not 0 <= epoch < 2 ** 31:
+        raise ValueError(f'bpr_negatives: {nnz} entries of {n_user} users over {n_item} items do not fit pos [{pos.numel()}], col_d [{col_d.numel()}]')
+    neg = torch.empty(nnz, dtype=torch.int32, device=row_u.device)
+    nv.check(nv.lib().ure_bpr_sample(nv.ptr(off_d.contiguous()), nv.ptr(col_d.contiguous()), col_d.numel(), nv.ptr(row_u.contiguous()),
+                                     nv.ptr(pos.contiguous()), nnz, n_user, int(n_item), int(key) & 0xFFFFFFFFFFFFFFFF, int(epoch), nv.ptr(neg),
+                                     nv.stream_handle()), 'ure_bpr_sample')
+    return neg
+
+
+@bpr_negatives.register_fake
+def _(off_d, col_d, row_u, pos, n_item, key, epoch):
+    return row_u.new_empty(row_u.numel())
