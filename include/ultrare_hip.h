@@ -781,5 +781,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_gcn.h"
 /* BPR training with device-side negative sampling (csrc/bpr.hip): the per-epoch draw and negative index, the pairwise loss walks. */
 #include "ultrare_bpr.h"
+/* Newton-step (influence) unlearning (csrc/influence.hip): Hessian-vector walks over a shard's CSR / CSC and device-side CG. */
+#include "ultrare_influence.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -200,6 +200,21 @@ _BPR_PROTOTYPES = {
 }
 BPR_EXPORTS = tuple(_BPR_PROTOTYPES)
 
+# include/ultrare_influence.h (Newton-step unlearning, csrc/influence.hip): a table of its own, as the header is;
+# tests/test_cpu_influence.py holds the table, the header and the library to each other, tests/test_gpu_influence.py runs every entry in guard zones.
+_f64 = ctypes.c_double
+_INF_PROTOTYPES = {
+    'ure_inf_coef': (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    'ure_inf_walk': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    'ure_inf_dot_scratch': (_i64, [_i64]),
+    'ure_inf_dot': (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    'ure_inf_cg_start': (ctypes.c_int, [_vp, _f64, _vp]),
+    'ure_inf_cg_xr': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'ure_inf_cg_beta': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    'ure_inf_cg_p': (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp]),
+}
+INF_EXPORTS = tuple(_INF_PROTOTYPES)
+
 _lib = None
 
 
@@ -215,7 +230,7 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -10,6 +10,8 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
   +   InsParam(..., model='mf', gcn_layers=2) optional backbone ('lightgcn': engine.GcnJob, artifacts under LightGCN_*) and its layers
   +   InsParam(..., loss='mse')              optional training loss ('bpr': pairwise, negatives drawn on the device; needs model='lightgcn';
                                              artifacts under LightGCN_bpr_*)
+  +   InsParam(..., unlearn='retrain')       optional unlearning route of runGroup ('influence': Sisa.unlearn_influence, Newton steps on the
+                                             affected shards instead of retraining them; model='mf' with loss='mse' only)
   +   dataset 'toy' is usable end to end     (the reference only has its batch size)
 """
 import os
@@ -34,7 +36,13 @@ DATASETS = {
 
 class InsParam(object):
     def __init__(self, dataset='toy', epochs=50, n_worker=24, layers=[32], n_group=2, del_per=2, del_type='test',
-                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2, loss='mse'):
+                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2, loss='mse', unlearn='retrain'):
+        if unlearn not in ('retrain', 'influence'):
+            raise ValueError(f"unlearn {unlearn!r}: 'retrain' or 'influence'")
+        if unlearn == 'influence':
+            from .influence import check_model
+            check_model(model, loss)
+            self.unlearn = unlearn              # (set only off the default: the saved param of a plain run keeps its bytes)
         # model param
         self.k = k  # dimension of embedding (config.py:19 hard-codes 16)
         self.lam = 0.1  # regularization coefficient
@@ -208,7 +216,10 @@ class Instance(object):
             for rating in self.param.del_rating:
                 if rating[0] not in del_user:
                     del_user.append(rating[0])
-            model.unlearn(model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir)
+            if getattr(self.param, 'unlearn', 'retrain') == 'influence':
+                model.unlearn_influence(model_list, train_dlist, test_data, del_user, verbose, save_dir)
+            else:
+                model.unlearn(model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir)
         self.last = model
         return model.model_list
 

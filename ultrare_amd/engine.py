@@ -2305,3 +2305,205 @@ class GcnJob:
 
     def close(self):
         self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = self._bpr = None
+
+
+# ---------------------------------------------------------------------------
+# Newton-step (influence) unlearning (csrc/influence.hip, include/ultrare_influence.h; the contract is influence.py)
+# ---------------------------------------------------------------------------
+def _inf_on(stream):
+    import contextlib
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def _inf_tables(graph, U, V, who):
+    """The checks of the two float32 tables of a shard: -> d."""
+    from . import lightgcn
+    if not (torch.is_tensor(U) and U.is_cuda and torch.is_tensor(V) and V.is_cuda):
+        raise nv.NativeError(f'{who} runs on the HIP device only (no CPU fallback)')
+    d = lightgcn.check_width(int(U.shape[1]) if U.dim() == 2 else 0)
+    _gcn_table(U, graph.n_user, d, 'U', graph.device)
+    _gcn_table(V, graph.n_item, d, 'V', graph.device)
+    return d
+
+
+def _inf_f64(t, shape, what, dev):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise nv.NativeError('the influence entries run on the HIP device only (no CPU fallback)')
+    if not (t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev):
+        raise ValueError(f'{what} must be a contiguous float64 {list(shape)} tensor on {dev}, not {tuple(t.shape)} {t.dtype} on {t.device}')
+    return t
+
+
+def _inf_active(graph, active):
+    """active None, or (active_u, active_i) masks (numpy or tensors; None in a slot: all rows) -> two uint8 device tensors or None."""
+    if active is None:
+        return None, None
+    if not (isinstance(active, (tuple, list)) and len(active) == 2):
+        raise ValueError('active must be None or (active_u, active_i)')
+    out = []
+    for a, n, what in ((active[0], graph.n_user, 'active_u'), (active[1], graph.n_item, 'active_i')):
+        if a is None:
+            out.append(None)
+            continue
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8)))
+        if a.shape != (n,):
+            raise ValueError(f'{what} must have {n} entries, not {tuple(a.shape)}')
+        out.append(a.to(device=graph.device, dtype=torch.uint8).contiguous())
+    return out[0], out[1]
+
+
+def inf_coef(graph, U, V, P=None, Q=None, out=None, stream=None):
+    """influence.coef_ref on the device: the residuals e [nnz] float64 of the CSR entries, or with a float64 direction (P, Q) the
+    tangents t.  Nothing synchronises."""
+    d = _inf_tables(graph, U, V, 'inf_coef')
+    if (P is None) != (Q is None):
+        raise ValueError('a direction is both P and Q')
+    if P is not None:
+        _inf_f64(P, (graph.n_user, d), 'P', graph.device)
+        _inf_f64(Q, (graph.n_item, d), 'Q', graph.device)
+    with _inf_on(stream):
+        if out is None:
+            out = torch.empty(graph.nnz, dtype=torch.float64, device=graph.device)
+        _inf_f64(out, (graph.nnz,), 'out', graph.device)
+        nv.check(nv.lib().ure_inf_coef(nv.ptr(graph.row_u), nv.ptr(graph.col), nv.ptr(graph.rating), graph.nnz, nv.ptr(U), nv.ptr(V), nv.ptr(P), nv.ptr(Q),
+                                       graph.n_user, graph.n_item, d, nv.ptr(out), nv.stream_handle(stream)), 'ure_inf_coef')
+    return out
+
+
+def _inf_walks(graph, d, a, U, V, b, DU, DV, reg, XU, XV, act, outU, outV, stream):
+    """Both sides of one walk: the users' rows over the CSR against (V, DV), the items' rows over the CSC against (U, DU)."""
+    g, L, st = graph, nv.lib(), nv.stream_handle(stream)
+    nv.check(L.ure_inf_walk(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(a), nv.ptr(V), nv.ptr(b), nv.ptr(DV) if b is not None else None, float(reg),
+                            nv.ptr(XU), nv.ptr(act[0]), g.n_user, g.n_item, g.nnz, d, nv.ptr(outU), st), 'ure_inf_walk')
+    nv.check(L.ure_inf_walk(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(a), nv.ptr(U), nv.ptr(b), nv.ptr(DU) if b is not None else None,
+                            float(reg), nv.ptr(XV), nv.ptr(act[1]), g.n_item, g.n_user, g.nnz, d, nv.ptr(outV), st), 'ure_inf_walk')
+
+
+def _inf_reg(l2, damping, curvature):
+    from . import influence
+    if curvature not in influence.CURVATURES:
+        raise ValueError(f"curvature must be 'full' or 'gn', not {curvature!r}")
+    l2, damping = float(l2), float(damping)
+    if not (np.isfinite(l2) and l2 > 0 and np.isfinite(damping) and damping >= 0):
+        raise ValueError(f'need l2 > 0 and damping >= 0, both finite, not {l2!r}, {damping!r}')
+    return l2 + damping
+
+
+def inf_matvec(graph, U, V, P, Q, l2, damping=0.0, curvature='full', active=None, e=None, stream=None):
+    """influence.matvec_ref bit for bit: (H + 2 damping I)(P, Q) -> (HU, HV) float64 for the float32 tables (U, V) of a shard, its
+    GcnGraph of the remaining triples and a float64 direction.  e: the residuals (inf_coef) when the caller holds them.  Three
+    launches (four without e under 'full'); nothing synchronises."""
+    d = _inf_tables(graph, U, V, 'inf_matvec')
+    reg = _inf_reg(l2, damping, curvature)
+    _inf_f64(P, (graph.n_user, d), 'P', graph.device)
+    _inf_f64(Q, (graph.n_item, d), 'Q', graph.device)
+    act = _inf_active(graph, active)
+    with _inf_on(stream):
+        b = None
+        if curvature == 'full':
+            b = inf_coef(graph, U, V, stream=stream) if e is None else _inf_f64(e, (graph.nnz,), 'e', graph.device)
+        t = inf_coef(graph, U, V, P, Q, stream=stream)
+        HU, HV = torch.empty_like(P), torch.empty_like(Q)
+        _inf_walks(graph, d, t, U, V, b, P, Q, reg, P, Q, act, HU, HV, stream)
+    return HU, HV
+
+
+def inf_grad(graph, U, V, l2, active=None, e=None, stream=None):
+    """influence.grad_ref bit for bit: grad F -> (gU, gV) float64, +0.0 on inactive and emptied rows."""
+    d = _inf_tables(graph, U, V, 'inf_grad')
+    reg = _inf_reg(l2, 0.0, 'gn')
+    act = _inf_active(graph, active)
+    with _inf_on(stream):
+        if e is None:
+            e = inf_coef(graph, U, V, stream=stream)
+        _inf_f64(e, (graph.nnz,), 'e', graph.device)
+        U64, V64 = U.double(), V.double()
+        gU, gV = torch.empty_like(U64), torch.empty_like(V64)
+        _inf_walks(graph, d, e, U, V, None, None, None, reg, U64, V64, act, gU, gV, stream)
+    return gU, gV
+
+
+def inf_dot(x, y, out=None, stream=None):
+    """influence.dot_ref bit for bit on two float64 device tensors of one size -> float64 [1] on the device (out: where to leave
+    it).  Nothing synchronises."""
+    n = x.numel()
+    _inf_f64(x, x.shape, 'x', x.device)
+    _inf_f64(y, x.shape, 'y', x.device)
+    with _inf_on(stream):
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=x.device)
+        L = nv.lib()
+        nbytes = L.ure_inf_dot_scratch(n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        nv.check(L.ure_inf_dot(nv.ptr(x), nv.ptr(y), n, nv.ptr(scratch), nbytes, nv.ptr(out), nv.stream_handle(stream)), 'ure_inf_dot')
+    return out
+
+
+def inf_objective(graph, U, V, l2, e=None, stream=None):
+    """The two sums of influence.objective_ref on the device -> float64 [2] = (dot(e, e), dot(theta, theta)); F = [0] + l2 * [1]."""
+    _inf_tables(graph, U, V, 'inf_objective')
+    with _inf_on(stream):
+        if e is None:
+            e = inf_coef(graph, U, V, stream=stream)
+        th = torch.cat([U.reshape(-1), V.reshape(-1)]).double()
+        out = torch.empty(2, dtype=torch.float64, device=graph.device)
+        inf_dot(e, e, out[0:1], stream)
+        inf_dot(th, th, out[1:2], stream)
+    return out
+
+
+def inf_solve(graph, U, V, bU, bV, l2, damping=0.0, curvature='full', active=None, e=None, iters=512, tol=1e-8, stream=None):
+    """influence.solve_ref on the device: conjugate gradients on (H + 2 damping I) x = (bU, bV) from x = 0 -> (xU, xV, log) with
+    log = {'rr': the float64 residual norms per iteration, 'flag', 'iters_run', 'status'} (0 out of iterations, 1 converged, 2
+    non-positive curvature).  The scalars stay on the device (ure_inf_cg_*); the host reads the flags of the log once per
+    influence.LOG_BLOCK iterations to stop launching, and the rr history once at the end."""
+    from . import influence
+    influence.check_args(curvature, damping, 1, iters, tol, l2)              # (refuses the undamped full Hessian)
+    d = _inf_tables(graph, U, V, 'inf_solve')
+    reg = _inf_reg(l2, damping, curvature)
+    g, dev, L, st = graph, graph.device, nv.lib(), nv.stream_handle(stream)
+    _inf_f64(bU, (g.n_user, d), 'bU', dev)
+    _inf_f64(bV, (g.n_item, d), 'bV', dev)
+    act = _inf_active(graph, active)
+    nu, n = g.n_user * d, (g.n_user + g.n_item) * d
+    sides = lambda v: (v[:nu].view(g.n_user, d), v[nu:].view(g.n_item, d))
+    with _inf_on(stream):
+        b = None
+        if curvature == 'full':
+            b = inf_coef(graph, U, V, stream=stream) if e is None else _inf_f64(e, (g.nnz,), 'e', dev)
+        x = torch.zeros(n, dtype=torch.float64, device=dev)
+        r = torch.cat([bU.reshape(-1), bV.reshape(-1)])
+        p, Ap = r.clone(), torch.empty_like(r)
+        t = torch.empty(g.nnz, dtype=torch.float64, device=dev)
+        state = torch.zeros(8, dtype=torch.float64, device=dev)
+        log_rr, log_flag = torch.zeros(iters, dtype=torch.float64, device=dev), torch.zeros(iters, dtype=torch.int32, device=dev)
+        nbytes = L.ure_inf_dot_scratch(n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        (pU, pV), (ApU, ApV) = sides(p), sides(Ap)
+
+        def dot(a, c, slot):
+            nv.check(L.ure_inf_dot(nv.ptr(a), nv.ptr(c), n, nv.ptr(scratch), nbytes, state.data_ptr() + 8 * slot, st), 'ure_inf_dot')
+
+        dot(r, r, 0)
+        nv.check(L.ure_inf_cg_start(nv.ptr(state), float(tol), st), 'ure_inf_cg_start')
+        ran, status = iters, influence.RUNNING
+        for it in range(iters):
+            inf_coef(graph, U, V, pU, pV, out=t, stream=stream)
+            _inf_walks(graph, d, t, U, V, b, pU, pV, reg, pU, pV, act, ApU, ApV, stream)
+            dot(p, Ap, 1)
+            nv.check(L.ure_inf_cg_xr(nv.ptr(state), nv.ptr(x), nv.ptr(r), nv.ptr(p), nv.ptr(Ap), n, st), 'ure_inf_cg_xr')
+            dot(r, r, 2)
+            nv.check(L.ure_inf_cg_beta(nv.ptr(state), nv.ptr(log_rr), nv.ptr(log_flag), it, iters, st), 'ure_inf_cg_beta')
+            nv.check(L.ure_inf_cg_p(nv.ptr(state), nv.ptr(p), nv.ptr(r), n, st), 'ure_inf_cg_p')
+            if (it + 1) % influence.LOG_BLOCK == 0 or it + 1 == iters:
+                a0 = it + 1 - ((it % influence.LOG_BLOCK) + 1)
+                flags = log_flag[a0:it + 1].cpu().numpy()                      # the one read of the loop: a block of flags
+                hit = np.flatnonzero(flags)
+                if len(hit):
+                    ran, status = a0 + int(hit[0]) + 1, int(flags[hit[0]])
+                    break
+        rr = log_rr[:ran].cpu().numpy()
+        flag = log_flag[:ran].cpu().numpy()
+    xU, xV = sides(x)
+    return xU, xV, {'rr': rr, 'flag': flag, 'iters_run': ran, 'status': status}

@@ -27,7 +27,10 @@ Same flags, defaults and assertions; additions are optional:
   --loss         'mse' (default: the reference's MSELoss(sum) on the rating) or 'bpr': the pairwise BPR loss, one negative per triple and
                  epoch drawn on the device (ultrare_amd/bpr.py, csrc/bpr.hip).  Needs --model lightgcn (--gcn-layers 0 is
                  BPR-MF); artifacts under LightGCN_bpr_*; train_loss is the mean batch loss; judge the result with rank_eval
-  --data-dir / --save-dir   roots of data/ and result/ (default: ./data, ./result)
+  --unlearn      'retrain' (default: the affected shards are retrained, Sisa.unlearn) or 'influence': damped Newton steps on the remaining
+                 data of every affected shard, no retraining (Sisa.unlearn_influence, ultrare_amd/influence.py, csrc/influence.hip,
+                 DESIGN 4.25): approximate.  Needs --model mf --loss mse
+  --data-dir / --save-dir  roots of data/ and result/ (default: ./data, ./result)
 """
 import argparse
 import os
@@ -50,6 +53,7 @@ parser.add_argument('--lr', type=float, default=None, help='learning rate (defau
 parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn'], help="'mf' (reference) or 'lightgcn'")
 parser.add_argument('--gcn-layers', type=int, default=2, help="propagations per side of the 'lightgcn' backbone (0 .. 8)")
 parser.add_argument('--loss', type=str, default='mse', choices=['mse', 'bpr'], help="'mse' (reference) or 'bpr' (needs --model lightgcn)")
+parser.add_argument('--unlearn', type=str, default='retrain', choices=['retrain', 'influence'], help="'retrain' (reference) or 'influence' (Newton steps, no retraining; --model mf --loss mse)")
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -88,7 +92,7 @@ def main(argv=None):
     torch.manual_seed(42)   # the reference never seeds the CPU generator; a fixed run needs it
     param = InsParam(args.dataset, args.epoch, args.worker, args.layer, args.group, args.delper, args.deltype,
                      k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr,
-                     model=args.model, gcn_layers=args.gcn_layers, loss=args.loss)
+                     model=args.model, gcn_layers=args.gcn_layers, loss=args.loss, unlearn=args.unlearn)
     ins = Instance(param, save_dir=args.save_dir)
 
     if args.group == 0:

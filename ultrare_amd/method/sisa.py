@@ -698,3 +698,53 @@ class Sisa(Scratch):
         self.test(test_data, verbose, save_dir)
         self.retrained = sorted(retrain_gid)
         return self.model_list
+
+    def unlearn_influence(self, model_list, train_dlist, test_data, del_user, verbose, save_dir, **kw):
+        '''
+        Approximate unlearning without retraining: every shard that holds a deleted user -- found exactly as unlearn
+        finds them -- takes utils.newton_unlearn's damped Newton steps on its post-deletion loader train_dlist[i], over its OWN rows
+        of the merged user table and its item table; the rows go back into the merged table, where the deleted users' rows are zero.
+        kw: newton_unlearn's keywords (l2 None: trainer_l2 of the shard's remaining ratings with the trainer's batch and lam).
+        self.influenced lists the updated shards and self.influence_logs their per-step logs; self.retrained is empty; a fitted
+        combiner is dropped and folded is kept as unlearn keeps it.  More than one rank and model_type='lightgcn' (or loss='bpr') are
+        refused before any device work.  unlearn itself is untouched and may follow.
+        '''
+        from ..influence import check_model
+        check_model(self.model_type, getattr(self, 'loss', 'mse'))
+        dist = _dist()
+        if dist is not None and dist.get_world_size() > 1:
+            raise ValueError(f'unlearn_influence runs on one rank, not {dist.get_world_size()}')
+        assert len(train_dlist) == self.n_group
+        kw = dict(kw)
+        if kw.get('l2') is None:
+            kw.setdefault('batch', self.batch)
+            kw.setdefault('lam', self.lam)
+        first_group = np.full(max(self.n_user, 1 + max((int(max(g)) for g in self.group_index if len(g)), default=0)), -1, dtype=np.int64)
+        for i in reversed(range(self.n_group)):
+            first_group[np.asarray(self.group_index[i], dtype=np.int64)] = i
+        users = np.asarray(list(del_user), dtype=np.int64).reshape(-1)
+        users = users[(users >= 0) & (users < len(first_group))]
+        gids = sorted(int(g) for g in np.unique(first_group[users]) if g >= 0)
+        for i in gids:                  # every setting of every affected shard, before any device work or change
+            n = len(utils._rating_triple(train_dlist[i])[0])
+            if n == 0:
+                raise ValueError(f'shard {i} has no rating left: nothing to take a Newton step on (unlearn retrains it)')
+            utils.newton_unlearn_check(self.model_type, 'mse', n_rows=n, **{k: v for k, v in kw.items() if k != 'scope'})
+        self.combiner = None
+        self.model_list = model_list
+        self.folded ={u: g for u, g in getattr(self, 'folded', {}).items() if g not in set(gids)}
+
+        merged = model_list[0].user_mat.weight.detach().clone().contiguous()
+        self.influence_logs = {}
+        for i in gids:
+            # the shard's view: a copy of the merged user table (the rows of other shards' users have no entry in this loader; only
+            # group_index[i]'s rows are merged back) and its own item table, updated in place
+            shard = MF.from_tables(merged.clone(), self.model_list[i].item_mat.weight.detach().clone().contiguous())
+            self.influence_logs[i] = utils.newton_unlearn(shard, train_dlist[i], **kw)
+            self.model_list[i] = shard
+        self._merge(merged, gids)
+
+        self.test(test_data, verbose, save_dir)
+        self.influenced = gids
+        self.retrained = []
+        return self.model_list

@@ -928,3 +928,85 @@ def attribute_unlearn(model, id1, id2, var='d2d', eta=1.0, alpha=0.0, lr=0.1, st
         for b in host[2]:
             check_bandwidth(b)
     return {'dis': host[0].tolist(), 'reg': host[1].tolist(), 'bandwidth': host[2].tolist()}
+
+
+def newton_unlearn_check(model_type='mf', loss='mse', l2=None, batch=None, lam=None, damping=None, curvature='full', steps=1, iters=512, tol=1e-8,
+                         n_rows=0):
+    """The settings of newton_unlearn, checked on the host (ValueError) -> (l2, damping).  l2 None: trainer_l2(n_rows, batch, lam)."""
+    from ..influence import check_args, check_model
+    check_model(model_type, loss)
+    if l2 is None:
+        if batch is None or lam is None:
+            raise ValueError('newton_unlearn needs l2, or batch and lam for l2 = trainer_l2(len(train_data), batch, lam)')
+        l2 = trainer_l2(n_rows, batch, lam)
+    return check_args(curvature, damping, steps, iters, tol, l2)
+
+
+def newton_unlearn(model, train_data, l2=None, batch=None, lam=None, damping=None, curvature='full', steps=1, iters=512, tol=1e-8, scope='all'):
+    """Approximate unlearning of TRAINED users without retraining (the contract is influence.newton_unlearn_ref):
+    `steps` damped Newton steps on F = sum_D e^2 + l2 (|U|^2 + |V|^2) over the REMAINING data D = train_data (a post-deletion
+    loader, or a (uid, iid, rating / 5) triple), in place on the two tables of an MF model trained with the MSE loss.  A row
+    without an entry in D -- a deleted user's -- becomes +0.0; rows outside scope = (users, items) (None in a slot: all rows of that
+    side; 'all': every row) keep their bytes.  Each step solves (H + 2 damping I) x = -grad F by conjugate gradients on the device
+    (engine.inf_solve: CSR / CSC Hessian-vector walks in float64, at most `iters` iterations to a relative residual `tol`) and
+    rounds theta + x to float32 once.  curvature='full' is the exact Hessian and needs damping > 0 (it is singular along the common
+    rotations of both tables); 'gn' is the Gauss-Newton matrix, positive definite and slower to close the gap.
+    l2 None: trainer_l2(len(D), batch, lam), the ridge strength of the trainer's own fixed point.  damping None: 0.1 * l2 for 'full'
+    and 0 for 'gn' -- the setting of the float64 prototype, a starting point that NOBODY HAS TUNED.
+    A step whose solve met non-positive curvature (status 2), or that did not reduce F (the float64 value on the device, one read per
+    step), is not applied: the tables keep the last good bytes, the step's log says why and no further step is tried; nothing is
+    raised.  Returns the per-step logs: inf_solve's log plus F_before, F_after, applied, reason.  ValueError for bad settings before
+    any device work."""
+    from .. import influence
+    uid, iid, r = _rating_triple(train_data)
+    l2, damping = newton_unlearn_check('mf', 'mse', l2, batch, lam, damping, curvature, steps, iters, tol, len(uid))
+    W_u, W_v = model.user_mat.weight, model.item_mat.weight
+    n_user, n_item = int(W_u.shape[0]), int(W_v.shape[0])
+    free_u, free_i = influence.check_scope(scope, n_user, n_item)
+    if len(uid) == 0:
+        raise ValueError('newton_unlearn needs at least one remaining rating')
+    U, V, d = padded_tables(model)
+    k, dev = int(W_u.shape[1]), U.device
+    if U.data_ptr() == W_u.data_ptr():
+        U = U.clone()
+    if V.data_ptr() == W_v.data_ptr():
+        V = V.clone()
+    graph = engine.GcnGraph(uid, iid, r, n_user, n_item, device=dev)
+    g = graph.host
+    has_u, has_i = np.diff(g.off_u) > 0, np.diff(g.off_i) > 0
+    active = (has_u & free_u, has_i & free_i)
+    act = engine._inf_active(graph, active)
+    au, ai = act[0].bool(), act[1].bool()
+    U[torch.from_numpy(~has_u).to(dev)] = 0.0
+    V[torch.from_numpy(~has_i).to(dev)] = 0.0
+
+    def objective(U, V, e):
+        parts = engine.inf_objective(graph, U, V, l2, e).cpu().numpy()          # the one read of a step
+        return float(parts[0] + l2 * parts[1])
+
+    e = engine.inf_coef(graph, U, V)
+    F = objective(U, V, e)
+    logs = []
+    for _ in range(steps):
+        gU, gV = engine.inf_grad(graph, U, V, l2, act, e)
+        xU, xV, log = engine.inf_solve(graph, U, V, -gU, -gV, l2, damping, curvature, act, e, iters, tol)
+        log['F_before'] = F
+        if log['status'] == influence.NON_POSITIVE:
+            log.update(applied=False, reason='non-positive curvature met by the solve', F_after=F)
+            logs.append(log)
+            break
+        U1, V1 = U.clone(), V.clone()
+        U1[au], V1[ai] = (U.double() + xU).float()[au], (V.double() + xV).float()[ai]
+        e1 = engine.inf_coef(graph, U1, V1)
+        F1 = objective(U1, V1, e1)
+        if not F1 < F:
+            log.update(applied=False, reason='the step did not reduce the objective', F_after=F1)
+            logs.append(log)
+            break
+        U, V, e, F = U1, V1, e1, F1
+        log.update(applied=True, reason='', F_after=F1)
+        logs.append(log)
+    with torch.no_grad():
+        W_u[:, :k] = U[:, :k]
+        W_v[:, :k] = V[:, :k]
+    return logs

@@ -48,6 +48,10 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.bpr_negatives(off_d, col_d, row_u, pos, n_item, key, epoch)
                                                         (new)             neg [nnz]: one epoch's BPR negatives, uniform over the
                                                                           items a CSR entry's user has none of (ultrare_amd/bpr.py)
+    torch.ops.ultrare.inf_matvec(off_u, col, row_u, off_i, row, to_csr, rating, U, V, P, Q, l2, damping, full)
+                                                        (new)             (HU, HV) float64: the product of the MSE objective's
+                                                                          Hessian (full) or Gauss-Newton matrix, plus 2 damping I,
+                                                                          with a float64 direction (ultrare_amd/influence.py)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -416,3 +420,29 @@ def bpr_negatives(off_d: torch.Tensor, col_d: torch.Tensor, row_u: torch.Tensor,
 @bpr_negatives.register_fake
 def _(off_d, col_d, row_u, pos, n_item, key, epoch):
     return row_u.new_empty(row_u.numel())
+
+
+@torch.library.custom_op('ultrare::inf_matvec', mutates_args=())
+def inf_matvec(off_u: torch.Tensor, col: torch.Tensor, row_u: torch.Tensor, off_i: torch.Tensor, row: torch.Tensor, to_csr: torch.Tensor,
+               rating: torch.Tensor, U: torch.Tensor, V: torch.Tensor, P: torch.Tensor, Q: torch.Tensor, l2: float, damping: float = 0.0,
+               full: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """engine.inf_matvec on the halves of a graph that are on the device already (the arrays of lightgcn.Graph: off_u, off_i int64;
+    col, row_u, row, to_csr int32 [nnz]; rating float32 [nnz] in CSR order; the caller vouches for the index ranges), float32 tables
+    U, V and a float64 direction P, Q.  full: the Hessian, else the Gauss-Newton matrix."""
+    import types
+    _dev(off_u, col, row_u, off_i, row, to_csr, rating, U, V, P, Q)
+    if [off_u.dtype, col.dtype, row_u.dtype, off_i.dtype, row.dtype, to_csr.dtype, rating.dtype] != [torch.int64, torch.int32, torch.int32, torch.int64,
+                                                                                                      torch.int32, torch.int32, torch.float32]:
+        raise ValueError('inf_matvec takes (int64 off_u, int32 col, int32 row_u, int64 off_i, int32 row, int32 to_csr, float32 rating)')
+    nnz, n_user, n_item = col.numel(), off_u.numel() - 1, off_i.numel() - 1
+    if nnz < 1 or n_user < 1 or n_item < 1 or [row_u.numel(), row.numel(), to_csr.numel(), rating.numel()] != [nnz] * 4:
+        raise ValueError(f'inf_matvec: {nnz} entries of {n_user} users and {n_item} items do not fit the index arrays')
+    c = lambda t: t.contiguous()
+    g = types.SimpleNamespace(off_u=c(off_u), col=c(col), row_u=c(row_u), off_i=c(off_i), row=c(row), to_csr=c(to_csr), rating=c(rating), nnz=nnz, N=nnz,
+                              n_user=n_user, n_item=n_item, device=U.device)
+    return engine.inf_matvec(g, U, V, P, Q, l2, damping, 'full' if full else 'gn')
+
+
+@inf_matvec.register_fake
+def _(off_u, col, row_u, off_i, row, to_csr, rating, U, V, P, Q, l2, damping=0.0, full=True):
+    return torch.empty_like(P), torch.empty_like(Q)
