@@ -783,5 +783,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_bpr.h"
 /* Newton-step (influence) unlearning (csrc/influence.hip): Hessian-vector walks over a shard's CSR / CSC and device-side CG. */
 #include "ultrare_influence.h"
+/* The NeuMF backbone (csrc/nmf.hip): per-sample MLP forward / backward, weight-gradient sums, masked row sums and scoring. */
+#include "ultrare_nmf.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -215,6 +215,19 @@ _INF_PROTOTYPES = {
 }
 INF_EXPORTS = tuple(_INF_PROTOTYPES)
 
+# include/ultrare_nmf.h (the NeuMF backbone, csrc/nmf.hip): a table of its own, as the header is; tests/test_cpu_nmf.py holds the
+# table, the header and the library to each other, tests/test_gpu_nmf.py runs every entry in guard zones.
+_NMF_SHAPE = [_i32, _vp, _i32]                       # k, layers (a HOST int32 array), n_layers
+_NMF_PROTOTYPES = {
+    'ure_nmf_dense_size': (_i64, _NMF_SHAPE),
+    'ure_nmf_forward_backward': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _i64, _vp] + _NMF_SHAPE + [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'ure_nmf_weight_grad_scratch': (_i64, [_i32] + _NMF_SHAPE),
+    'ure_nmf_weight_grad': (ctypes.c_int, [_vp, _vp, _vp, _i32] + _NMF_SHAPE + [_vp, _vp, _i64, _i32, _vp]),
+    'ure_nmf_row_sum': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'ure_nmf_score': (ctypes.c_int, [_vp, _vp, _vp] + _NMF_SHAPE + [_i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+}
+NMF_EXPORTS = tuple(_NMF_PROTOTYPES)
+
 _lib = None
 
 
@@ -230,7 +243,7 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -8,6 +8,8 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
   +   InsParam(..., k=16, parallel=False)    optional embedding width and shard-parallel mode
   +   InsParam(..., optimizer='sgd', lr=None) optional optimizer ('adam': engine.TrainJob) and learning rate (None: 0.001)
   +   InsParam(..., model='mf', gcn_layers=2) optional backbone ('lightgcn': engine.GcnJob, artifacts under LightGCN_*) and its layers
+  +   InsParam(..., model='nmf', layers=[64, 32]) optional neural backbone (NeuMF: engine.NmfJob, artifacts under NMF_*); `layers` is its MLP
+                                             stack [L0, .., Lm] (ultrare_amd/nmf.py); optimizer='sgd' and loss='mse' only
   +   InsParam(..., loss='mse')              optional training loss ('bpr': pairwise, negatives drawn on the device; needs model='lightgcn';
                                              artifacts under LightGCN_bpr_*)
   +   InsParam(..., unlearn='retrain')       optional unlearning route of runGroup ('influence': Sisa.unlearn_influence, Newton steps on the
@@ -46,7 +48,7 @@ class InsParam(object):
         # model param
         self.k = k  # dimension of embedding (config.py:19 hard-codes 16)
         self.lam = 0.1  # regularization coefficient
-        self.layers = layers  # unused by MF (structure of FC layers in DMF)
+        self.layers = layers  # the MLP stack [L0, .., Lm] of model='nmf' (the reference's "structure of FC layers"); unused by 'mf' and 'lightgcn'
 
         # training param
         self.seed = 42
@@ -65,8 +67,15 @@ class InsParam(object):
         self.optimizer = optimizer  # 'adam': momentum is not used; betas / eps are torch.optim.Adam's defaults
         self.betas = (0.9, 0.999)
         self.eps = 1e-8
-        if model not in ('mf', 'lightgcn'):
-            raise ValueError(f"model {model!r}: 'mf' or 'lightgcn'")
+        if model not in ('mf', 'lightgcn', 'nmf'):
+            raise ValueError(f"model {model!r}: 'mf', 'lightgcn' or 'nmf'")
+        if model == 'nmf':
+            from .nmf import check_layers as check_stack
+            if optimizer != 'sgd':
+                raise ValueError(f"model='nmf' trains with optimizer='sgd' only, not {optimizer!r}")
+            if loss != 'mse':
+                raise ValueError(f"model='nmf' trains with loss='mse' only, not {loss!r}")
+            self.k, self.layers = check_stack(k, layers)
         if model == 'lightgcn' and optimizer != 'sgd':
             raise ValueError(f"model='lightgcn' trains with optimizer='sgd' only, not {optimizer!r}")
         if loss not in ('mse', 'bpr'):
@@ -75,8 +84,8 @@ class InsParam(object):
             raise ValueError("loss='bpr' trains with model='lightgcn' only: --model lightgcn --gcn-layers 0 is BPR-MF")
         self.loss = loss                        # 'mse' (the reference's), or 'bpr' (ultrare_amd/bpr.py)
         from .lightgcn import check_layers
-        self.model = model                      # the backbone: 'mf', or 'lightgcn' (ultrare_amd/lightgcn.py)
-        self.gcn_layers = check_layers(gcn_layers)   # propagations per side of the 'lightgcn' backbone (`layers` above is the DMF flag)
+        self.model = model                      # the backbone: 'mf', 'lightgcn' (ultrare_amd/lightgcn.py) or 'nmf' (ultrare_amd/nmf.py)
+        self.gcn_layers = check_layers(gcn_layers)   # propagations per side of the 'lightgcn' backbone (`layers` above is the 'nmf' backbone's stack)
 
         # dataset-varied param
         self.del_rating = []  # 2d array/list [[uid, iid], ...]
@@ -229,7 +238,7 @@ class Instance(object):
     def _model(self):
         """(model_type, artifact prefix) of the backbone the parameters name."""
         model = getattr(self.param, 'model', 'mf')
-        prefix = {'mf': 'MF_', 'lightgcn': 'LightGCN_'}[model]
+        prefix = {'mf': 'MF_', 'lightgcn': 'LightGCN_', 'nmf': 'NMF_'}[model]
         return model, prefix + ('bpr_' if getattr(self.param, 'loss', 'mse') == 'bpr' else '')
 
     def runFull(self, is_save=True, verbose=1):

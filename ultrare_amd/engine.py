@@ -1010,6 +1010,27 @@ class EvalSet:
             nv.check(L.ure_score(Up, Vp, len(chunk), S, int(c0 == 0), int(c0 + len(chunk) >= S),
                                  nv.ptr(self.uid), nv.ptr(self.iid), nv.ptr(self.rating), self.n, d,
                                  nv.ptr(self.pred), nv.ptr(self.sse), st), 'ure_score')
+        return self._rank_and_reduce(st, top_k, out)
+
+    def evaluate_nmf(self, models, stream=None, top_k=10, out=None):
+        """baseTest for an ensemble of NeuMF models: `models` = list of (U, V, dense, k, layers) (nmf.py's tables and dense vector
+        on the device).  One ure_nmf_score call per model, in list order, under ure_score's protocol; the ranking and the reduction
+        are evaluate's calls on the same buffers.  Returns (rmse, ndcg, hr), or `out`."""
+        assert top_k == 10, 'the kernel implements the reference default top_k=10'
+        if not models:
+            raise ValueError('evaluate_nmf needs at least one model')
+        if self.n == 0:
+            if out is not None:
+                return out.fill_(float('nan'))
+            return float('nan'), float('nan'), float('nan')
+        S = len(models)
+        for s, (U, V, dense, k, layers) in enumerate(models):
+            nmf_score(U, V, dense, k, layers, self.uid, self.iid, self.rating, self.pred, self.sse, S, s == 0, s == S - 1, stream)
+        return self._rank_and_reduce(nv.stream_handle(stream), top_k, out)
+
+    def _rank_and_reduce(self, st, top_k, out):
+        """The per-user ranking and the reduction of what a scoring pass left in pred and sse."""
+        L = nv.lib()
         nv.check(L.ure_eval_users(nv.ptr(self.off), self.n_users, nv.ptr(self.pred), nv.ptr(self.rating),
                                   nv.ptr(self.log2), nv.ptr(self.hits), nv.ptr(self.ndcg), nv.ptr(self.top_rating), self.n_wide, self.n_half, st),
                  'ure_eval_users')
@@ -2305,6 +2326,177 @@ class GcnJob:
 
     def close(self):
         self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = self._bpr = None
+
+
+# ---------------------------------------------------------------------------
+# The NeuMF backbone (csrc/nmf.hip, include/ultrare_nmf.h; the contract is nmf.py)
+# ---------------------------------------------------------------------------
+def _nmf_layers(layers):
+    """The stack as the host int32 array the entries take."""
+    return np.ascontiguousarray(layers, dtype=np.int32)
+
+
+def _nmf_tensor(t, shape, dtype, what, dev=None):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise nv.NativeError('nmf_score runs on the HIP device only (no CPU fallback)')
+    if not (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f'{what} must be a contiguous {dtype} {list(shape)} tensor, not {t.dtype} {list(t.shape)}')
+    if dev is not None and t.device != dev:
+        raise ValueError(f'{what} is on {t.device}, the tables on {dev}')
+    return t
+
+
+def nmf_score(U, V, dense, k, layers, uid, iid, rating=None, pred=None, sse=None, n_models_total=1, first=True, last=True, stream=None):
+    """nmf.score_ref's step for ONE model (U [n_user, k + e], V [n_item, k + e], dense) at the pairs (uid, iid) int32 [n] on the
+    device, under ure_score's protocol: pred (default: a new tensor; must be given unless `first`) receives the running sum, and
+    on `last` the mean over n_models_total; sse (optional, float64 [SCORE_PARTIALS], with rating) the squared-error partials.
+    -> pred.  Nothing synchronises."""
+    from . import nmf
+    S = nmf.Shape(k, layers)                                # (the ValueError of a bad stack comes before any device work)
+    for t in (U, V, dense, uid, iid):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise nv.NativeError('nmf_score runs on the HIP device only (no CPU fallback)')
+    dev, n = U.device, int(uid.numel())
+    _nmf_tensor(U, (U.shape[0], S.wd), torch.float32, 'U')
+    _nmf_tensor(V, (V.shape[0], S.wd), torch.float32, 'V', dev)
+    _nmf_tensor(dense, (S.n_dense,), torch.float32, 'dense', dev)
+    _nmf_tensor(uid, (n,), torch.int32, 'uid', dev)
+    _nmf_tensor(iid, (n,), torch.int32, 'iid', dev)
+    if n < 1:
+        raise ValueError('nmf_score needs at least one pair')
+    if pred is None:
+        if not first:
+            raise ValueError('pred holds the running sum of the models before: it must be given unless first')
+        pred = torch.empty(n, dtype=torch.float32, device=dev)
+        _csr_held_for(stream, pred)
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() < n or pred.device != dev:
+        raise ValueError(f'pred must be a contiguous float32 tensor of at least {n} elements on {dev}')
+    if sse is not None:
+        _nmf_tensor(sse, (SCORE_PARTIALS,), torch.float64, 'sse', dev)
+        if rating is None:
+            raise ValueError('sse needs the ratings')
+    if rating is not None and (rating.dtype != torch.float32 or not rating.is_contiguous() or rating.numel() < n or rating.device != dev):
+        raise ValueError(f'rating must be a contiguous float32 tensor of at least {n} elements on {dev}')
+    lay = _nmf_layers(S.layers)
+    nv.check(nv.lib().ure_nmf_score(nv.ptr(U), nv.ptr(V), nv.ptr(dense), S.k, nv.ptr(lay), len(lay), int(U.shape[0]), int(V.shape[0]),
+                                    int(n_models_total), int(bool(first)), int(bool(last)), nv.ptr(uid), nv.ptr(iid), nv.ptr(rating), n, nv.ptr(pred),
+                                    nv.ptr(sse), nv.stream_handle(stream)), 'ure_nmf_score')
+    return pred
+
+
+class NmfJob:
+    """One shard trained with the NeuMF backbone (nmf.train_ref in float32, bit for bit): per step the forward / backward pass over
+    the shard's entries (the batch's write their slot), the weight-gradient sums over the slots, the two masked row sums of the
+    embedding gradients, the loss fold, and ONE SGD update of every parameter -- both tables and the dense vector are one
+    contiguous run of floats, as are their momenta and gradients.  What Scratch._train uses of a TrainJob is here under the same
+    names.
+
+    graph  : GcnGraph
+    init   : (U0 [n_user, k + e], V0 [n_item, k + e], dense0 [nmf.Shape(k, layers).n_dense]) float32 numpy arrays or tensors
+    orders : int32 [epochs, N] -- per epoch the file positions in training order (batch t = orders[e][t B : (t + 1) B])"""
+
+    def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50):
+        from . import nmf
+        self.shape = S = nmf.Shape(k, layers)
+        self.graph, self.k, self.layers = graph, S.k, S.layers
+        self.batch, self.epochs, self.device = int(batch), int(epochs), graph.device
+        if self.batch < 1 or self.epochs < 0:
+            raise ValueError(f'batch {batch!r} must be positive and epochs {epochs!r} not negative')
+        if len(init) != 3:
+            raise ValueError('init is (U0, V0, dense0)')
+        U0, V0, dense0 = (np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32) for t in init)
+        nmf.check_model(U0, V0, dense0, S.k, S.layers, graph.n_user, graph.n_item)
+        orders = np.asarray(orders.cpu() if torch.is_tensor(orders) else orders)
+        if orders.shape != (self.epochs, graph.N) or orders.dtype.kind not in 'iu':
+            raise ValueError(f'orders must be integers of shape ({self.epochs}, {graph.N}), not {orders.dtype} {orders.shape}')
+        file_rank = np.empty((self.epochs, graph.N), dtype=np.int32)
+        place = np.arange(graph.N, dtype=np.int32)
+        for e in range(self.epochs):
+            o = orders[e].astype(np.int64)
+            if o.min() < 0 or o.max() >= graph.N or (np.bincount(o, minlength=graph.N) != 1).any():
+                raise ValueError(f'orders[{e}] is not a permutation of 0 .. {graph.N - 1}')
+            file_rank[e, o] = place                         # the inverse permutation: a triple's place in the epoch's order
+        # StepLR as engine.TrainJob makes it: float32 values
+        self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
+        self._lam, self._mu = float(np.float32(lam)), float(np.float32(momentum))
+        self.steps = (graph.N + self.batch - 1) // self.batch
+        self._lay = _nmf_layers(S.layers)
+        dev, B = self.device, min(self.batch, graph.N)
+        self._nu, self._ni = graph.n_user * S.wd, graph.n_item * S.wd
+        self.n_params = self._nu + self._ni + S.n_dense
+        # everything below is written before it is read (the momenta by the first step): torch.empty
+        self._pool = torch.empty(3, self.n_params, dtype=torch.float32, device=dev)      # parameters, momenta, gradients
+        self._pool[0].copy_(torch.from_numpy(np.concatenate([U0.reshape(-1), V0.reshape(-1), dense0])))
+        self._file_rank = torch.from_numpy(file_rank).to(dev)
+        self._rank = torch.empty(graph.nnz, dtype=torch.int32, device=dev)
+        self._err = torch.empty(B, dtype=torch.float32, device=dev)
+        self._act = torch.empty(B, S.A, dtype=torch.float32, device=dev)
+        self._dlt = torch.empty(B, S.Dw, dtype=torch.float32, device=dev)
+        self._emb = torch.empty(B, 2 * S.wd, dtype=torch.float32, device=dev)
+        self._scratch_bytes = int(nv.lib().ure_nmf_weight_grad_scratch(B, S.k, nv.ptr(self._lay), len(self._lay)))
+        self._scratch = torch.empty(self._scratch_bytes, dtype=torch.uint8, device=dev)
+        self._row_loss = torch.empty(graph.n_user, dtype=torch.float64, device=dev)
+        self._sse = torch.zeros(max(self.epochs, 1), dtype=torch.float64, device=dev)
+        self.done = 0            # optimizer steps run
+        self.ticks = self.epochs * self.steps
+
+    def _part(self, which):
+        """(U, V, dense) views of the parameters (0), the momenta (1) or the gradients (2)."""
+        g, S, t = self.graph, self.shape, self._pool[which]
+        return t[:self._nu].view(g.n_user, S.wd), t[self._nu:self._nu + self._ni].view(g.n_item, S.wd), t[self._nu + self._ni:]
+
+    def _step(self, e, s, stream=None):
+        g, S, L, st = self.graph, self.shape, nv.lib(), nv.stream_handle(stream)
+        if s == 0:
+            nv.check(L.ure_gcn_gather_tags(nv.ptr(self._file_rank[e]), nv.ptr(g.pos), g.nnz, nv.ptr(self._rank), st), 'ure_gcn_gather_tags')
+        lo = s * self.batch
+        n_slots = min(self.batch, g.N - lo)
+        (U, V, dense), (gU, gV, gd) = self._part(0), self._part(2)
+        lay, m = nv.ptr(self._lay), len(self._lay)
+        nv.check(L.ure_nmf_forward_backward(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(self._rank), g.nnz, lo, n_slots, U.data_ptr(),
+                                            V.data_ptr(), g.n_user, g.n_item, dense.data_ptr(), S.k, lay, m, nv.ptr(self._err), None, nv.ptr(self._act),
+                                            nv.ptr(self._dlt), nv.ptr(self._emb), st), 'ure_nmf_forward_backward')
+        nv.check(L.ure_nmf_weight_grad(nv.ptr(self._err), nv.ptr(self._act), nv.ptr(self._dlt), n_slots, S.k, lay, m, gd.data_ptr(),
+                                       nv.ptr(self._scratch), self._scratch_bytes, 0, st), 'ure_nmf_weight_grad')
+        nv.check(L.ure_nmf_row_sum(nv.ptr(g.off_u), None, nv.ptr(self._rank), g.n_user, g.nnz, lo, n_slots, nv.ptr(self._emb), 2 * S.wd, 0, S.wd,
+                                   nv.ptr(self._err), gU.data_ptr(), nv.ptr(self._row_loss), st), 'ure_nmf_row_sum')
+        nv.check(L.ure_nmf_row_sum(nv.ptr(g.off_i), nv.ptr(g.to_csr), nv.ptr(self._rank), g.n_item, g.nnz, lo, n_slots, nv.ptr(self._emb), 2 * S.wd,
+                                   S.wd, S.wd, None, gV.data_ptr(), None, st), 'ure_nmf_row_sum')
+        nv.check(L.ure_gcn_step_loss(nv.ptr(self._row_loss), g.n_user, int(s == 0), self._sse[e:].data_ptr(), st), 'ure_gcn_step_loss')
+        nv.check(L.ure_gcn_sgd_step(self._pool[0].data_ptr(), self._pool[1].data_ptr(), self._pool[2].data_ptr(), self.n_params, 1.0,
+                                    float(self._lr_host[e]), self._lam, self._mu, int(self.done == 0), st), 'ure_gcn_sgd_step')
+        self.done += 1
+
+    # ---- what Scratch._train uses of a job -----------------------------------------------------------------------------
+    def steps_per_epoch(self, s=0):
+        return self.steps
+
+    def run_epochs(self, n_epochs, stream=None):
+        """Advance by whole epochs on `stream` (default: the current one).  Nothing synchronises."""
+        assert self._pool is not None, 'the job is closed'
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(self.device))          # (the uploads and fills of __init__)
+        e0 = self.done // self.steps
+        assert self.done % self.steps == 0 and e0 + n_epochs <= self.epochs
+        for e in range(e0, e0 + n_epochs):
+            for s in range(self.steps):
+                self._step(e, s, stream)
+        return self.done
+
+    def run(self, stream=None):
+        return self.run_epochs(self.epochs - self.done // self.steps, stream)
+
+    def params(self):
+        """(U [n_user, k + e], V [n_item, k + e], dense): views of the job's current parameters."""
+        return self._part(0)
+
+    def epoch_sse(self, s=0):
+        """Per-epoch sum of squared training errors (host float64 array; synchronises)."""
+        assert s == 0
+        return self._sse[:self.epochs].cpu().numpy()
+
+    def close(self):
+        self._pool = self._file_rank = self._rank = self._err = self._act = self._dlt = self._emb = self._scratch = self._row_loss = self._sse = None
 
 
 # ---------------------------------------------------------------------------

@@ -23,7 +23,11 @@ Same flags, defaults and assertions; additions are optional:
   --lr           learning rate (default 0.001, config.py:27)
   --model        'mf' (default) or 'lightgcn': the graph backbone (ultrare_amd/lightgcn.py, csrc/gcn.hip), trained shard after
                  shard whatever --parallel says, artifacts under LightGCN_* with the parameters as base_user_mat / base_item_mat
-  --gcn-layers   propagations per side of the 'lightgcn' backbone, 0 .. 8 (default 2).  --layer stays the reference's unused DMF flag
+  --gcn-layers   propagations per side of the 'lightgcn' backbone, 0 .. 8 (default 2)
+  --model nmf    the NeuMF backbone (ultrare_amd/nmf.py, csrc/nmf.hip): GMF of width --k beside an MLP whose stack is
+                 --layer L0 L1 .. Lm (the reference's "setting of layers"; powers of two, 1 .. 4 fully connected layers), trained shard
+                 after shard with SGD on the MSE loss, artifacts under NMF_* with the four tables as user_mat_mf / user_mat_mlp /
+                 item_mat_mf / item_mat_mlp.  'mf' and 'lightgcn' do not read --layer
   --loss         'mse' (default: the reference's MSELoss(sum) on the rating) or 'bpr': the pairwise BPR loss, one negative per triple and
                  epoch drawn on the device (ultrare_amd/bpr.py, csrc/bpr.hip).  Needs --model lightgcn (--gcn-layers 0 is
                  BPR-MF); artifacts under LightGCN_bpr_*; train_loss is the mean batch loss; judge the result with rank_eval
@@ -50,12 +54,20 @@ parser.add_argument('--parallel', type=int, default=1, help='1 (default): shards
 parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', or 'rating-ot' (OT groups), 'rating-bkmeans', 'rating-bkmedoids', 'rating-blpa' (balanced k-means / k-medoids / label propagation groups) on the sparse rating matrix, no --group 0 run needed")
 parser.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adam'], help="'sgd' (reference) or 'adam'")
 parser.add_argument('--lr', type=float, default=None, help='learning rate (default 0.001)')
-parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn'], help="'mf' (reference) or 'lightgcn'")
+parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn', 'nmf'], help="'mf' (reference), 'lightgcn' or 'nmf' (NeuMF; its MLP is --layer)")
 parser.add_argument('--gcn-layers', type=int, default=2, help="propagations per side of the 'lightgcn' backbone (0 .. 8)")
 parser.add_argument('--loss', type=str, default='mse', choices=['mse', 'bpr'], help="'mse' (reference) or 'bpr' (needs --model lightgcn)")
 parser.add_argument('--unlearn', type=str, default='retrain', choices=['retrain', 'influence'], help="'retrain' (reference) or 'influence' (Newton steps, no retraining; --model mf --loss mse)")
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
+
+
+def layer_ints(layer):
+    """--layer as integers for the 'nmf' backbone (ValueError names the value that is none)."""
+    try:
+        return [int(i) for i in layer]
+    except ValueError:
+        raise ValueError(f'--layer takes integers, not {layer!r}') from None
 
 
 def main(argv=None):
@@ -66,6 +78,8 @@ def main(argv=None):
     assert args.worker > 0
     assert args.verbose in [0, 1, 2]
     assert args.group >= 0
+    if args.model == 'nmf':          # values given on the command line arrive as strings; the other models see them as they came
+        args.layer = layer_ints(args.layer)
     for i in args.layer:
         assert type(i) == int
     assert args.learn in ['sisa']

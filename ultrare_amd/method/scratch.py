@@ -16,7 +16,7 @@ from torch import nn
 
 from .. import engine, rng
 from ..read import as_loader
-from .utils import MF, padded_tables, seed_all
+from .utils import MF, NMF, padded_tables, seed_all
 
 PERM_THREADS = rng.perm_threads()
 # end-of-epoch snapshots kept on the device for the per-epoch test series (per job).  They hold the rows with interactions in
@@ -118,8 +118,17 @@ class Scratch(object):
                     'total_hr': [],
                     'time': []}
 
-        if self.model_type not in ('mf', 'lightgcn'):
-            raise NotImplementedError("model_type is 'mf' on the published path (config.py:185-199), or 'lightgcn' (ultrare_amd/lightgcn.py)")
+        if self.model_type not in ('mf', 'lightgcn', 'nmf'):
+            raise NotImplementedError("model_type is 'mf' on the published path (config.py:185-199), 'lightgcn' (ultrare_amd/lightgcn.py) or 'nmf' "
+                                      "(ultrare_amd/nmf.py)")
+        if self.model_type == 'nmf':
+            # the neural backbone (engine.NmfJob): SGD on the MSE loss only; `layers` is the MLP stack [L0, .., Lm]
+            from ..nmf import check_layers as check_stack
+            if self.optimizer != 'sgd':
+                raise ValueError(f"model_type='nmf' trains with optimizer='sgd' only, not {self.optimizer!r}")
+            if getattr(param, 'loss', 'mse') != 'mse':
+                raise ValueError(f"model_type='nmf' trains with loss='mse' only, not {param.loss!r}")
+            self.k, self.layers = check_stack(self.k, getattr(param, 'layers', None))
         if self.model_type == 'lightgcn':
             # the graph backbone (engine.GcnJob): SGD only, gcn_layers propagations per side
             from ..lightgcn import check_layers
@@ -161,6 +170,8 @@ class Scratch(object):
         if self.model_type == 'lightgcn':
             job, series = self._gcn_job(train_data, has_total, given_model, id), False     # (the per-epoch branch: no queued series)
             n_train, device = job.graph.N, job.device
+        elif self.model_type == 'nmf':
+            return self._train_nmf(train_data, test_data, test_total, has_total, verbose, save_dir, id, given_model)
         else:
             shard, init, perms = prepare_shard(train_data, self.n_user, self.n_item, self.k, self.epochs, has_total, given_model)
             batch = as_loader(train_data).batch_size
@@ -234,6 +245,47 @@ class Scratch(object):
         self.save(model, save_dir, id)
         return model
 
+    def _nmf_job(self, train_data, has_total, given_model):
+        """The job of a NeuMF request: the model's draws (utils.NMF, on the CPU after seed_all), then the epochs' seeds as an MF
+        request draws them; the orders are the epochs' permutations as file positions."""
+        if not (_is_empty(given_model) or given_model == ''):
+            raise ValueError("given_model is not supported with model_type='nmf': the job starts from NMF's own init")
+        loader = as_loader(train_data)
+        init = tuple(t.numpy() for t in NMF(self.n_user, self.n_item, self.k, self.layers).tables())
+        seeds = rng.epoch_seeds(self.epochs, has_total)
+        n = len(loader.dataset)
+        orders = rng.epoch_perms(seeds, n, threads=PERM_THREADS) if loader.shuffle else torch.arange(n, dtype=torch.int32).repeat(self.epochs, 1)
+        graph = engine.GcnGraph(*loader.dataset.triples(), self.n_user, self.n_item)
+        return engine.NmfJob(graph, init, orders, self.k, self.layers, loader.batch_size, self.epochs, self.lr, self.lam, self.momentum, self.lr_decay)
+
+    def _train_nmf(self, train_data, test_data, test_total, has_total, verbose, save_dir, id, given_model):
+        """_train for the 'nmf' backbone: the per-epoch branch (no queued series), every epoch's two tests through
+        EvalSet.evaluate_nmf on the models trained before (Sisa) and the job's current parameters."""
+        job = self._nmf_job(train_data, has_total, given_model)
+        test_ev = as_loader(test_data).eval_set()
+        total_ev = as_loader(test_total).eval_set() if has_total else None
+        before = [m.tables() + (m.k, m.layers) for m in self._models_before()]
+        for t in range(self.epochs):
+            epoch_start = time.time()
+            job.run_epochs(1)
+            models = before + [job.params() + (self.k, self.layers)]
+            test = test_ev.evaluate_nmf(models)
+            total = total_ev.evaluate_nmf(models) if has_total else test
+            train_loss = float(np.sqrt(job.epoch_sse(0) / job.graph.N)[t])
+            epoch_time = time.strftime('%H:%M:%S', time.gmtime(time.time() - epoch_start))
+            print_epoch(verbose, t, self.epochs, train_loss, test, total, has_total, epoch_time)
+            self.log['train_loss'].append(train_loss)
+            for c, key in enumerate(('test_rmse', 'test_ndcg', 'test_hr')):
+                self.log[key].append(test[c])
+            self.log['time'].append(epoch_time)
+            if has_total:
+                for c, key in enumerate(('total_rmse', 'total_ndcg', 'total_hr')):
+                    self.log[key].append(total[c])
+        model = NMF.from_tables(*(t.clone() for t in job.params()), self.k, self.layers)
+        job.close()
+        self.save(model, save_dir, id)
+        return model
+
     def _train_loss(self, job, n_train):
         """The train_loss series of a job: sqrt(sse / N) (utils.py:101-103), or under BPR the reference's is_rmse == False
         reporting, loss_sum / N (utils.py:104-106)."""
@@ -262,8 +314,16 @@ class Scratch(object):
 
     def save(self, model, save_dir, id):
         """scratch.py:131-144: model{id}.pth, user_mat{id}.npy, item_mat{id}.npy, log{id}.npy; a LightGCN model's parameters beside
-        them as base_user_mat{id}.npy and base_item_mat{id}.npy."""
+        them as base_user_mat{id}.npy and base_item_mat{id}.npy.  An NMF model: model{id}.pth, user_mat_mf{id}.npy, user_mat_mlp{id}.npy,
+        item_mat_mf{id}.npy, item_mat_mlp{id}.npy, log{id}.npy."""
         from .utils import dist_rank
+        if isinstance(model, NMF):                          # the reference's attribute names (method/sisa.py:39-50) as file names
+            if len(save_dir) > 0 and dist_rank()[0] == 0:
+                torch.save(model.state_dict(), save_dir + '/model' + str(id) + '.pth')
+                for name in ('user_mat_mf', 'user_mat_mlp', 'item_mat_mf', 'item_mat_mlp'):
+                    np.save(save_dir + '/' + name + str(id), getattr(model, name).weight.detach().cpu().numpy())
+                np.save(save_dir + '/log' + str(id), self.log)
+            return
         if len(save_dir) > 0 and dist_rank()[0] == 0:       # several ranks running the same call: one set of files
             torch.save(model.state_dict(), save_dir + '/model' + str(id) + '.pth')
             np.save(save_dir + '/user_mat' + str(id), model.user_mat.weight.detach().cpu().numpy())

@@ -198,11 +198,11 @@ class Sisa(Scratch):
         self.n_group = n_group
         self.group_index = group_index
         self.parallel = bool(getattr(param, 'parallel', False))
-        if self.model_type == 'lightgcn':
+        if self.model_type in ('lightgcn', 'nmf'):
             self._gcn_one_rank()
-            if self.parallel:           # a GcnJob holds one shard: the shards train one after the other
+            if self.parallel:           # a GcnJob / NmfJob holds one shard: the shards train one after the other
                 import warnings
-                warnings.warn("model_type='lightgcn' trains its shards one after the other: parallel is ignored")
+                warnings.warn(f"model_type={self.model_type!r} trains its shards one after the other: parallel is ignored")
                 self.parallel = False
         self.epoch_logs = bool(getattr(param, 'epoch_logs', True))   # parallel mode: rebuild the per-epoch test logs
         self.model_list = []
@@ -211,8 +211,13 @@ class Sisa(Scratch):
 
     def _gcn_one_rank(self):
         dist = _dist()
-        if self.model_type == 'lightgcn' and dist is not None and dist.get_world_size() > 1:
-            raise ValueError(f"model_type='lightgcn' runs on one rank, not {dist.get_world_size()}")
+        if self.model_type in ('lightgcn', 'nmf') and dist is not None and dist.get_world_size() > 1:
+            raise ValueError(f"model_type={self.model_type!r} runs on one rank, not {dist.get_world_size()}")
+
+    def _refuse_nmf(self, who):
+        """`who` is defined for models scored as the dot product of two tables."""
+        if getattr(self, 'model_type', 'mf') == 'nmf':
+            raise ValueError(f"Sisa.{who} needs a model scored as the dot product of two tables ('mf' or 'lightgcn'), not the 'nmf' backbone")
 
     def test(self, test_data, verbose, save_dir):
         dist = _dist()
@@ -237,6 +242,7 @@ class Sisa(Scratch):
         ratings a deletion removes, so it is refitted on the post-deletion train_dlist.  Every rank of a parallel run holds
         the merged models and fits its own (bitwise the same)."""
         from ..combine import check_fit_args
+        self._refuse_nmf('fit_combiner')
         check_fit_args(link, l2, 25, 1e-10)
         if len(train_dlist) != self.n_group:
             raise ValueError(f'{len(train_dlist)} training loaders for {self.n_group} groups')
@@ -248,6 +254,7 @@ class Sisa(Scratch):
     def test_combined(self, test_data, verbose, save_dir):
         """Sisa.test with the fitted weights: (rmse, ndcg, hr), kept in self.log0c and saved as log0c.npy beside log0.npy.
         Sisa.test and log0 stay the mean's."""
+        self._refuse_nmf('test_combined')
         if getattr(self, 'combiner', None) is None:
             raise ValueError('no combiner: call fit_combiner after learn / unlearn (a deletion drops the fitted weights)')
         rmse, ndcg, hr = baseTest(test_data, self.model_list, nn.MSELoss(reduction='sum'), self.device, verbose, combiner=self.combiner)
@@ -279,7 +286,15 @@ class Sisa(Scratch):
             fut.result()
 
     def _merge(self, merged, ids):
-        """sisa.py:52-58 / 107-113: merged[group_index[i]] = U_i[group_index[i]]."""
+        """sisa.py:52-58 / 107-113: merged[group_index[i]] = U_i[group_index[i]]; for 'nmf' both user tables (sisa.py:39-50, 92-104),
+        merged = {attribute name: table}."""
+        if self.model_type == 'nmf':
+            for name, table in merged.items():
+                for i in ids:
+                    engine.merge_rows(table, getattr(self.model_list[i], name).weight.detach().contiguous(), self._rows_dev(i))
+                for m in self.model_list:
+                    getattr(m, name).weight = nn.Parameter(table, requires_grad=False)
+            return
         for i in ids:
             src = self.model_list[i].user_mat.weight.detach().contiguous()
             engine.merge_rows(merged, src, self._rows_dev(i))
@@ -494,7 +509,7 @@ class Sisa(Scratch):
                 self.model_list.append(model)
 
         # merge user mat (sisa.py:52-58)
-        merged = torch.zeros_like(self.model_list[0].user_mat.weight.detach()).contiguous()
+        merged = self._merge_target(self.model_list[0], zero=True)
         self._merge(merged, range(self.n_group))
         engine.mark('merged')
 
@@ -502,6 +517,13 @@ class Sisa(Scratch):
         self.test(test_data, verbose, save_dir)
         engine.mark('tested')
         return self.model_list
+
+    def _merge_target(self, model, zero=False):
+        """What _merge writes into: a new table shaped as (zero) or copied from `model`'s user table -- for 'nmf' one per user table."""
+        make = (lambda t: torch.zeros_like(t.detach()).contiguous()) if zero else (lambda t: t.detach().clone().contiguous())
+        if self.model_type == 'nmf':
+            return {name: make(getattr(model, name).weight) for name in ('user_mat_mf', 'user_mat_mlp')}
+        return make(model.user_mat.weight)
 
     # ------------------------------------------------------------------ fold-in
     def _merged_table(self):
@@ -536,6 +558,7 @@ class Sisa(Scratch):
         ValueError before any device work.  Returns (users ascending int64, their groups int64).  forget_folded deletes them
         exactly."""
         from ..ridge import check_ridge_args
+        self._refuse_nmf('fold_in')
         check_ridge_args(l2, l2_n)
         if against not in ('home', 'ensemble'):
             raise ValueError(f"against must be 'home' or 'ensemble', not {against!r}")
@@ -619,6 +642,7 @@ class Sisa(Scratch):
         the rows this call moves); test, recommend, rank_eval and unlearn read the table itself and see the new rows.
         ValueError before any device work for groups that are empty, overlap, repeat a user or leave the table."""
         from ..attr_unlearn import check_groups
+        self._refuse_nmf('attribute_unlearn')
         if not self.model_list:
             raise ValueError('attribute_unlearn needs trained models: call learn first')
         rows, n1, _ = check_groups(id1, id2, self.n_user)
@@ -645,12 +669,14 @@ class Sisa(Scratch):
     def recommend(self, users, top_k=10, exclude=None):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers
         from the retrained shards.  Every rank of a parallel run holds the merged models and answers its own queries."""
+        self._refuse_nmf('recommend')
         return recommend(self.model_list, users, top_k, exclude)
 
     def rank_eval(self, test_data, exclude=None, ks=(10, 20)):
         """Full-ranking HR@K / Recall@K / NDCG@K / MRR of the current ensemble on a test loader (utils.rank_eval over
         self.model_list): after unlearn it evaluates the retrained shards.  Every rank of a parallel run holds the merged models
         and answers for itself."""
+        self._refuse_nmf('rank_eval')
         return rank_eval(self.model_list, test_data, exclude, ks)
 
     def unlearn(self, model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir):
@@ -678,7 +704,7 @@ class Sisa(Scratch):
         self.folded = {u: g for u, g in getattr(self, 'folded', {}).items() if g not in retrain_gid}
 
         model_before_unlearn = model_list[0]
-        merged = model_before_unlearn.user_mat.weight.detach().clone().contiguous()
+        merged = self._merge_target(model_before_unlearn)
 
         if self.parallel:
             ids = list(retrain_gid)

@@ -3,7 +3,9 @@ the reference), backed by the HIP engine.
 
   seed_all     utils.py:21-25
   MF           utils.py:30-43    two embedding tables; forward = row-wise dot
-  baseTest     utils.py:115-187  ensemble mean score, RMSE, HR@10, NDCG@10
+  NMF          (new)             NeuMF: the reference's user_mat_mf / user_mat_mlp (sisa.py:39-50) beside an MLP and a head; forward =
+                                 the HIP scoring kernel of csrc/nmf.hip; refuse_nmf: what needs two dot-product tables says so
+  baseTest     utils.py:115-187  ensemble mean score, RMSE, HR@10, NDCG@10 (a list of MF models or a list of NMF models)
   fit_combiner (new)             fitted weights of the shard scores in place of their mean (baseTest(..., combiner=))
   recommend    (new)             top-k items over the whole catalogue from the same ensemble mean
   rank_eval    (new)             full-ranking HR@K / Recall@K / NDCG@K / MRR of the test pairs (rank_metrics: the reduction)
@@ -93,8 +95,92 @@ class MF(nn.Module):
         return pred
 
 
+class NMF(nn.Module):
+    """NeuMF as rating regression (ultrare_amd/nmf.py): the reference's attribute names user_mat_mf, item_mat_mf, user_mat_mlp,
+    item_mat_mlp (method/sisa.py:39-50), the MLP fc[j] = nn.Linear(L_j, L_(j+1)) and the head nn.Linear(k + Lm, 1).
+    Constructed on the CPU after seed_all, like MF.  The draws from torch's generator, in order: the four embeddings' normal_(std=0.01)
+    fills in the order above (they are made without nn.Embedding's own N(0, 1) fill: nothing is drawn and thrown away), then torch's
+    default fill of every nn.Linear in layer order, the head last.
+    forward() scores (uid, iid) pairs with the HIP scoring kernel (no sigmoid: the loss is MSELoss(sum) on rating / 5)."""
+
+    EMB_STD = 0.01
+
+    def __init__(self, n_user, n_item, k, layers):
+        from ..nmf import check_layers
+        super().__init__()
+        self.k, self.layers = check_layers(k, layers)
+        e = self.layers[0] // 2
+        def emb(rows, width):                               # (skip_init: no N(0, 1) fill first)
+            table = nn.utils.skip_init(nn.Embedding, rows, width)
+            nn.init.normal_(table.weight, std=self.EMB_STD)
+            return table
+        self.user_mat_mf = emb(n_user, self.k)
+        self.item_mat_mf = emb(n_item, self.k)
+        self.user_mat_mlp = emb(n_user, e)
+        self.item_mat_mlp = emb(n_item, e)
+        self.fc = nn.ModuleList([nn.Linear(a, b) for a, b in zip(self.layers[:-1], self.layers[1:])])
+        self.head = nn.Linear(self.k + self.layers[-1], 1)
+
+    @classmethod
+    def from_tables(cls, U, V, dense, k, layers):
+        """Wrap trained device tensors (nmf.py's U [n_user, k + e], V [n_item, k + e] and dense vector) without drawing from any
+        generator: every parameter is a copy-free view or a contiguous copy of them."""
+        from ..nmf import Shape
+        S = Shape(k, layers)
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        m.k, m.layers = S.k, S.layers
+        emb = lambda t: nn.Embedding(t.shape[0], t.shape[1], _weight=t.contiguous())
+        m.user_mat_mf, m.item_mat_mf = emb(U[:, :S.k]), emb(V[:, :S.k])
+        m.user_mat_mlp, m.item_mat_mlp = emb(U[:, S.k:]), emb(V[:, S.k:])
+        W, b, h, c = S.unpack(dense)
+
+        def linear(weight, bias):                             # (skip_init: no default fill, so no draw)
+            lin = nn.utils.skip_init(nn.Linear, weight.shape[1], weight.shape[0])
+            lin.weight, lin.bias = nn.Parameter(weight.clone()), nn.Parameter(bias.clone())
+            return lin
+        m.fc = nn.ModuleList([linear(Wj, bj) for Wj, bj in zip(W, b)])
+        m.head = linear(h.reshape(1, -1), c.reshape(1))
+        m.requires_grad_(False)
+        return m
+
+    def tables(self):
+        """(U [n_user, k + e], V [n_item, k + e], dense) float32 on the parameters' device, as nmf.py and the kernels hold a model.
+        Packed once and kept until a parameter is replaced, moved or written in place (its address or version changes): forward and
+        baseTest do not concatenate the tables again per call.  Read-only for the caller."""
+        from ..nmf import Shape
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        kept = getattr(self, '_packed', None)
+        if kept is not None and kept[0] == key:
+            return kept[1]
+        S = Shape(self.k, self.layers)
+        w = lambda p: p.detach().float()
+        U = torch.cat([w(self.user_mat_mf.weight), w(self.user_mat_mlp.weight)], dim=1).contiguous()
+        V = torch.cat([w(self.item_mat_mf.weight), w(self.item_mat_mlp.weight)], dim=1).contiguous()
+        parts = [p.reshape(-1) for lin in self.fc for p in (w(lin.weight), w(lin.bias))] + [w(self.head.weight).reshape(-1), w(self.head.bias).reshape(-1)]
+        dense = torch.cat(parts + [U.new_zeros(S.n_dense - S.n_real)])
+        self._packed = (key, (U, V, dense))
+        return U, V, dense
+
+    def forward(self, uid, iid):
+        U, V, dense = self.tables()
+        if not U.is_cuda:
+            raise nv.NativeError('model tables are not on the HIP device (call model.to("cuda")): no CPU fallback')
+        return engine.nmf_score(U, V, dense, self.k, self.layers, uid.to(device=U.device, dtype=torch.int32).contiguous(),
+                                iid.to(device=U.device, dtype=torch.int32).contiguous())
+
+
+def refuse_nmf(models, who):
+    """ValueError when `who` -- something defined for a model scored as the dot product of two tables -- is handed the 'nmf' backbone."""
+    for m in (models if isinstance(models, (list, tuple)) else [models]):
+        if isinstance(m, NMF):
+            raise ValueError(f"{who} needs a model scored as the dot product of two tables ('mf' or 'lightgcn'): the 'nmf' backbone scores "
+                             'a pair through an MLP and has no such tables')
+
+
 def padded_tables(model):
     """(U, V, d) as contiguous device tensors whose width is the kernels' padded d."""
+    refuse_nmf(model, 'padded_tables')
     U, V = model.user_mat.weight.detach(), model.item_mat.weight.detach()
     if not U.is_cuda:
         raise nv.NativeError('model tables are not on the HIP device (call model.to("cuda")): no CPU fallback')
@@ -113,7 +199,17 @@ def baseTest(dataloader, models, loss_fn=None, device=None, verbose=0, top_k=10,
     """utils.py:115-187: (rmse, ndcg, hr) of the mean-ensemble of `models` on a test
     loader.  loss_fn / device are accepted for signature compatibility.  combiner (fit_combiner's result, optional): the
     pairs are scored with its fitted weights instead of the mean; without one nothing changes."""
+    n_nmf = sum(isinstance(m, NMF) for m in models)
+    if n_nmf and n_nmf != len(models):
+        raise ValueError(f"baseTest takes models of one backbone: {n_nmf} of {len(models)} are 'nmf'")
+    if n_nmf and combiner is not None:
+        refuse_nmf(models, 'baseTest(combiner=)')
     ev = as_loader(dataloader).eval_set()
+    if n_nmf:                                                # one scoring call per model (engine.EvalSet.evaluate_nmf); the rest is shared
+        rmse, ndcg, hr = ev.evaluate_nmf([m.tables() + (m.k, m.layers) for m in models], top_k=top_k)
+        if verbose == 2:
+            print(f'Test - RMSE: {rmse:>.4f}, NDCG: {ndcg:>.3f}, HR: {hr:>.3f}')
+        return rmse, ndcg, hr
     tabs = [padded_tables(m) for m in models]
     d = tabs[0][2]
     if combiner is None:
@@ -138,6 +234,7 @@ def fit_combiner(models, train_data, link='linear', l2=0.0, groups=None, max_ite
     work) and for a singular system (naming l2)."""
     check_fit_args(link, l2, max_iter, tol)
     S = len(models)
+    refuse_nmf(models, 'fit_combiner')
     if not 1 <= S <= nv.MAX_MODELS_PER_CALL:
         raise ValueError(f'fit_combiner takes 1 .. {nv.MAX_MODELS_PER_CALL} models, not {S}')
     many = isinstance(train_data, (list, tuple))
@@ -218,6 +315,7 @@ def fold_in(models, data, l2, l2_n=0.0, item_table='mean'):
     from ..ridge import check_ridge_args
     l2, l2_n = check_ridge_args(l2, l2_n)
     S = len(models)
+    refuse_nmf(models, 'fold_in')
     if S < 1:
         raise ValueError('fold_in needs at least one model')
     _check_item_table(item_table, S)
@@ -263,6 +361,7 @@ def als_sweeps(model, train_data, l2, l2_n=0.0, sweeps=1):
     l2, l2_n = check_ridge_args(l2, l2_n)
     if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or sweeps < 0:
         raise ValueError(f'sweeps must be an integer >= 0, not {sweeps!r}')
+    refuse_nmf(model, 'als_sweeps')
     uid, iid, r = _rating_triple(train_data)
     U, V, d = padded_tables(model)
     k, dev = int(model.k), U.device
@@ -286,6 +385,7 @@ def recommend(models, users, top_k=10, exclude=None):
     `models`, bit for bit), ties by ascending item id.  exclude: a scipy CSR with user ids as rows (read.readSparseMat of the
     training set) whose items are never returned.  Returns (scores [n, top_k], items [n, top_k] int64) on the device; a user
     with fewer eligible items than top_k gets (NaN, -1) at the end.  The full model is recommend([model], ...)."""
+    refuse_nmf(models, 'recommend')
     tabs = [padded_tables(m) for m in models]
     users = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
     excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
@@ -348,6 +448,7 @@ def rank_eval(models, test_data, exclude=None, ks=(10, 20)):
     them, and HR@K, Recall@K, NDCG@K and MRR are taken from those ranks (rank_metrics; every test pair is relevant, no rating
     threshold).  These are NOT baseTest's HR@10 / NDCG@10, which rank a user's test items only against each other.  A test pair
     that is also in `exclude` does not count.  Returns the dict of rank_metrics."""
+    refuse_nmf(models, 'rank_eval')
     tabs = [padded_tables(m) for m in models]
     users, off, items = relevant_pairs(test_data, int(tabs[0][1].shape[0]))
     excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
@@ -896,6 +997,7 @@ def attribute_unlearn(model, id1, id2, var='d2d', eta=1.0, alpha=0.0, lr=0.1, st
     overlap, repeat a row or leave the table, and for var outside {'d2d', 'u2u'}; ValueError as well for a bandwidth that is
     not positive and finite (at entry: before any change)."""
     from ..attr_unlearn import check_bandwidth
+    refuse_nmf(model, 'attribute_unlearn')
     var, eta, alpha, lr, steps, kernel_mul, kernel_num, fix_sigma = attribute_unlearn_check(var, eta, alpha, lr, steps, kernel_mul, kernel_num, fix_sigma)
     W = model.user_mat.weight
     groups = engine.GroupRows(id1, id2, W.shape[0], W.device if W.is_cuda else None)
@@ -959,6 +1061,7 @@ def newton_unlearn(model, train_data, l2=None, batch=None, lam=None, damping=Non
     any device work."""
     from .. import influence
     uid, iid, r = _rating_triple(train_data)
+    refuse_nmf(model, 'newton_unlearn')
     l2, damping = newton_unlearn_check('mf', 'mse', l2, batch, lam, damping, curvature, steps, iters, tol, len(uid))
     W_u, W_v = model.user_mat.weight, model.item_mat.weight
     n_user, n_item = int(W_u.shape[0]), int(W_v.shape[0])

@@ -52,6 +52,9 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         (new)             (HU, HV) float64: the product of the MSE objective's
                                                                           Hessian (full) or Gauss-Newton matrix, plus 2 damping I,
                                                                           with a float64 direction (ultrare_amd/influence.py)
+    torch.ops.ultrare.nmf_score(U, V, dense, k, layers, uid, iid)
+                                                        (new)             the NeuMF forward of one model (ultrare_amd/nmf.py: U, V
+                                                                          [rows, k + layers[0] / 2], dense the layers and the head)
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -446,3 +449,18 @@ def inf_matvec(off_u: torch.Tensor, col: torch.Tensor, row_u: torch.Tensor, off_
 @inf_matvec.register_fake
 def _(off_u, col, row_u, off_i, row, to_csr, rating, U, V, P, Q, l2, damping=0.0, full=True):
     return torch.empty_like(P), torch.empty_like(Q)
+
+
+@torch.library.custom_op('ultrare::nmf_score', mutates_args=())
+def nmf_score(U: torch.Tensor, V: torch.Tensor, dense: torch.Tensor, k: int, layers: List[int], uid: torch.Tensor, iid: torch.Tensor) -> torch.Tensor:
+    """engine.nmf_score of one model at the pairs (uid, iid): the bytes the training forward gives (nmf.forward_ref in float32)."""
+    from . import nmf
+    nmf.check_layers(k, list(layers))                        # (a bad stack is a ValueError before anything else)
+    _dev(U, V, dense, uid, iid)
+    return engine.nmf_score(U.contiguous(), V.contiguous(), dense.contiguous(), k, list(layers), uid.to(torch.int32).contiguous(),
+                            iid.to(torch.int32).contiguous())
+
+
+@nmf_score.register_fake
+def _(U, V, dense, k, layers, uid, iid):
+    return U.new_empty(uid.numel())
