@@ -785,5 +785,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_influence.h"
 /* The NeuMF backbone (csrc/nmf.hip): per-sample MLP forward / backward, weight-gradient sums, masked row sums and scoring. */
 #include "ultrare_nmf.h"
+/* Full-catalogue top-k and exact ranks under a NeuMF ensemble (csrc/nmf_rank.hip): one lane per item, the layer-0 user prefix shared. */
+#include "ultrare_nmf_rank.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -228,6 +228,17 @@ _NMF_PROTOTYPES = {
 }
 NMF_EXPORTS = tuple(_NMF_PROTOTYPES)
 
+# include/ultrare_nmf_rank.h (top-k and exact ranks under a NeuMF ensemble, csrc/nmf_rank.hip): a table of its own, as the header is;
+# tests/test_cpu_nmf_rank.py holds the table, the header and the library to each other, tests/test_gpu_nmf_rank.py runs both entries in guard zones.
+_NMF_MODELS = [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i32] + _NMF_SHAPE     # U_tables, V_tables, dense_vecs (HOST arrays), n_models, the stack
+_NMF_RANK_PROTOTYPES = {
+    'ure_nmf_recommend_scratch': (_i64, [_i64, _i32, _i32, _i32] + _NMF_SHAPE),
+    'ure_nmf_recommend_topk': (ctypes.c_int, _NMF_MODELS + [_i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'ure_nmf_rank_pairs_scratch': (_i64, [_i64, _i64, _i32, _i32] + _NMF_SHAPE),
+    'ure_nmf_rank_pairs': (ctypes.c_int, _NMF_MODELS + [_i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
+NMF_RANK_EXPORTS = tuple(_NMF_RANK_PROTOTYPES)
+
 _lib = None
 
 
@@ -243,7 +254,7 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

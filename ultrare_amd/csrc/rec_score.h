@@ -119,4 +119,26 @@ __device__ __forceinline__ float rec_score_pair(const float *const *tab, int n_m
     return acc / n_s;
 }
 
+// The MF ensemble as a scorer policy of the selection (rec_select.h) and counting (rank_count.h) kernels: rec_score_tile over
+// Us [QT][D] and Vs [64][D + 4] at the head of the workgroup's LDS, rec_score_pair straight from the tables.
+template <int LPR>
+struct MfScorer {
+    static constexpr int QW = LPR * 4 >= 256 ? 4 : 8;
+    static constexpr int D = LPR * 4;
+    static constexpr int QT = kWavesPerBlock * QW;
+    struct Ctx {
+        const float *const *tab;     // [2 * S] device: U_0 .. U_{S-1}, V_0 .. V_{S-1}
+        int n_models;
+    };
+    __host__ __device__ static constexpr int tile_lds(const Ctx &) { return (QT * D + kRecItems * (D + 4)) * 4; }
+    __host__ __device__ static constexpr int pair_lds(const Ctx &) { return 0; }
+    __device__ __forceinline__ static void tile(float (&s)[QW], const Ctx &C, char *lds, const int32_t *uid, int64_t q0, int64_t n_query, int i0,
+                                                int ie)
+    {
+        float *Us = reinterpret_cast<float *>(lds);
+        rec_score_tile<LPR, QW>(s, C.tab, C.n_models, Us, Us + QT * D, uid, q0, n_query, i0, ie);
+    }
+    __device__ __forceinline__ static float pair(const Ctx &C, char *, int user, int item) { return rec_score_pair<LPR>(C.tab, C.n_models, user, item); }
+};
+
 }  // namespace ure

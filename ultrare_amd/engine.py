@@ -2384,6 +2384,103 @@ def nmf_score(U, V, dense, k, layers, uid, iid, rating=None, pred=None, sse=None
     return pred
 
 
+def _nmf_models(models, k, layers, who):
+    """The checks every catalogue sweep makes of its ensemble: models = [(U, V, dense)] device tensors of ONE stack.
+    -> (Shape, device, n_user, n_item, the three host pointer arrays, the host layers array)."""
+    from . import nmf
+    S = nmf.Shape(k, layers)                                # (the ValueError of a bad stack comes before any device work)
+    models = list(models)
+    if not models:
+        raise ValueError(f'{who} needs at least one model')
+    for m in models:
+        if len(m) != 3:
+            raise ValueError(f'{who}: a model is (U, V, dense), not {len(m)} tensors')
+        for t in m:
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise nv.NativeError(f'{who} runs on the HIP device only (no CPU fallback)')
+    dev, n_user, n_item = models[0][0].device, int(models[0][0].shape[0]), int(models[0][1].shape[0])
+    for U, V, dense in models:
+        _nmf_tensor(U, (n_user, S.wd), torch.float32, 'U', dev)
+        _nmf_tensor(V, (n_item, S.wd), torch.float32, 'V', dev)
+        _nmf_tensor(dense, (S.n_dense,), torch.float32, 'dense', dev)
+    ptrs = tuple((ctypes.c_void_p * len(models))(*[m[j].data_ptr() for m in models]) for j in range(3))
+    return S, dev, n_user, n_item, ptrs, _nmf_layers(S.layers)
+
+
+def _query_users(users, n_user, who):
+    users = users.detach().cpu().numpy() if torch.is_tensor(users) else np.asarray(users)
+    users = users.astype(np.int64).reshape(-1)
+    if users.size == 0:
+        raise ValueError(f'{who} needs at least one user')
+    if users.min() < 0 or users.max() >= n_user:
+        raise ValueError(f'user ids outside [0, {n_user})')
+    return users
+
+
+def nmf_recommend(models, k, layers, users, top_k, excl=None, stream=None):
+    """Top-k items of every user of `users` over the whole catalogue under a NeuMF ensemble (ure_nmf_recommend_topk; the contract
+    is nmf.recommend_ref): models = [(U, V, dense)] device tensors of one (k, layers), the scores those a chain of nmf_score calls
+    gives for the same pairs, bit for bit; excl = (off, items) from exclusion_rows or None.  Returns (scores [n, top_k] float32,
+    items [n, top_k] int64) on the device; padding is (NaN, -1)."""
+    S, dev, n_user, n_item, (Up, Vp, Dp), lay = _nmf_models(models, k, layers, 'nmf_recommend')
+    if isinstance(top_k, bool) or not 1 <= int(top_k) <= RECOMMEND_MAX_K:
+        raise ValueError(f'top_k = {top_k} outside [1, {RECOMMEND_MAX_K}]')
+    users = _query_users(users, n_user, 'nmf_recommend')
+    if excl is not None:
+        off, items = _check_rows(*(t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in excl), len(users), n_item, 'exclusion')
+    n, top_k = len(users), int(top_k)
+    uid = to_device_async(users.astype(np.int32), dev)
+    e_off = e_items = None
+    if excl is not None:
+        e_off = to_device_async(off, dev)
+        e_items = to_device_async(items if items.size else np.zeros(1, dtype=np.int32), dev)
+    L = nv.lib()
+    nbytes = int(L.ure_nmf_recommend_scratch(n, n_item, top_k, len(models), S.k, nv.ptr(lay), len(lay)))
+    if nbytes < 0:
+        raise ValueError(f'ure_nmf_recommend_scratch refused n_query = {n}, n_item = {n_item}, top_k = {top_k}, k = {S.k}, layers = {S.layers}')
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    scores = torch.empty(n, top_k, dtype=torch.float32, device=dev)
+    items_out = torch.empty(n, top_k, dtype=torch.int32, device=dev)
+    _csr_held_for(stream, *(t for t in (uid, e_off, e_items, scratch, scores, items_out) if t is not None))
+    nv.check(L.ure_nmf_recommend_topk(Up, Vp, Dp, len(models), S.k, nv.ptr(lay), len(lay), n_user, nv.ptr(uid), n, n_item, nv.ptr(e_off),
+                                      nv.ptr(e_items), top_k, nv.ptr(scores), nv.ptr(items_out), nv.ptr(scratch), scratch.numel(),
+                                      nv.stream_handle(stream)), 'ure_nmf_recommend_topk')
+    return scores, items_out.long()
+
+
+def nmf_rank_pairs(models, k, layers, users, targets, excl=None, stream=None):
+    """Exact full-catalogue rank of every (user, target item) pair under a NeuMF ensemble (ure_nmf_rank_pairs; the contract is
+    nmf.rank_ref): models as in nmf_recommend, targets = (off [n + 1], items) with query row q's targets items[off[q]:off[q + 1]]
+    (any order, duplicates, empty rows), excl = (off, items) or None.  rank = the number of non-excluded items whose (score, id)
+    key beats the target's -- the position nmf_recommend would give it -- or -1 for an excluded target.  Returns ranks
+    [len(items)] int32 on the device, in input order."""
+    S, dev, n_user, n_item, (Up, Vp, Dp), lay = _nmf_models(models, k, layers, 'nmf_rank_pairs')
+    users = _query_users(users, n_user, 'nmf_rank_pairs')
+    t_off, t_items = _check_rows(*(t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in targets), len(users), n_item, 'target')
+    if excl is not None:
+        e_off_h, e_items_h = _check_rows(*(t.detach().cpu().numpy() if torch.is_tensor(t) else t for t in excl), len(users), n_item, 'exclusion')
+    n, n_t = len(users), len(t_items)
+    ranks = torch.empty(max(n_t, 1), dtype=torch.int32, device=dev)
+    if n_t == 0:
+        return ranks[:0]
+    uid = to_device_async(users.astype(np.int32), dev)
+    d_off, d_items = to_device_async(t_off, dev), to_device_async(t_items, dev)
+    e_off = e_items = None
+    if excl is not None:
+        e_off = to_device_async(e_off_h, dev)
+        e_items = to_device_async(e_items_h if e_items_h.size else np.zeros(1, dtype=np.int32), dev)
+    L = nv.lib()
+    nbytes = int(L.ure_nmf_rank_pairs_scratch(n, n_t, n_item, len(models), S.k, nv.ptr(lay), len(lay)))
+    if nbytes < 0:
+        raise ValueError(f'ure_nmf_rank_pairs_scratch refused n_query = {n}, n_targets = {n_t}, n_item = {n_item}, k = {S.k}, layers = {S.layers}')
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _csr_held_for(stream, *(t for t in (ranks, uid, d_off, d_items, e_off, e_items, scratch) if t is not None))
+    nv.check(L.ure_nmf_rank_pairs(Up, Vp, Dp, len(models), S.k, nv.ptr(lay), len(lay), n_user, nv.ptr(uid), n, n_item, nv.ptr(d_off),
+                                  nv.ptr(d_items), nv.ptr(e_off), nv.ptr(e_items), nv.ptr(ranks), nv.ptr(scratch), nbytes,
+                                  nv.stream_handle(stream)), 'ure_nmf_rank_pairs')
+    return ranks
+
+
 class NmfJob:
     """One shard trained with the NeuMF backbone (nmf.train_ref in float32, bit for bit): per step the forward / backward pass over
     the shard's entries (the batch's write their slot), the weight-gradient sums over the slots, the two masked row sums of the

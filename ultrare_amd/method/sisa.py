@@ -668,16 +668,27 @@ class Sisa(Scratch):
     # ------------------------------------------------------------------ unlearn
     def recommend(self, users, top_k=10, exclude=None):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers
-        from the retrained shards.  Every rank of a parallel run holds the merged models and answers its own queries."""
+        from the retrained shards.  Every rank of a parallel run holds the merged models and answers its own queries.
+        The 'nmf' backbone is answered by recommend_nmf."""
         self._refuse_nmf('recommend')
         return recommend(self.model_list, users, top_k, exclude)
+
+    def recommend_nmf(self, users, top_k=10, exclude=None):
+        """recommend for the 'nmf' backbone (utils.recommend_nmf over self.model_list): the same return values and padding, the
+        scores those baseTest gives a NeuMF ensemble; after unlearn it answers from the retrained shards."""
+        return utils.recommend_nmf(self.model_list, users, top_k, exclude)
 
     def rank_eval(self, test_data, exclude=None, ks=(10, 20)):
         """Full-ranking HR@K / Recall@K / NDCG@K / MRR of the current ensemble on a test loader (utils.rank_eval over
         self.model_list): after unlearn it evaluates the retrained shards.  Every rank of a parallel run holds the merged models
-        and answers for itself."""
+        and answers for itself.  The 'nmf' backbone is evaluated by rank_eval_nmf."""
         self._refuse_nmf('rank_eval')
         return rank_eval(self.model_list, test_data, exclude, ks)
+
+    def rank_eval_nmf(self, test_data, exclude=None, ks=(10, 20)):
+        """rank_eval for the 'nmf' backbone (utils.rank_eval_nmf over self.model_list): the same metrics over the whole catalogue;
+        after unlearn it evaluates the retrained shards."""
+        return utils.rank_eval_nmf(self.model_list, test_data, exclude, ks)
 
     def unlearn(self, model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir):
         '''

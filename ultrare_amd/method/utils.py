@@ -384,7 +384,8 @@ def recommend(models, users, top_k=10, exclude=None):
     """The top_k items of each user in `users` over the whole catalogue, by the score baseTest gives the pair (the mean of
     `models`, bit for bit), ties by ascending item id.  exclude: a scipy CSR with user ids as rows (read.readSparseMat of the
     training set) whose items are never returned.  Returns (scores [n, top_k], items [n, top_k] int64) on the device; a user
-    with fewer eligible items than top_k gets (NaN, -1) at the end.  The full model is recommend([model], ...)."""
+    with fewer eligible items than top_k gets (NaN, -1) at the end.  The full model is recommend([model], ...).
+    NeuMF models are answered by recommend_nmf."""
     refuse_nmf(models, 'recommend')
     tabs = [padded_tables(m) for m in models]
     users = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
@@ -447,12 +448,50 @@ def rank_eval(models, test_data, exclude=None, ks=(10, 20)):
     -- exclude: a scipy CSR with user ids as rows, read.readSparseMat of the training set -- by (score, id) as recommend orders
     them, and HR@K, Recall@K, NDCG@K and MRR are taken from those ranks (rank_metrics; every test pair is relevant, no rating
     threshold).  These are NOT baseTest's HR@10 / NDCG@10, which rank a user's test items only against each other.  A test pair
-    that is also in `exclude` does not count.  Returns the dict of rank_metrics."""
+    that is also in `exclude` does not count.  Returns the dict of rank_metrics.  NeuMF models are evaluated by rank_eval_nmf."""
     refuse_nmf(models, 'rank_eval')
     tabs = [padded_tables(m) for m in models]
     users, off, items = relevant_pairs(test_data, int(tabs[0][1].shape[0]))
     excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
     ranks = engine.rank_pairs([(U, V) for U, V, _ in tabs], tabs[0][2], users, (off, items), excl)
+    return rank_metrics(off, ranks, ks)
+
+
+def _nmf_ensemble(models, who):
+    """[(U, V, dense)], k, layers of a list of NMF models of ONE stack, or ValueError."""
+    models = list(models) if isinstance(models, (list, tuple)) else [models]
+    if not models:
+        raise ValueError(f'{who} needs at least one model')
+    for m in models:
+        if not isinstance(m, NMF):
+            raise ValueError(f"{who} takes models of the 'nmf' backbone only, not {type(m).__name__} (recommend / rank_eval serve 'mf' and 'lightgcn')")
+    k, layers = models[0].k, list(models[0].layers)
+    for m in models:
+        if (m.k, list(m.layers)) != (k, layers):
+            raise ValueError(f'{who}: the models of an ensemble share one stack, not k = {k}, layers = {layers} and k = {m.k}, layers = {list(m.layers)}')
+    tabs = [m.tables() for m in models]
+    if not all(t.is_cuda for tab in tabs for t in tab):
+        raise nv.NativeError('model tables are not on the HIP device (call model.to("cuda")): no CPU fallback')
+    return tabs, k, layers
+
+
+def recommend_nmf(models, users, top_k=10, exclude=None):
+    """recommend for NeuMF models (a list of NMF of one stack): the top_k items of each user over the whole catalogue by the score
+    baseTest gives the pair (the ensemble mean of the models' forwards, bit for bit), ties by ascending item id; exclude and the
+    return values as recommend's."""
+    tabs, k, layers = _nmf_ensemble(models, 'recommend_nmf')
+    users = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
+    excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
+    return engine.nmf_recommend(tabs, k, layers, users, top_k, excl)
+
+
+def rank_eval_nmf(models, test_data, exclude=None, ks=(10, 20)):
+    """rank_eval for NeuMF models (a list of NMF of one stack): every distinct (user, item) pair of `test_data` ranked among all
+    items the user has not trained on, by (score, id) as recommend_nmf orders them.  Returns the dict of rank_metrics."""
+    tabs, k, layers = _nmf_ensemble(models, 'rank_eval_nmf')
+    users, off, items = relevant_pairs(test_data, int(tabs[0][1].shape[0]))
+    excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
+    ranks = engine.nmf_rank_pairs(tabs, k, layers, users, (off, items), excl)
     return rank_metrics(off, ranks, ks)
 
 

@@ -315,3 +315,148 @@ def train_ref(uid, iid, rating, U0, V0, dense0, orders, batch, lr_host, lam, mu,
     out = {name: np.stack(v) for name, v in out.items()}
     out['sse'], out['loss'] = sse, np.sqrt(sse / max(N, 1))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Catalogue sweeps (csrc/nmf_rank.hip, include/ultrare_nmf_rank.h): top-k and exact ranks under an ensemble.
+# ---------------------------------------------------------------------------------------------------------------------
+RANK_LDS_BYTES = 163840         # URE_NMF_RANK_LDS_BYTES: what a workgroup of the tile kernels may hold
+RANK_PLANTS = ('fma', 'item_first')
+
+
+def prefix_ref(U, dense, k, layers, uid, dtype=np.float32):
+    """-> [n, L1]: the layer-0 chains of forward_ref stopped after the user half -- output o's chain over a_0 = [pm ; qm] in
+    ascending i from +0.0, its first e terms.  They depend on (model, user, o) alone; the tile kernel sums them once per user."""
+    T = dtype
+    S = Shape(k, layers)
+    W = S.unpack(np.asarray(dense, dtype=T))[0]
+    pm = np.asarray(U, dtype=T)[uid][:, S.k:]
+    t = np.zeros((len(pm), S.layers[1]), dtype=T)
+    for i in range(S.e):
+        t = t + W[0][:, i][None, :] * pm[:, i][:, None]
+    return t
+
+
+def forward_from_prefix_ref(prefix, V, dense, k, layers, U, uid, iid, dtype=np.float32, plant=None, want_a1=False):
+    """-> pred [n] (want_a1: (pred, a_1 [n, L1])): forward_ref's prediction with the layer-0 chains of pair j continued from prefix[j] (prefix_ref at uid) over
+    qm, then the rest of the stack, the GMF products and the head.  The same float32 operations in the same order as forward_ref,
+    hence the same bytes.
+    plant (tests only), one of RANK_PLANTS: every chain's terms as fused multiply-adds; the item half summed from +0.0 on its
+    own and added to the prefix."""
+    assert plant is None or plant in RANK_PLANTS
+    T = dtype
+    S = Shape(k, layers)
+    W, b, h, c = S.unpack(np.asarray(dense, dtype=T))
+    u, v = np.asarray(U, dtype=T)[uid], np.asarray(V, dtype=T)[iid]
+    n, e = len(v), S.e
+    def mad(t, w, x):                                       # one term of a chain: fl(t + fl(w * x)); the plant: fmaf(w, x, t)
+        if plant != 'fma':
+            return t + w * x
+        w, x = np.broadcast_arrays(np.asarray(w, dtype=T), np.asarray(x, dtype=T))
+        return lightgcn._fma32(*np.broadcast_arrays(w, x, t)).astype(T)
+    t = np.array(prefix, dtype=T)
+    if plant == 'item_first':
+        t = np.zeros_like(t)
+    for i in range(e):
+        t = mad(t, W[0][:, e + i][None, :], v[:, k + i][:, None])
+    if plant == 'item_first':
+        t = np.asarray(prefix, dtype=T) + t
+    z = t + b[0][None, :]
+    a = a1 = np.where(z <= 0, T(0), z)
+    for j in range(1, S.m):
+        t = np.zeros((n, S.layers[j + 1]), dtype=T)
+        for i in range(S.layers[j]):
+            t = mad(t, W[j][:, i][None, :], a[:, i][:, None])
+        z = t + b[j][None, :]
+        a = np.where(z <= 0, T(0), z)
+    g = u[:, :k] * v[:, :k]
+    t = np.zeros(n, dtype=T)
+    for col in range(k):
+        t = mad(t, h[col], g[:, col])
+    for col in range(S.layers[-1]):
+        t = mad(t, h[k + col], a[:, col])
+    return (t + c, a1) if want_a1 else t + c
+
+
+def order_bits(s):
+    """rec_score.h's order_bits of float32 scores as uint32: larger for the better score; NaN below -inf, -0.0 == +0.0."""
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    b = s.view(np.uint32).copy()
+    b[(b << np.uint32(1)) == 0] = 0
+    neg = (b & np.uint32(0x80000000)) != 0
+    out = np.where(neg, ~b, b | np.uint32(0x80000000))
+    out[np.isnan(s)] = 0
+    return out.astype(np.uint32)
+
+
+def rank_keys(s, items):
+    """rec_key: (order_bits(score) << 32) | ~item as uint64 -- larger for the better item, unique per item."""
+    return (order_bits(s).astype(np.uint64) << np.uint64(32)) | (~np.asarray(items).astype(np.uint32)).astype(np.uint64)
+
+
+def _excl_row(excl, q):
+    return np.zeros(0, dtype=np.int64) if excl is None else np.asarray(excl[1])[excl[0][q]:excl[0][q + 1]].astype(np.int64)
+
+
+def catalogue_scores_ref(models, k, layers, users, n_item):
+    """-> [n, n_item] float32: score_ref of every (user, item) pair."""
+    users = np.asarray(users, dtype=np.int64)
+    items = np.arange(n_item, dtype=np.int64)
+    return np.stack([score_ref(models, k, layers, np.full(n_item, u, dtype=np.int64), items) for u in users]).astype(np.float32)
+
+
+def recommend_ref(models, k, layers, users, n_item, top_k, excl=None, scores=None):
+    """ure_nmf_recommend_topk: -> (scores [n, top_k] float32, items [n, top_k] int64): per query row the top_k non-excluded items
+    under score_ref's ensemble mean, in key order (score descending, NaN below -inf, -0.0 == +0.0, then item id ascending);
+    padding is (NaN, -1).  excl = (off [n + 1], items) or None.  scores: catalogue_scores_ref's matrix when the caller has it."""
+    sc = catalogue_scores_ref(models, k, layers, users, n_item) if scores is None else np.asarray(scores, dtype=np.float32)
+    n = len(sc)
+    out_s, out_i = np.full((n, top_k), np.nan, dtype=np.float32), np.full((n, top_k), -1, dtype=np.int64)
+    for q in range(n):
+        keep = np.ones(n_item, dtype=bool)
+        keep[_excl_row(excl, q)] = False
+        ids = np.flatnonzero(keep)
+        best = ids[np.argsort(rank_keys(sc[q, ids], ids))[::-1][:top_k]]
+        out_s[q, :len(best)], out_i[q, :len(best)] = sc[q, best], best
+    return out_s, out_i
+
+
+def rank_ref(models, k, layers, users, targets, excl=None, scores=None, n_item=None):
+    """ure_nmf_rank_pairs: -> ranks int32 [n_targets] in input order: for target t of query row q the number of non-excluded items
+    whose key beats t's, -1 when t is excluded.  targets = (off [n + 1], items): any order, duplicates, empty rows."""
+    n_item = len(models[0][1]) if n_item is None else n_item
+    sc = catalogue_scores_ref(models, k, layers, users, n_item) if scores is None else np.asarray(scores, dtype=np.float32)
+    t_off, t_items = np.asarray(targets[0], dtype=np.int64), np.asarray(targets[1], dtype=np.int64)
+    ranks = np.zeros(len(t_items), dtype=np.int32)
+    for q in range(len(sc)):
+        keep = np.ones(n_item, dtype=bool)
+        keep[_excl_row(excl, q)] = False
+        keys = rank_keys(sc[q], np.arange(n_item))
+        live = np.sort(keys[keep])
+        for j in range(t_off[q], t_off[q + 1]):
+            t = t_items[j]
+            ranks[j] = len(live) - np.searchsorted(live, keys[t], side='right') if keep[t] else -1
+    return ranks
+
+
+def rank_lds_bytes(k, layers, QW, pshift, top_k=None):
+    """The LDS of a workgroup of the tile kernels at (QW, pshift) (include/ultrare_nmf_rank.h): the scorer's bytes plus the
+    selection state (top_k given) or the counting state."""
+    S = Shape(k, layers)
+    L = S.layers
+    w = sum(L[j] * (L[j + 1] + 1) + L[j + 1] for j in range(S.m)) + k + L[-1] + 1
+    wa = max(L[1], L[3] if S.m >= 4 else 0) if S.m >= 2 else 0
+    wb = L[2] if S.m >= 3 else 0
+    tile = -(-4 * (w + 65 * S.e + 4 * QW * (k + L[1] + (wa + wb) * (64 >> pshift))) // 16) * 16
+    return tile + (4 * QW * (12 * (top_k + 64) + 272) if top_k is not None else 49152 + 48 * QW)
+
+
+def rank_plan(k, layers, top_k=None):
+    """-> (QW, pshift) the entries run the stack at: the first of the header's list that fits RANK_LDS_BYTES, or None."""
+    m = len(layers) - 1
+    for QW, p in ((4, 0), (2, 0), (1, 0), (1, 1), (1, 2), (1, 3)):
+        if rank_lds_bytes(k, layers, QW, p, top_k) <= RANK_LDS_BYTES:
+            return QW, p
+        if m == 1:
+            break
+    return None

@@ -55,6 +55,10 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.nmf_score(U, V, dense, k, layers, uid, iid)
                                                         (new)             the NeuMF forward of one model (ultrare_amd/nmf.py: U, V
                                                                           [rows, k + layers[0] / 2], dense the layers and the head)
+    torch.ops.ultrare.nmf_recommend_topk(Us, Vs, denses, k, layers, users, excl_off, excl_items, top_k)
+                                                        (new)             recommend_topk under a NeuMF ensemble of one stack
+    torch.ops.ultrare.nmf_rank_pairs(Us, Vs, denses, k, layers, users, tgt_off, tgt_items, excl_off, excl_items)
+                                                        (new)             rank_pairs under a NeuMF ensemble of one stack
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -464,3 +468,38 @@ def nmf_score(U: torch.Tensor, V: torch.Tensor, dense: torch.Tensor, k: int, lay
 @nmf_score.register_fake
 def _(U, V, dense, k, layers, uid, iid):
     return U.new_empty(uid.numel())
+
+
+@torch.library.custom_op('ultrare::nmf_recommend_topk', mutates_args=())
+def nmf_recommend_topk(Us: List[torch.Tensor], Vs: List[torch.Tensor], denses: List[torch.Tensor], k: int, layers: List[int], users: torch.Tensor,
+                       excl_off: Optional[torch.Tensor], excl_items: Optional[torch.Tensor], top_k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """engine.nmf_recommend of the ensemble [(Us[m], Vs[m], denses[m])] of one (k, layers): (scores [n, top_k], items [n, top_k] int64)."""
+    from . import nmf
+    nmf.check_layers(k, list(layers))                        # (a bad stack is a ValueError before anything else)
+    _dev(*Us, *Vs, *denses, users, *[t for t in (excl_off, excl_items) if t is not None])
+    assert len(Us) == len(Vs) == len(denses) and (excl_off is None) == (excl_items is None)
+    excl = None if excl_off is None else (excl_off.cpu().numpy(), excl_items.cpu().numpy())
+    return engine.nmf_recommend([(U.contiguous(), V.contiguous(), d.contiguous()) for U, V, d in zip(Us, Vs, denses)], k, list(layers), users, top_k, excl)
+
+
+@nmf_recommend_topk.register_fake
+def _(Us, Vs, denses, k, layers, users, excl_off, excl_items, top_k):
+    return Us[0].new_empty(users.numel(), top_k), Us[0].new_empty(users.numel(), top_k, dtype=torch.int64)
+
+
+@torch.library.custom_op('ultrare::nmf_rank_pairs', mutates_args=())
+def nmf_rank_pairs(Us: List[torch.Tensor], Vs: List[torch.Tensor], denses: List[torch.Tensor], k: int, layers: List[int], users: torch.Tensor,
+                   tgt_off: torch.Tensor, tgt_items: torch.Tensor, excl_off: Optional[torch.Tensor], excl_items: Optional[torch.Tensor]) -> torch.Tensor:
+    """engine.nmf_rank_pairs of the ensemble [(Us[m], Vs[m], denses[m])] of one (k, layers): ranks int32 [len(tgt_items)]."""
+    from . import nmf
+    nmf.check_layers(k, list(layers))
+    _dev(*Us, *Vs, *denses, users, tgt_off, tgt_items, *[t for t in (excl_off, excl_items) if t is not None])
+    assert len(Us) == len(Vs) == len(denses) and (excl_off is None) == (excl_items is None)
+    excl = None if excl_off is None else (excl_off.cpu().numpy(), excl_items.cpu().numpy())
+    return engine.nmf_rank_pairs([(U.contiguous(), V.contiguous(), d.contiguous()) for U, V, d in zip(Us, Vs, denses)], k, list(layers), users,
+                                 (tgt_off.cpu().numpy(), tgt_items.cpu().numpy()), excl)
+
+
+@nmf_rank_pairs.register_fake
+def _(Us, Vs, denses, k, layers, users, tgt_off, tgt_items, excl_off, excl_items):
+    return Us[0].new_empty(tgt_items.numel(), dtype=torch.int32)
