@@ -2,8 +2,9 @@
 // per-epoch negative draw and the index of the entries by their negative item, and per step the coefficient pass and the two
 // gradient walks that stand where gcn.hip's residual pass and masked walks stand in an MSE step.
 //
-// The walks keep gcn.hip's shape: a group of G = d / 4 lanes owns an output row, the chain of a (row, column) is one lane's, in
-// ascending entry position, never split; every float operation is a rounded one of its own (gcn_ops.h).  The index is a stable
+// The walks are row_walk.h's: a group of G = d / 4 lanes owns an output row, the chain of a (row, column) is one lane's, in
+// ascending entry position, never split; theirs is what a fetch reads (the negative beside the item, the loss term of the entry's
+// own x) and what a term adds.  Every float operation is a rounded one of its own (gcn_ops.h).  The index is a stable
 // LSD radix sort of (negative item, CSR position) with 8-bit digits: per pass a histogram of every tile of kSortTile entries, one
 // scan of the (digit, tile) counts and a scatter that ranks a tile's entries in order.  Integer atomics only in the histograms.
 #include "gcn_ops.h"
@@ -207,50 +208,47 @@ __global__ __launch_bounds__(kBlock) void bpr_coef_kernel(const int32_t *__restr
     }
 }
 
-// G_u[r] = sum over user r's entries in the batch of w (V[item] - V[negative]): gcn_grad_kernel's walk, the negative fetched beside
-// the item.  Lane `sub` also turns its own entry's x into the loss term, so a tile's terms cost one evaluation; the row's float64
-// chain receives them in entry order in every lane (lane 0 stores it).
+// G_u[r] = sum over user r's entries in the batch of w (V[item] - V[negative]), the negative fetched beside the item.  The fetch
+// also turns its own entry's x into the loss term, so a tile's terms cost one evaluation each; the row's float64 chain receives
+// them in entry order in every lane (lane 0 stores it).
 template <int G>
 __global__ __launch_bounds__(kBlock) void bpr_grad_user_kernel(const int64_t *__restrict__ off, const int32_t *__restrict__ col, const int32_t *__restrict__ neg,
                                                                const int32_t *__restrict__ tag, const float *__restrict__ w, const float *__restrict__ x,
                                                                int64_t n_user, int64_t n_item, int step, const float *__restrict__ V,
                                                                float *__restrict__ Gout, double *__restrict__ row_loss)
 {
-    constexpr int kRows = kBlock / G, D = 4 * G;
-    const int sub = threadIdx.x % G;
-    const int64_t r = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    if (r >= n_user) return;                               // whole groups leave together
-    const int64_t b = ldg(off + r), e = ldg(off + r + 1);
+    constexpr int D = 4 * G;
+    const RowLanes<G> L;
+    if (L.past(n_user)) return;
     const unsigned last = (unsigned)(n_item - 1);
-    const float *__restrict__ v = V + 4 * sub;
+    const float *__restrict__ v = V + 4 * L.sub;
     float4 g = f4_zero();
     double loss = 0.0;
-    for (int64_t p0 = b; p0 < e; p0 += G) {
-        const int64_t k = p0 + sub;
-        unsigned mine_j = 0u, mine_n = 0u;
-        float mine_w = 0.f;
-        double mine_t = 0.0;
-        bool mine_in = false;
-        if (k < e) {
-            mine_in = ldg(tag + k) == step;
-            if (mine_in) {
-                mine_w = ldg(w + k);
-                mine_t = bpr_loss_term(ldg(x + k));
-                mine_j = min((unsigned)ldg(col + k), last);
-                mine_n = min((unsigned)ldg(neg + k), last);
+    struct Entry { unsigned j, n; float w; double t; bool in; };
+    tile_walk<G>(
+        ldg(off + L.r), ldg(off + L.r + 1), L.sub,
+        [&](int64_t k, bool inside) {
+            Entry mine{0u, 0u, 0.f, 0.0, false};
+            if (inside) {
+                mine.in = ldg(tag + k) == step;
+                if (mine.in) {
+                    mine.w = ldg(w + k);
+                    mine.t = bpr_loss_term(ldg(x + k));
+                    mine.j = min((unsigned)ldg(col + k), last);
+                    mine.n = min((unsigned)ldg(neg + k), last);
+                }
             }
-        }
-        const int m = (int)min<int64_t>(G, e - p0);
-        for (int u = 0; u < m; ++u) {
-            if (!group_read<G>((int)mine_in, u)) continue;          // uniform across the group
-            const unsigned j = group_read<G>(mine_j, u), n = group_read<G>(mine_n, u);
-            const float ww = group_read<G>(mine_w, u);
+            return mine;
+        },
+        [&](const Entry &mine, int u) {
+            if (!group_read<G>((int)mine.in, u)) return;
+            const unsigned j = group_read<G>(mine.j, u), n = group_read<G>(mine.n, u);
+            const float ww = group_read<G>(mine.w, u);
             g = f4_add(g, f4_scale(ww, f4_sub(ldg_f4(v + (size_t)j * D), ldg_f4(v + (size_t)n * D))));
-            loss += group_read<G>(mine_t, u);
-        }
-    }
-    stg_f4(Gout + (size_t)r * D + 4 * sub, g);
-    if (row_loss && sub == 0) stg(row_loss + r, loss);
+            loss += group_read<G>(mine.t, u);
+        });
+    stg_f4(Gout + (size_t)L.r * D + 4 * L.sub, g);
+    if (row_loss && L.sub == 0) stg(row_loss + L.r, loss);
 }
 
 // One part of an item's chain: the entries [b, e) of `idx` (their users) and `map` (their CSR positions), those of the batch
@@ -260,27 +258,26 @@ __device__ __forceinline__ float4 bpr_item_part(float4 g, int64_t b, int64_t e, 
                                                 const int32_t *__restrict__ tag, const float *__restrict__ w, unsigned last_user, unsigned last_pos,
                                                 int step, const float *__restrict__ x)
 {
-    constexpr int D = 4 * G;
-    for (int64_t p0 = b; p0 < e; p0 += G) {
-        const int64_t k = p0 + sub;
-        unsigned mine_j = 0u;
-        float mine_w = 0.f;
-        bool mine_in = false;
-        if (k < e) {
-            const unsigned q = min((unsigned)ldg(map + k), last_pos);
-            mine_in = ldg(tag + q) == step;
-            if (mine_in) {
-                mine_w = NEGATE ? -ldg(w + q) : ldg(w + q);
-                mine_j = min((unsigned)ldg(idx + k), last_user);
+    struct Entry { unsigned j; float w; bool in; };
+    tile_walk<G>(
+        b, e, sub,
+        [&](int64_t k, bool inside) {
+            Entry mine{0u, 0.f, false};
+            if (inside) {
+                const unsigned q = entry_pos<true>(map, k, last_pos);
+                mine.in = ldg(tag + q) == step;
+                if (mine.in) {
+                    mine.w = NEGATE ? -ldg(w + q) : ldg(w + q);
+                    mine.j = min((unsigned)ldg(idx + k), last_user);
+                }
             }
-        }
-        const int m = (int)min<int64_t>(G, e - p0);
-        for (int u = 0; u < m; ++u) {
-            if (!group_read<G>((int)mine_in, u)) continue;          // uniform across the group
-            const unsigned j = group_read<G>(mine_j, u);
-            g = f4_mul_add(g, group_read<G>(mine_w, u), ldg_f4(x + (size_t)j * D));
-        }
-    }
+            return mine;
+        },
+        [&](const Entry &mine, int u) {
+            if (!group_read<G>((int)mine.in, u)) return;
+            const unsigned j = group_read<G>(mine.j, u);
+            g = f4_mul_add(g, group_read<G>(mine.w, u), ldg_f4(x + (size_t)j * (4 * G)));
+        });
     return g;
 }
 
@@ -292,17 +289,15 @@ __global__ __launch_bounds__(kBlock) void bpr_grad_item_kernel(const int64_t *__
                                                                const float *__restrict__ w, int64_t n_item, int64_t n_user, int64_t nnz, int step,
                                                                const float *__restrict__ U, float *__restrict__ Gout)
 {
-    constexpr int kRows = kBlock / G, D = 4 * G;
-    const int sub = threadIdx.x % G;
-    const int64_t r = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    if (r >= n_item) return;                               // whole groups leave together
+    const RowLanes<G> L;
+    if (L.past(n_item)) return;
     const unsigned last_user = (unsigned)(n_user - 1), last_pos = (unsigned)(nnz - 1);
-    const float *__restrict__ x = U + 4 * sub;
+    const float *__restrict__ x = U + 4 * L.sub;
     // (offsets are read as they are in gcn.hip; the negative index's are clamped to its arrays, which this library made)
-    float4 g = bpr_item_part<G, false>(f4_zero(), ldg(off_i + r), ldg(off_i + r + 1), sub, row, to_csr, tag, w, last_user, last_pos, step, x);
-    const int64_t nb = min(max(ldg(off_n + r), (int64_t)0), nnz), ne = min(max(ldg(off_n + r + 1), nb), nnz);
-    g = bpr_item_part<G, true>(g, nb, ne, sub, usr_n, map_n, tag, w, last_user, last_pos, step, x);
-    stg_f4(Gout + (size_t)r * D + 4 * sub, g);
+    float4 g = bpr_item_part<G, false>(f4_zero(), ldg(off_i + L.r), ldg(off_i + L.r + 1), L.sub, row, to_csr, tag, w, last_user, last_pos, step, x);
+    const int64_t nb = min(max(ldg(off_n + L.r), (int64_t)0), nnz), ne = min(max(ldg(off_n + L.r + 1), nb), nnz);
+    g = bpr_item_part<G, true>(g, nb, ne, L.sub, usr_n, map_n, tag, w, last_user, last_pos, step, x);
+    stg_f4(Gout + (size_t)L.r * (4 * G) + 4 * L.sub, g);
 }
 
 inline int64_t align256(int64_t bytes) { return (bytes + 255) / 256 * 256; }

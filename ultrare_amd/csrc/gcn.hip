@@ -4,7 +4,9 @@
 // One shape serves the propagate and the two gradient walks: a group of G = d / 4 lanes owns an output row and holds its d
 // columns as one float4 per lane (1 lane at d = 4, a whole wavefront at d = 256); the row's entries are fetched a tile of G at
 // a time, one per lane, and handed round with group_read (csr_lanes.h); the chain of a (row, column) is one lane's, in
-// ascending entry position.  Every float operation is a rounded one of its own (gcn_ops.h).
+// ascending entry position.  Every float operation is a rounded one of its own (gcn_ops.h).  The gradient walk's loop, its row
+// ownership and its order are row_walk.h's; gcn_grad_kernel states what a fetch reads and what a term adds.  The propagate keeps
+// a loop of its own (the next tile's entries travel while this one is added, four rows in flight).
 #include "gcn_ops.h"
 
 namespace ure {
@@ -90,48 +92,46 @@ __global__ __launch_bounds__(kBlock) void gcn_propagate_kernel(const int64_t *__
     if (sum) stg_f4(sum + at, f4_add(ldg_f4(sum + at), y));
 }
 
-// G[r] = sum over row r's entries in the batch of (2 err) T[idx].  Lane `sub` fetches entry p0 + sub, its CSR position (through
-// map on the CSC side), that position's tag and -- for an entry of the batch -- its residual; the group then goes through the
-// tile and only an entry of the batch costs a row of T.  The row's float64 loss chain rides along in every lane (lane 0 stores it).
+// G[r] = sum over row r's entries in the batch of (2 err) T[idx].  A fetch reads the entry's tag and -- for an entry of the
+// batch -- its residual and its index, so only an entry of the batch costs a row of T.  The row's float64 loss chain rides along
+// in every lane (lane 0 stores it).
 template <int G, bool MAPPED>
 __global__ __launch_bounds__(kBlock) void gcn_grad_kernel(const int64_t *__restrict__ off, const int32_t *__restrict__ idx, const int32_t *__restrict__ map,
                                                           const int32_t *__restrict__ tag, const float *__restrict__ err, int64_t n_dst, int64_t n_src,
                                                           int64_t nnz, int step, const float *__restrict__ T, float *__restrict__ Gout,
                                                           double *__restrict__ row_loss)
 {
-    constexpr int kRows = kBlock / G, D = 4 * G;
-    const int sub = threadIdx.x % G;
-    const int64_t r = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    if (r >= n_dst) return;
-    const int64_t b = ldg(off + r), e = ldg(off + r + 1);
+    constexpr int D = 4 * G;
+    const RowLanes<G> L;
+    if (L.past(n_dst)) return;
     const unsigned last = (unsigned)(n_src - 1), last_pos = (unsigned)(nnz - 1);
-    const float *__restrict__ x = T + 4 * sub;
+    const float *__restrict__ x = T + 4 * L.sub;
     float4 g = f4_zero();
     double loss = 0.0;
-    for (int64_t p0 = b; p0 < e; p0 += G) {
-        const int64_t k = p0 + sub;
-        unsigned mine_j = 0u;
-        float mine_e = 0.f;
-        bool mine_in = false;
-        if (k < e) {
-            const unsigned q = MAPPED ? min((unsigned)ldg(map + k), last_pos) : (unsigned)k;
-            mine_in = ldg(tag + q) == step;
-            if (mine_in) {
-                mine_e = ldg(err + q);
-                mine_j = min((unsigned)ldg(idx + k), last);
+    struct Entry { unsigned j; float e; bool in; };
+    tile_walk<G>(
+        ldg(off + L.r), ldg(off + L.r + 1), L.sub,
+        [&](int64_t k, bool inside) {
+            Entry mine{0u, 0.f, false};
+            if (inside) {
+                const unsigned q = entry_pos<MAPPED>(map, k, last_pos);
+                mine.in = ldg(tag + q) == step;
+                if (mine.in) {
+                    mine.e = ldg(err + q);
+                    mine.j = min((unsigned)ldg(idx + k), last);
+                }
             }
-        }
-        const int m = (int)min<int64_t>(G, e - p0);
-        for (int u = 0; u < m; ++u) {
-            if (!group_read<G>((int)mine_in, u)) continue;          // uniform across the group
-            const unsigned j = group_read<G>(mine_j, u);
-            const float ee = group_read<G>(mine_e, u);
+            return mine;
+        },
+        [&](const Entry &mine, int u) {
+            if (!group_read<G>((int)mine.in, u)) return;
+            const unsigned j = group_read<G>(mine.j, u);
+            const float ee = group_read<G>(mine.e, u);
             g = f4_mul_add(g, __fmul_rn(2.f, ee), ldg_f4(x + (size_t)j * D));
             loss += (double)ee * (double)ee;
-        }
-    }
-    stg_f4(Gout + (size_t)r * D + 4 * sub, g);
-    if (row_loss && sub == 0) stg(row_loss + r, loss);
+        });
+    stg_f4(Gout + (size_t)L.r * D + 4 * L.sub, g);
+    if (row_loss && L.sub == 0) stg(row_loss + L.r, loss);
 }
 
 // The residual pass: a group of LPR = d / 4 lanes per CSR entry, the dot of score_dot.h.  Every lane of a wave takes part in
@@ -203,13 +203,8 @@ __global__ __launch_bounds__(256) void gcn_step_loss_kernel(const double *__rest
     __shared__ double part[256];
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) acc += ldg(row_loss + i);
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (first ? 0.0 : loss[0]) + part[0];
+    const double s = fold_256(acc, part);
+    if (threadIdx.x == 0) loss[0] = (first ? 0.0 : loss[0]) + s;
 }
 
 }  // namespace
@@ -280,13 +275,8 @@ extern "C" int ure_gcn_grad(const int64_t *off, const int32_t *idx, const int32_
     hipStream_t st = (hipStream_t)stream;
     dispatch_group_width(d / 4, [&](auto w) {
         constexpr int G = decltype(w)::value;
-        const dim3 grid(group_blocks(n_dst, G));
-        if (map)
-            hipLaunchKernelGGL((gcn_grad_kernel<G, true>), grid, dim3(kBlock), 0, st, off, idx, map, tag, err, n_dst, n_src, nnz, (int)step, T, G_out,
-                               row_loss);
-        else
-            hipLaunchKernelGGL((gcn_grad_kernel<G, false>), grid, dim3(kBlock), 0, st, off, idx, map, tag, err, n_dst, n_src, nnz, (int)step, T, G_out,
-                               row_loss);
+        launch_by_map(map, gcn_grad_kernel<G, true>, gcn_grad_kernel<G, false>, n_dst, G, st, off, idx, map, tag, err, n_dst, n_src, nnz, (int)step, T,
+                      G_out, row_loss);
     });
     URE_HIP(hipGetLastError());
     return 0;

@@ -1,8 +1,9 @@
-// gcn_ops.h -- what the kernels over a shard's graph share (gcn.hip, bpr.hip): the float4 operations of a lane's four columns,
-// every one a rounded float32 operation of its own (__fmul_rn / __fadd_rn: never contracted), and the host-side checks and grid
-// sizes of their entries.  The lane-group coordinates and the dot are csr_lanes.h's and score_dot.h's.
+// gcn_ops.h -- what the kernels over a shard's graph share (gcn.hip, bpr.hip, nmf.hip, influence.hip): the float4 operations of a
+// lane's four columns, every one a rounded float32 operation of its own (__fmul_rn / __fadd_rn: never contracted), the fold of
+// 256 float64 lane sums, and the host-side checks and grid sizes of their entries.  The masked row walk is row_walk.h's, the
+// lane-group coordinates and the dot are csr_lanes.h's and score_dot.h's.
 #pragma once
-#include "csr_lanes.h"
+#include "row_walk.h"
 #include "score_dot.h"
 
 namespace ure {
@@ -28,6 +29,19 @@ __device__ __forceinline__ float4 f4_add(float4 a, float4 b)
 __device__ __forceinline__ float4 f4_sub(float4 a, float4 b)
 {
     return make_float4(__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z), __fsub_rn(a.w, b.w));
+}
+
+// The sums of the 256 threads of a workgroup -> one value, in epoch_sse_kernel's order (job_io.hip): thread t += thread t + w for
+// w = 128, 64 .. 1.  Every thread calls it with the workgroup's part[256] of LDS and receives the sum.
+__device__ __forceinline__ double fold_256(double acc, double *part)
+{
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] = __dadd_rn(part[threadIdx.x], part[threadIdx.x + w]);
+        __syncthreads();
+    }
+    return part[0];
 }
 
 inline unsigned stream_blocks(int64_t items)

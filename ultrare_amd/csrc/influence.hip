@@ -2,10 +2,10 @@
 // ultrare_amd/influence.py): the coefficient pass, the Hessian-vector / gradient walk over a shard's CSR / CSC, the fixed-order
 // dot and the conjugate-gradient vector operations, whose scalars never leave the device.
 //
-// The walk has gcn_grad_kernel's shape: a group of G = d / 4 lanes owns an output row and holds its d columns as four float64
-// accumulators per lane; the row's entries are fetched a tile of G at a time, one per lane, and handed round with group_read
-// (csr_lanes.h); the chain of a (row, column) is one lane's, in ascending entry position.  Every operation is a rounded float64
-// operation of its own (__dmul_rn / __dadd_rn and -ffp-contract=off: never contracted).
+// The walk is row_walk.h's: a group of G = d / 4 lanes owns an output row, the chain of a (row, column) is one lane's, in
+// ascending entry position.  inf_walk_kernel's own: the d columns as four float64 accumulators per lane, what a fetch reads,
+// the early store of an inactive or empty row, the row end held inside nnz.  The 256-lane fold of the dot is gcn_ops.h's.  Every
+// operation is a rounded float64 operation of its own (__dmul_rn / __dadd_rn and -ffp-contract=off: never contracted).
 #include "gcn_ops.h"
 
 namespace ure {
@@ -84,9 +84,8 @@ __global__ __launch_bounds__(kBlock) void inf_coef_kernel(const int32_t *__restr
     }
 }
 
-// out[r] = 2 (sum over row r's entries of a[q] T[idx] [+ b[q] D[idx]]) + reg2 X[r].  Lane `sub` fetches entry p0 + sub, its CSR
-// position (through map on the CSC side) and that position's coefficients; the group then goes through the tile.  An inactive or
-// empty row stores zeros and reads no entry.
+// out[r] = 2 (sum over row r's entries of a[q] T[idx] [+ b[q] D[idx]]) + reg2 X[r].  A fetch reads the entry's coefficients and
+// its index; every entry of the row counts.  An inactive or empty row stores zeros and reads no entry.
 template <int G, bool MAPPED, bool SECOND>
 __global__ __launch_bounds__(kBlock) void inf_walk_kernel(const int64_t *__restrict__ off, const int32_t *__restrict__ idx, const int32_t *__restrict__ map,
                                                           const double *__restrict__ a, const float *__restrict__ T, const double *__restrict__ b,
@@ -94,15 +93,14 @@ __global__ __launch_bounds__(kBlock) void inf_walk_kernel(const int64_t *__restr
                                                           const uint8_t *__restrict__ active, int64_t n_dst, int64_t n_src, int64_t nnz,
                                                           double *__restrict__ out)
 {
-    constexpr int kRows = kBlock / G, D = 4 * G;
-    const int sub = threadIdx.x % G;
-    const int64_t r = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    if (r >= n_dst) return;                                // whole groups leave together
-    const size_t at = (size_t)r * D + 4 * sub;
+    constexpr int D = 4 * G;
+    const RowLanes<G> L;
+    if (L.past(n_dst)) return;
+    const size_t at = (size_t)L.r * D + 4 * L.sub;
     int64_t p_begin = 0, p_end = 0;
-    if (!active || ldg(active + r)) {
-        p_begin = ldg(off + r);
-        p_end = min<int64_t>(ldg(off + r + 1), nnz);
+    if (!active || ldg(active + L.r)) {
+        p_begin = ldg(off + L.r);
+        p_end = min<int64_t>(ldg(off + L.r + 1), nnz);
     }
     d4 acc = d4{0.0, 0.0, 0.0, 0.0};
     if (p_begin >= p_end) {
@@ -110,25 +108,26 @@ __global__ __launch_bounds__(kBlock) void inf_walk_kernel(const int64_t *__restr
         return;
     }
     const unsigned last = (unsigned)(n_src - 1), last_pos = (unsigned)(nnz - 1);
-    const float *__restrict__ t = T + 4 * sub;
-    const double *__restrict__ dd = SECOND ? Dir + 4 * sub : nullptr;
-    for (int64_t p0 = p_begin; p0 < p_end; p0 += G) {
-        const int64_t k = p0 + sub;
-        unsigned mine_j = 0u;
-        double mine_a = 0.0, mine_b = 0.0;
-        if (k < p_end) {
-            const unsigned q = MAPPED ? min((unsigned)ldg(map + k), last_pos) : (unsigned)k;
-            mine_a = ldg(a + q);
-            if (SECOND) mine_b = ldg(b + q);
-            mine_j = min((unsigned)ldg(idx + k), last);
-        }
-        const int m = (int)min<int64_t>(G, p_end - p0);
-        for (int u = 0; u < m; ++u) {
-            const unsigned j = group_read<G>(mine_j, u);
-            acc = d4_mul_add(acc, group_read<G>(mine_a, u), widen(ldg_f4(t + (size_t)j * D)));
-            if (SECOND) acc = d4_mul_add(acc, group_read<G>(mine_b, u), ldg_d4(dd + (size_t)j * D));
-        }
-    }
+    const float *__restrict__ t = T + 4 * L.sub;
+    const double *__restrict__ dd = SECOND ? Dir + 4 * L.sub : nullptr;
+    struct Entry { unsigned j; double a, b; };
+    tile_walk<G>(
+        p_begin, p_end, L.sub,
+        [&](int64_t k, bool inside) {
+            Entry mine{0u, 0.0, 0.0};
+            if (inside) {
+                const unsigned q = entry_pos<MAPPED>(map, k, last_pos);
+                mine.a = ldg(a + q);
+                if (SECOND) mine.b = ldg(b + q);
+                mine.j = min((unsigned)ldg(idx + k), last);
+            }
+            return mine;
+        },
+        [&](const Entry &mine, int u) {
+            const unsigned j = group_read<G>(mine.j, u);
+            acc = d4_mul_add(acc, group_read<G>(mine.a, u), widen(ldg_f4(t + (size_t)j * D)));
+            if (SECOND) acc = d4_mul_add(acc, group_read<G>(mine.b, u), ldg_d4(dd + (size_t)j * D));
+        });
     const d4 x = ldg_d4(X + at);
     d4 y;
     y.x = __dadd_rn(__dmul_rn(2.0, acc.x), __dmul_rn(reg2, x.x));
@@ -139,18 +138,6 @@ __global__ __launch_bounds__(kBlock) void inf_walk_kernel(const int64_t *__restr
 }
 
 constexpr int kDotChunk = 4096;                            // influence.DOT_CHUNK: 16 values per lane
-
-// lane sums -> one value, gcn_step_loss_kernel's fold (thread 0 holds it)
-__device__ __forceinline__ double fold_256(double acc, double *part)
-{
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] = __dadd_rn(part[threadIdx.x], part[threadIdx.x + w]);
-        __syncthreads();
-    }
-    return part[0];
-}
 
 __global__ __launch_bounds__(256) void inf_dot_chunk_kernel(const double *x, const double *y, int64_t n, double *__restrict__ partial)
 {
@@ -276,15 +263,12 @@ extern "C" int ure_inf_walk(const int64_t *off, const int32_t *idx, const int32_
     const double reg2 = 2.0 * reg;
     dispatch_group_width(d / 4, [&](auto w) {
         constexpr int G = decltype(w)::value;
-        const dim3 grid(group_blocks(n_dst, G));
-#define URE_INF_WALK(MAPPED, SECOND)                                                                                                               \
-    hipLaunchKernelGGL((inf_walk_kernel<G, MAPPED, SECOND>), grid, dim3(kBlock), 0, st, off, idx, map, a, T, b, D, reg2, X, active, n_dst, n_src, \
-                       nnz, out)
-        if (map && b) URE_INF_WALK(true, true);
-        else if (map) URE_INF_WALK(true, false);
-        else if (b) URE_INF_WALK(false, true);
-        else URE_INF_WALK(false, false);
-#undef URE_INF_WALK
+        if (b)
+            launch_by_map(map, inf_walk_kernel<G, true, true>, inf_walk_kernel<G, false, true>, n_dst, G, st, off, idx, map, a, T, b, D, reg2, X, active,
+                          n_dst, n_src, nnz, out);
+        else
+            launch_by_map(map, inf_walk_kernel<G, true, false>, inf_walk_kernel<G, false, false>, n_dst, G, st, off, idx, map, a, T, b, D, reg2, X, active,
+                          n_dst, n_src, nnz, out);
     });
     URE_HIP(hipGetLastError());
     return 0;

@@ -1,6 +1,6 @@
 // nmf.hip -- the NeuMF backbone (include/ultrare_nmf.h; the contract is ultrare_amd/nmf.py): the per-sample forward and backward
-// through GMF, MLP and head, the weight-gradient sums over a step's slots, the masked row sums of the embedding gradients and
-// the scoring pass.
+// through GMF, MLP and head, the weight-gradient sums over a step's slots, the masked row sums of the embedding gradients (the
+// walk is row_walk.h's; nmf_row_sum_kernel states what a fetch reads and what a term adds) and the scoring pass.
 //
 // The MLP runs on the VALU (f32 MFMA issues at the vector rate on gfx950 and its summation order cannot be stated).  One
 // wavefront owns a sample: lane o holds the chain of output o of a layer (forward) or of input i (backward), the activations
@@ -212,48 +212,45 @@ __global__ __launch_bounds__(kBlock) void nmf_wgrad_sum_kernel(const float *__re
     stg(out + p, t);
 }
 
-// gcn_grad_kernel's walk with the batch named by rank and the term a slot's row: lane `sub` fetches entry p0 + sub, its CSR
-// position, that position's slot and -- for an entry of the batch -- its residual; the group then goes through the tile.  The
-// group is the power of two that covers width / 4 lanes; lanes beyond the width idle.
+// The masked row sums (row_walk.h's walk): the batch is named by rank and the term is a slot's row.  A fetch reads the entry's
+// slot and -- for an entry of the batch -- its residual; an entry outside the batch has slot -1.  The group is the power of two
+// that covers width / 4 lanes; lanes beyond the width idle.
 template <int G, bool MAPPED>
 __global__ __launch_bounds__(kBlock) void nmf_row_sum_kernel(const int64_t *__restrict__ off, const int32_t *__restrict__ map,
                                                              const int32_t *__restrict__ rank, int64_t n_rows, int64_t nnz, int lo, int n_slots,
                                                              const float *__restrict__ E, int ld, int col0, int width, const float *__restrict__ err,
                                                              float *__restrict__ Gout, double *__restrict__ row_loss)
 {
-    constexpr int kRows = kBlock / G;
-    const int sub = threadIdx.x % G;
-    const int64_t r = (int64_t)blockIdx.x * kRows + threadIdx.x / G;
-    if (r >= n_rows) return;
-    const int64_t b = ldg(off + r), e = ldg(off + r + 1);
+    const RowLanes<G> L;
+    if (L.past(n_rows)) return;
     const unsigned last_pos = (unsigned)(nnz - 1);
-    const bool live = 4 * sub < width;
-    const float *__restrict__ x = E + col0 + 4 * (live ? sub : 0);
+    const bool live = 4 * L.sub < width;
+    const float *__restrict__ x = E + col0 + 4 * (live ? L.sub : 0);
     float4 g = f4_zero();
     double loss = 0.0;
-    for (int64_t p0 = b; p0 < e; p0 += G) {
-        const int64_t p = p0 + sub;
-        int mine_slot = -1;
-        float mine_e = 0.f;
-        if (p < e) {
-            const unsigned q = MAPPED ? min((unsigned)ldg(map + p), last_pos) : (unsigned)p;
-            const int64_t s = (int64_t)ldg(rank + q) - lo;
-            if (s >= 0 && s < n_slots) {
-                mine_slot = (int)s;
-                if (row_loss) mine_e = ldg(err + s);
+    struct Entry { int slot; float e; };
+    tile_walk<G>(
+        ldg(off + L.r), ldg(off + L.r + 1), L.sub,
+        [&](int64_t p, bool inside) {
+            Entry mine{-1, 0.f};
+            if (inside) {
+                const int64_t s = (int64_t)ldg(rank + entry_pos<MAPPED>(map, p, last_pos)) - lo;
+                if (s >= 0 && s < n_slots) {
+                    mine.slot = (int)s;
+                    if (row_loss) mine.e = ldg(err + s);
+                }
             }
-        }
-        const int m = (int)min<int64_t>(G, e - p0);
-        for (int u = 0; u < m; ++u) {
-            const int slot = group_read<G>(mine_slot, u);          // uniform across the group
-            if (slot < 0) continue;
-            const float ee = group_read<G>(mine_e, u);
+            return mine;
+        },
+        [&](const Entry &mine, int u) {
+            const int slot = group_read<G>(mine.slot, u);
+            if (slot < 0) return;
+            const float ee = group_read<G>(mine.e, u);
             g = f4_add(g, ldg_f4(x + (size_t)slot * ld));
             loss += (double)ee * (double)ee;
-        }
-    }
-    if (live) stg_f4(Gout + (size_t)r * width + 4 * sub, g);
-    if (row_loss && sub == 0) stg(row_loss + r, loss);
+        });
+    if (live) stg_f4(Gout + (size_t)L.r * width + 4 * L.sub, g);
+    if (row_loss && L.sub == 0) stg(row_loss + L.r, loss);
 }
 
 }  // namespace
@@ -328,13 +325,8 @@ extern "C" int ure_nmf_row_sum(const int64_t *off, const int32_t *map, const int
     hipStream_t st = (hipStream_t)stream;
     dispatch_group_width(group_width(width / 4), [&](auto w) {
         constexpr int G = decltype(w)::value;
-        const dim3 grid(group_blocks(n_rows, G));
-        if (map)
-            hipLaunchKernelGGL((nmf_row_sum_kernel<G, true>), grid, dim3(kBlock), 0, st, off, map, rank, n_rows, nnz, (int)lo, (int)n_slots, E, (int)ld,
-                               (int)col0, (int)width, err, G_out, row_loss);
-        else
-            hipLaunchKernelGGL((nmf_row_sum_kernel<G, false>), grid, dim3(kBlock), 0, st, off, map, rank, n_rows, nnz, (int)lo, (int)n_slots, E, (int)ld,
-                               (int)col0, (int)width, err, G_out, row_loss);
+        launch_by_map(map, nmf_row_sum_kernel<G, true>, nmf_row_sum_kernel<G, false>, n_rows, G, st, off, map, rank, n_rows, nnz, (int)lo, (int)n_slots, E,
+                      (int)ld, (int)col0, (int)width, err, G_out, row_loss);
     });
     URE_HIP(hipGetLastError());
     return 0;

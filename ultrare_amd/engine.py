@@ -2003,6 +2003,17 @@ def gcn_step_tags(graph, order, batch, stream=None):
     return tag
 
 
+def _gcn_mse_walks(graph, tag, step, U, V, d, err, pred, Gu, Gi, row_loss, st):
+    """The residual pass and the two masked walks of an MSE step on checked tensors (pred may be None)."""
+    g, L = graph, nv.lib()
+    nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(tag), g.nnz, int(step), nv.ptr(U), nv.ptr(V), g.n_user,
+                                g.n_item, d, nv.ptr(err), nv.ptr(pred), st), 'ure_gcn_residual')
+    nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(tag), nv.ptr(err), g.n_user, g.n_item, g.nnz, int(step), nv.ptr(V), d,
+                            nv.ptr(Gu), nv.ptr(row_loss), st), 'ure_gcn_grad')
+    nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(tag), nv.ptr(err), g.n_item, g.n_user, g.nnz, int(step), nv.ptr(U),
+                            d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
+
+
 def gcn_loss_grad(graph, tag, step, U, V, want_pred=False, stream=None):
     """lightgcn.loss_grad_ref of the batch {CSR entries with tag == step} under the final tables (U, V) [rows, d]:
     -> (G_u [n_user, d], G_i [n_item, d], loss float64 [1] on the device, err [nnz], pred [nnz] or None -- both in CSR order, +0.0
@@ -2020,12 +2031,7 @@ def gcn_loss_grad(graph, tag, step, U, V, want_pred=False, stream=None):
     pred = torch.empty(g.nnz, dtype=torch.float32, device=dev) if want_pred else None
     Gu, Gi = torch.empty_like(U), torch.empty_like(V)
     row_loss, loss = torch.empty(g.n_user, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float64, device=dev)
-    nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(tag), g.nnz, int(step), nv.ptr(U), nv.ptr(V), g.n_user,
-                                g.n_item, d, nv.ptr(err), nv.ptr(pred), st), 'ure_gcn_residual')
-    nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(tag), nv.ptr(err), g.n_user, g.n_item, g.nnz, int(step), nv.ptr(V), d,
-                            nv.ptr(Gu), nv.ptr(row_loss), st), 'ure_gcn_grad')
-    nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(tag), nv.ptr(err), g.n_item, g.n_user, g.nnz, int(step), nv.ptr(U),
-                            d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
+    _gcn_mse_walks(g, tag, step, U, V, d, err, pred, Gu, Gi, row_loss, st)
     nv.check(L.ure_gcn_step_loss(nv.ptr(row_loss), g.n_user, 1, nv.ptr(loss), st), 'ure_gcn_step_loss')
     _csr_held_for(stream, err, Gu, Gi, row_loss, loss, *([pred] if want_pred else []))
     return Gu, Gi, loss, err, pred
@@ -2142,7 +2148,80 @@ def bpr_loss_grad(graph, tag, step, U, V, neg, index=None, coef=None, stream=Non
     return Gu, Gi, loss, w, x, sp, sn
 
 
-class GcnJob:
+class _GraphJob:
+    """What the trainers over a GcnGraph share (GcnJob, NmfJob): the checks of batch, epochs and orders, the float32 schedule and
+    scalars, the epoch bookkeeping, and the three launches a step of either makes beside its own -- the gather of the epoch's table
+    at its first step, the loss fold and the SGD update.  A subclass checks its init, allocates its buffers (_pool, _row_loss and
+    _sse among them) and writes _step(e, s, stream)."""
+
+    def _check_sizes(self, graph, batch, epochs):
+        self.graph, self.batch, self.epochs, self.device = graph, int(batch), int(epochs), graph.device
+        if self.batch < 1 or self.epochs < 0:
+            raise ValueError(f'batch {batch!r} must be positive and epochs {epochs!r} not negative')
+
+    def _plan(self, orders, lr, lam, momentum, lr_decay, lr_step):
+        """-> int32 [epochs, N]: a triple's place in every epoch's order (the inverse permutations; place // batch is its step), every
+        order checked once.  Sets the schedule, the scalars and the counters; no device work."""
+        N = self.graph.N
+        orders = np.asarray(orders.cpu() if torch.is_tensor(orders) else orders)
+        if orders.shape != (self.epochs, N) or orders.dtype.kind not in 'iu':
+            raise ValueError(f'orders must be integers of shape ({self.epochs}, {N}), not {orders.dtype} {orders.shape}')
+        places = np.empty((self.epochs, N), dtype=np.int32)
+        for e in range(self.epochs):
+            o = orders[e].astype(np.int64)
+            if o.min() < 0 or o.max() >= N or (np.bincount(o, minlength=N) != 1).any():
+                raise ValueError(f'orders[{e}] is not a permutation of 0 .. {N - 1}')
+            places[e, o] = np.arange(N, dtype=np.int32)
+        # StepLR as engine.TrainJob makes it: float32 values
+        self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
+        self._lam, self._mu = float(np.float32(lam)), float(np.float32(momentum))
+        self.steps = (N + self.batch - 1) // self.batch
+        self.ticks = self.epochs * self.steps
+        self.done = 0            # optimizer steps run
+        return places
+
+    # ---- the launches both jobs make ------------------------------------------------------------------------------------
+    def _gather(self, table, out, st):
+        """out [nnz] (CSR order) = one epoch's row of a file-order table."""
+        g = self.graph
+        nv.check(nv.lib().ure_gcn_gather_tags(nv.ptr(table), nv.ptr(g.pos), g.nnz, nv.ptr(out), st), 'ure_gcn_gather_tags')
+
+    def _fold_loss(self, e, s, st):
+        """The epoch's loss takes (step 0) or is advanced by the fold of the users' sums of this step."""
+        nv.check(nv.lib().ure_gcn_step_loss(nv.ptr(self._row_loss), self.graph.n_user, int(s == 0), self._sse[e:].data_ptr(), st), 'ure_gcn_step_loss')
+
+    def _sgd(self, e, w, m, g, gscale, st):
+        """One update of every parameter at epoch e's rate; counts the step."""
+        nv.check(nv.lib().ure_gcn_sgd_step(nv.ptr(w), nv.ptr(m), nv.ptr(g), w.numel(), gscale, float(self._lr_host[e]), self._lam, self._mu,
+                                           int(self.done == 0), st), 'ure_gcn_sgd_step')
+        self.done += 1
+
+    # ---- what Scratch._train uses of a job -----------------------------------------------------------------------------
+    def steps_per_epoch(self, s=0):
+        return self.steps
+
+    def run_epochs(self, n_epochs, stream=None):
+        """Advance by whole epochs on `stream` (default: the current one).  Nothing synchronises."""
+        assert self._pool is not None, 'the job is closed'
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(self.device))          # (the uploads and fills of __init__)
+        e0 = self.done // self.steps
+        assert self.done % self.steps == 0 and e0 + n_epochs <= self.epochs
+        for e in range(e0, e0 + n_epochs):
+            for s in range(self.steps):
+                self._step(e, s, stream)
+        return self.done
+
+    def run(self, stream=None):
+        return self.run_epochs(self.epochs - self.done // self.steps, stream)
+
+    def epoch_sse(self, s=0):
+        """Per-epoch sum of squared training errors (host float64 array; synchronises)."""
+        assert s == 0
+        return self._sse[:self.epochs].cpu().numpy()
+
+
+class GcnJob(_GraphJob):
     """One shard trained with the LightGCN backbone (lightgcn.train_ref in float32, bit for bit): per step a forward of `layers`
     propagations per side, the residual pass and the two masked gradient walks, `layers` more propagations back, and one SGD
     update of every row of the parameters.  What Scratch._train uses of a TrainJob is here under the same names.
@@ -2164,30 +2243,15 @@ class GcnJob:
             raise ValueError(f'key must be an integer in 0 .. 2^64 - 1, not {key!r}')
         self.loss, self.key = loss, int(key)
         self.layers = lightgcn.check_layers(layers)
-        self.graph, self.k, self.d = graph, int(k), pad_dim(int(k))
-        self.batch, self.epochs, self.device = int(batch), int(epochs), graph.device
-        if self.batch < 1 or self.epochs < 0:
-            raise ValueError(f'batch {batch!r} must be positive and epochs {epochs!r} not negative')
+        self.k, self.d = int(k), pad_dim(int(k))
+        self._check_sizes(graph, batch, epochs)
         P0, Q0 = (np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32) for t in init)
         if P0.shape != (graph.n_user, self.k) or Q0.shape != (graph.n_item, self.k):
             raise ValueError(f'init tables have shapes {P0.shape}, {Q0.shape}: ({graph.n_user}, {self.k}) and ({graph.n_item}, {self.k}) are needed')
-        orders = np.asarray(orders.cpu() if torch.is_tensor(orders) else orders)
-        if orders.shape != (self.epochs, graph.N) or orders.dtype.kind not in 'iu':
-            raise ValueError(f'orders must be integers of shape ({self.epochs}, {graph.N}), not {orders.dtype} {orders.shape}')
-        step_of = (np.arange(graph.N) // self.batch).astype(np.int32)
-        file_tags = np.empty((self.epochs, graph.N), dtype=np.int32)
-        for e in range(self.epochs):
-            o = orders[e].astype(np.int64)
-            if o.min() < 0 or o.max() >= graph.N or (np.bincount(o, minlength=graph.N) != 1).any():
-                raise ValueError(f'orders[{e}] is not a permutation of 0 .. {graph.N - 1}')
-            file_tags[e, o] = step_of
-        # StepLR as engine.TrainJob makes it: float32 values
+        file_tags = (self._plan(orders, lr, lam, momentum, lr_decay, lr_step).astype(np.int64) // self.batch).astype(np.int32)      # a triple's step
         if loss == 'bpr':
             bpr_prepare(graph)                              # (refuses a user without a negative)
-        self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
-        self._lam, self._mu = float(np.float32(lam)), float(np.float32(momentum))
         self._c = float(lightgcn.layer_scale(self.layers))
-        self.steps = (graph.N + self.batch - 1) // self.batch
         dev, R = self.device, graph.n_user + graph.n_item
         self.rows = R
         self._pool = torch.zeros(len(self._TABLES), R, self.d, dtype=torch.float32, device=dev)
@@ -2206,9 +2270,7 @@ class GcnJob:
             self._bpr = dict(neg=ints(), map_n=ints(), usr_n=ints(), off_n=torch.zeros(graph.n_item + 1, dtype=torch.int64, device=dev),
                              w=torch.zeros(graph.nnz, dtype=torch.float32, device=dev),
                              scratch=torch.zeros(int(nv.lib().ure_bpr_index_scratch(graph.nnz, graph.n_item)), dtype=torch.uint8, device=dev))
-        self.done = 0            # optimizer steps run
         self._star_at = -1       # the step count Star belongs to
-        self.ticks = self.epochs * self.steps
 
     # ---- launches ------------------------------------------------------------------------------------------------------
     def _sides(self, t):
@@ -2242,9 +2304,9 @@ class GcnJob:
         self._star_at = self.done
 
     def _step(self, e, s, stream=None):
-        g, t, L, st = self.graph, self._t, nv.lib(), nv.stream_handle(stream)
+        g, t, st = self.graph, self._t, nv.stream_handle(stream)
         if s == 0:
-            nv.check(L.ure_gcn_gather_tags(nv.ptr(self._file_tags[e]), nv.ptr(g.pos), g.nnz, nv.ptr(self._tag), st), 'ure_gcn_gather_tags')
+            self._gather(self._file_tags[e], self._tag, st)
         self._forward(stream)
         U, V = self._sides(t['Star'])
         Gu, Gi = self._sides(t['G'])
@@ -2254,49 +2316,20 @@ class GcnJob:
             if s == 0:                                      # this epoch's negatives and their index
                 _bpr_sample(g, self.key, e, b['neg'], st)
                 _bpr_index(g, b['neg'], *index, b['scratch'], st)
-            nv.check(L.ure_bpr_coef(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(b['neg']), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
-                                    g.n_item, self.d, nv.ptr(b['w']), nv.ptr(self._err), None, None, st), 'ure_bpr_coef')
+            nv.check(nv.lib().ure_bpr_coef(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(b['neg']), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
+                                           g.n_item, self.d, nv.ptr(b['w']), nv.ptr(self._err), None, None, st), 'ure_bpr_coef')
             _bpr_walks(g, self._tag, s, U, V, b['neg'], index, b['w'], self._err, self.d, Gu, Gi, self._row_loss, st)
         else:
-            self._mse_grad(g, s, U, V, Gu, Gi, st)
-        nv.check(L.ure_gcn_step_loss(nv.ptr(self._row_loss), g.n_user, int(s == 0), self._sse[e:].data_ptr(), st), 'ure_gcn_step_loss')
+            _gcn_mse_walks(g, self._tag, s, U, V, self.d, self._err, None, Gu, Gi, self._row_loss, st)
+        self._fold_loss(e, s, st)
         src = t['G']
         for l in range(self.layers):                        # Horner: H^l = G + A H^(l-1)
             dst = t['Xa'] if l % 2 == 0 else t['Xb']
             self._layer(src, dst, t['G'], None, stream)
             src = dst
-        nv.check(L.ure_gcn_sgd_step(nv.ptr(t['W']), nv.ptr(t['M']), nv.ptr(src), src.numel(), self._c, float(self._lr_host[e]), self._lam, self._mu,
-                                    int(self.done == 0), st), 'ure_gcn_sgd_step')
-        self.done += 1
+        self._sgd(e, t['W'], t['M'], src, self._c, st)
 
-    def _mse_grad(self, g, s, U, V, Gu, Gi, st):
-        L = nv.lib()
-        nv.check(L.ure_gcn_residual(nv.ptr(g.row_u), nv.ptr(g.col), nv.ptr(g.rating), nv.ptr(self._tag), g.nnz, s, nv.ptr(U), nv.ptr(V), g.n_user,
-                                    g.n_item, self.d, nv.ptr(self._err), None, st), 'ure_gcn_residual')
-        nv.check(L.ure_gcn_grad(nv.ptr(g.off_u), nv.ptr(g.col), None, nv.ptr(self._tag), nv.ptr(self._err), g.n_user, g.n_item, g.nnz, s, nv.ptr(V),
-                                self.d, nv.ptr(Gu), nv.ptr(self._row_loss), st), 'ure_gcn_grad')
-        nv.check(L.ure_gcn_grad(nv.ptr(g.off_i), nv.ptr(g.row), nv.ptr(g.to_csr), nv.ptr(self._tag), nv.ptr(self._err), g.n_item, g.n_user, g.nnz, s,
-                                nv.ptr(U), self.d, nv.ptr(Gi), None, st), 'ure_gcn_grad')
-
-    # ---- what Scratch._train uses of a job -----------------------------------------------------------------------------
-    def steps_per_epoch(self, s=0):
-        return self.steps
-
-    def run_epochs(self, n_epochs, stream=None):
-        """Advance by whole epochs on `stream` (default: the current one).  Nothing synchronises."""
-        assert self._pool is not None, 'the job is closed'
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream(self.device))          # (the uploads and fills of __init__)
-        e0 = self.done // self.steps
-        assert self.done % self.steps == 0 and e0 + n_epochs <= self.epochs
-        for e in range(e0, e0 + n_epochs):
-            for s in range(self.steps):
-                self._step(e, s, stream)
-        return self.done
-
-    def run(self, stream=None):
-        return self.run_epochs(self.epochs - self.done // self.steps, stream)
-
+    # ---- what Scratch._train uses of a job, beside the base's ------------------------------------------------------------
     def padded_tables(self, s=0, stream=None):
         """The final tables (U*, V*) of the current parameters at the padded width: recomputed by a forward pass when read."""
         assert s == 0
@@ -2317,12 +2350,11 @@ class GcnJob:
         assert s == 0
         if self.loss != 'mse':
             raise ValueError(f"epoch_sse is the MSE job's: a loss={self.loss!r} job reports epoch_loss()")
-        return self._sse[:self.epochs].cpu().numpy()
+        return super().epoch_sse(s)
 
     def epoch_loss(self, s=0):
         """Per-epoch sum of the steps' batch losses, whatever the loss (host float64 array; synchronises)."""
-        assert s == 0
-        return self._sse[:self.epochs].cpu().numpy()
+        return super().epoch_sse(s)
 
     def close(self):
         self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = self._bpr = None
@@ -2481,7 +2513,7 @@ def nmf_rank_pairs(models, k, layers, users, targets, excl=None, stream=None):
     return ranks
 
 
-class NmfJob:
+class NmfJob(_GraphJob):
     """One shard trained with the NeuMF backbone (nmf.train_ref in float32, bit for bit): per step the forward / backward pass over
     the shard's entries (the batch's write their slot), the weight-gradient sums over the slots, the two masked row sums of the
     embedding gradients, the loss fold, and ONE SGD update of every parameter -- both tables and the dense vector are one
@@ -2495,28 +2527,13 @@ class NmfJob:
     def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50):
         from . import nmf
         self.shape = S = nmf.Shape(k, layers)
-        self.graph, self.k, self.layers = graph, S.k, S.layers
-        self.batch, self.epochs, self.device = int(batch), int(epochs), graph.device
-        if self.batch < 1 or self.epochs < 0:
-            raise ValueError(f'batch {batch!r} must be positive and epochs {epochs!r} not negative')
+        self.k, self.layers = S.k, S.layers
+        self._check_sizes(graph, batch, epochs)
         if len(init) != 3:
             raise ValueError('init is (U0, V0, dense0)')
         U0, V0, dense0 = (np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32) for t in init)
         nmf.check_model(U0, V0, dense0, S.k, S.layers, graph.n_user, graph.n_item)
-        orders = np.asarray(orders.cpu() if torch.is_tensor(orders) else orders)
-        if orders.shape != (self.epochs, graph.N) or orders.dtype.kind not in 'iu':
-            raise ValueError(f'orders must be integers of shape ({self.epochs}, {graph.N}), not {orders.dtype} {orders.shape}')
-        file_rank = np.empty((self.epochs, graph.N), dtype=np.int32)
-        place = np.arange(graph.N, dtype=np.int32)
-        for e in range(self.epochs):
-            o = orders[e].astype(np.int64)
-            if o.min() < 0 or o.max() >= graph.N or (np.bincount(o, minlength=graph.N) != 1).any():
-                raise ValueError(f'orders[{e}] is not a permutation of 0 .. {graph.N - 1}')
-            file_rank[e, o] = place                         # the inverse permutation: a triple's place in the epoch's order
-        # StepLR as engine.TrainJob makes it: float32 values
-        self._lr_host = np.array([lr * (lr_decay ** (t // lr_step)) for t in range(self.epochs)], dtype=np.float32)
-        self._lam, self._mu = float(np.float32(lam)), float(np.float32(momentum))
-        self.steps = (graph.N + self.batch - 1) // self.batch
+        file_rank = self._plan(orders, lr, lam, momentum, lr_decay, lr_step)
         self._lay = _nmf_layers(S.layers)
         dev, B = self.device, min(self.batch, graph.N)
         self._nu, self._ni = graph.n_user * S.wd, graph.n_item * S.wd
@@ -2534,8 +2551,6 @@ class NmfJob:
         self._scratch = torch.empty(self._scratch_bytes, dtype=torch.uint8, device=dev)
         self._row_loss = torch.empty(graph.n_user, dtype=torch.float64, device=dev)
         self._sse = torch.zeros(max(self.epochs, 1), dtype=torch.float64, device=dev)
-        self.done = 0            # optimizer steps run
-        self.ticks = self.epochs * self.steps
 
     def _part(self, which):
         """(U, V, dense) views of the parameters (0), the momenta (1) or the gradients (2)."""
@@ -2545,7 +2560,7 @@ class NmfJob:
     def _step(self, e, s, stream=None):
         g, S, L, st = self.graph, self.shape, nv.lib(), nv.stream_handle(stream)
         if s == 0:
-            nv.check(L.ure_gcn_gather_tags(nv.ptr(self._file_rank[e]), nv.ptr(g.pos), g.nnz, nv.ptr(self._rank), st), 'ure_gcn_gather_tags')
+            self._gather(self._file_rank[e], self._rank, st)
         lo = s * self.batch
         n_slots = min(self.batch, g.N - lo)
         (U, V, dense), (gU, gV, gd) = self._part(0), self._part(2)
@@ -2559,38 +2574,12 @@ class NmfJob:
                                    nv.ptr(self._err), gU.data_ptr(), nv.ptr(self._row_loss), st), 'ure_nmf_row_sum')
         nv.check(L.ure_nmf_row_sum(nv.ptr(g.off_i), nv.ptr(g.to_csr), nv.ptr(self._rank), g.n_item, g.nnz, lo, n_slots, nv.ptr(self._emb), 2 * S.wd,
                                    S.wd, S.wd, None, gV.data_ptr(), None, st), 'ure_nmf_row_sum')
-        nv.check(L.ure_gcn_step_loss(nv.ptr(self._row_loss), g.n_user, int(s == 0), self._sse[e:].data_ptr(), st), 'ure_gcn_step_loss')
-        nv.check(L.ure_gcn_sgd_step(self._pool[0].data_ptr(), self._pool[1].data_ptr(), self._pool[2].data_ptr(), self.n_params, 1.0,
-                                    float(self._lr_host[e]), self._lam, self._mu, int(self.done == 0), st), 'ure_gcn_sgd_step')
-        self.done += 1
-
-    # ---- what Scratch._train uses of a job -----------------------------------------------------------------------------
-    def steps_per_epoch(self, s=0):
-        return self.steps
-
-    def run_epochs(self, n_epochs, stream=None):
-        """Advance by whole epochs on `stream` (default: the current one).  Nothing synchronises."""
-        assert self._pool is not None, 'the job is closed'
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream(self.device))          # (the uploads and fills of __init__)
-        e0 = self.done // self.steps
-        assert self.done % self.steps == 0 and e0 + n_epochs <= self.epochs
-        for e in range(e0, e0 + n_epochs):
-            for s in range(self.steps):
-                self._step(e, s, stream)
-        return self.done
-
-    def run(self, stream=None):
-        return self.run_epochs(self.epochs - self.done // self.steps, stream)
+        self._fold_loss(e, s, st)
+        self._sgd(e, *self._pool, 1.0, st)                  # (the pool's rows: parameters, momenta, gradients)
 
     def params(self):
         """(U [n_user, k + e], V [n_item, k + e], dense): views of the job's current parameters."""
         return self._part(0)
-
-    def epoch_sse(self, s=0):
-        """Per-epoch sum of squared training errors (host float64 array; synchronises)."""
-        assert s == 0
-        return self._sse[:self.epochs].cpu().numpy()
 
     def close(self):
         self._pool = self._file_rank = self._rank = self._err = self._act = self._dlt = self._emb = self._scratch = self._row_loss = self._sse = None
