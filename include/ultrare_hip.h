@@ -787,5 +787,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_nmf.h"
 /* Full-catalogue top-k and exact ranks under a NeuMF ensemble (csrc/nmf_rank.hip): one lane per item, the layer-0 user prefix shared. */
 #include "ultrare_nmf_rank.h"
+/* Full-catalogue top-k and exact ranks under the learned shard combiner (csrc/mf_combine_rank.hip): ure_score_weighted's floats, ranked. */
+#include "ultrare_combine_rank.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -239,6 +239,19 @@ _NMF_RANK_PROTOTYPES = {
 }
 NMF_RANK_EXPORTS = tuple(_NMF_RANK_PROTOTYPES)
 
+# include/ultrare_combine_rank.h (top-k and exact ranks under the learned shard combiner, csrc/mf_combine_rank.hip): ure_recommend_topk's /
+# ure_rank_pairs' arguments followed by link, W, n_groups, group_of_user, n_user; tests/test_cpu_combine_rank.py holds the table to the header.
+_COMBINER = [_i32, _vp, _i32, _vp, _i32]
+_COMBINE_RANK_PROTOTYPES = {
+    'ure_recommend_weighted_scratch': (_i64, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    'ure_recommend_topk_weighted': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp,
+                                                   _vp, _i64, _vp] + _COMBINER),
+    'ure_rank_pairs_weighted_scratch': (_i64, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
+    'ure_rank_pairs_weighted': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _i64, _vp] + _COMBINER),
+}
+COMBINE_RANK_EXPORTS = tuple(_COMBINE_RANK_PROTOTYPES)
+
 _lib = None
 
 
@@ -254,7 +267,8 @@ def lib():
         # Loading this library first would pull /opt/rocm's copy and split the process in two.
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES,
+                                  **_COMBINE_RANK_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -124,6 +124,65 @@ def first_group_map(groups, n_user):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Ranking under the fitted weights (csrc/mf_combine_rank.hip, include/ultrare_combine_rank.h): the contract in numpy.
+# ---------------------------------------------------------------------------------------------------------------------
+def weight_rows(W, users, group_of_user=None):
+    """The weight row of every user of `users` -> (rows float64 [n, S + 1], outside bool [n]): W[group_of_user[u]], row 0
+    without a map; a user whose entry is outside [0, G) (or whose id is outside the map) is `outside` and gets the mean
+    ensemble w = 1/S, b = 0."""
+    W = np.asarray(W, dtype=np.float64)
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    if group_of_user is None:
+        g = np.zeros(len(users), dtype=np.int64)
+    else:
+        m = np.asarray(group_of_user, dtype=np.int64)
+        inside = (users >= 0) & (users < len(m))
+        g = np.where(inside, m[np.where(inside, users, 0)], -1)
+    outside = (g < 0) | (g >= len(W))
+    rows = W[np.where(outside, 0, g)].copy()
+    rows[outside] = mean_weights(W.shape[1] - 1)
+    return rows, outside
+
+
+def weighted_scores_ref(P, link, rows, outside=None):
+    """score_w of ure_score_weighted from the per-model float32 scores P [n, S] (column s: model s's score as ure_score gives
+    it for that model alone) and the pairs' weight rows [n, S + 1]: p_s = 0.f + P[:, s] (a score of -0.0 becomes +0.0);
+    z = b, then z = z + w[s] * (double)p_s for s = 0, 1, ... with every product rounded; mu = z (link 0) or
+    1 / (1 + exp(-z)) (link 1); -> (float32)mu.  `outside` pairs (weight_rows) are NaN under link 1.  numpy's exp may differ
+    from the device's in the last place: the linear link is exact here, the logistic one to that."""
+    code = link if isinstance(link, (int, np.integer)) and not isinstance(link, bool) else link_code(link)
+    P = np.asarray(P, dtype=np.float32)
+    rows = np.asarray(rows, dtype=np.float64)
+    S = P.shape[1]
+    z = rows[:, S].copy()
+    for s in range(S):
+        z = z + rows[:, s] * (np.float32(0) + P[:, s]).astype(np.float64)
+    with np.errstate(over='ignore'):
+        mu = z if code == 0 else 1.0 / (1.0 + np.exp(-z))
+    if code != 0 and outside is not None:
+        mu = np.where(outside, np.nan, mu)
+    return mu.astype(np.float32)
+
+
+def recommend_ref(scores, top_k, excl=None):
+    """ure_recommend_topk_weighted over a score matrix [n, n_item] float32 (score_w of every (query user, item) pair) ->
+    (scores [n, top_k] float32, items [n, top_k] int64): per query row the top_k non-excluded items in key order (score
+    descending, NaN below -inf, -0.0 == +0.0, then item id ascending); padding is (NaN, -1).  excl = (off [n + 1], items)."""
+    from .nmf import recommend_ref as by_key
+    scores = np.asarray(scores, dtype=np.float32)
+    return by_key(None, None, None, None, scores.shape[1], top_k, excl, scores=scores)
+
+
+def rank_ref(scores, targets, excl=None):
+    """ure_rank_pairs_weighted over a score matrix [n, n_item] float32 -> ranks int32 [n_targets] in input order: for target t
+    of query row q the number of non-excluded items whose key beats t's, -1 when t is excluded.  targets = (off [n + 1],
+    items): any order, duplicates, empty rows.  A target of rank r < top_k is item r of recommend_ref's row."""
+    from .nmf import rank_ref as by_key
+    scores = np.asarray(scores, dtype=np.float32)
+    return by_key(None, None, None, None, targets, excl, scores=scores, n_item=scores.shape[1])
+
+
 class Combiner:
     """Fitted weights of the shard scores.  W float64 [G, S + 1] (host; row g = (w, b) of group g), link ('linear' |
     'logistic'), groups (the index lists the rows belong to, or None: one row for every user), and per group n, iters,
@@ -159,6 +218,29 @@ class Combiner:
             raise ValueError(f"{int((m < 0).sum())} of {n_user} users are in no group (the first: {int(np.flatnonzero(m < 0)[0])}): "
                              "link='logistic' has no weights for them")
         return m
+
+    def check_query(self, n_models, users, n_user):
+        """What recommend / rank_eval check before any device work (ValueError): the combiner was fitted on n_models models, and
+        under the logistic link every QUERY user is in a group (under the linear link such a user takes the mean weights)."""
+        if self.n_models != n_models:
+            raise ValueError(f'the combiner was fitted on {self.n_models} models, not {n_models}')
+        if self.groups is None or self.link_code == 0:
+            return
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        m = first_group_map(self.groups, n_user)
+        lost = users[(users < 0) | (users >= n_user) | (m[np.clip(users, 0, max(n_user - 1, 0))] < 0)] if n_user > 0 else users
+        if lost.size:
+            raise ValueError(f"{lost.size} of {users.size} query users are in no group (the first: {int(lost[0])}): link='logistic' has no weights for them")
+
+    def on_device_for_query(self, device, n_user):
+        """on_device for a ranking call: the same tensors, but the map is not refused for users outside every group (check_query
+        has looked at the query users; the others are not scored)."""
+        import torch
+        key = (str(device), int(n_user), 'query')
+        if key not in self._dev:
+            m = None if self.groups is None else first_group_map(self.groups, n_user)
+            self._dev[key] = (torch.from_numpy(self.W).to(device), None if m is None else torch.from_numpy(m).to(device))
+        return self._dev[key]
 
     def on_device(self, device, n_user):
         """(W tensor [G, S + 1] float64, group_of_user int32 tensor or None) on `device`, uploaded once per (device, n_user)."""

@@ -34,8 +34,6 @@ constexpr int kCbOwn = 3;                // sums per thread: 595 <= 3 * 256
 static inline int64_t cb_len(int S) { return 2 + (int64_t)(S + 1) + (int64_t)(S + 1) * (S + 2) / 2; }
 static inline int64_t cb_blocks(int64_t n) { return std::min<int64_t>((n + kCbTile - 1) / kCbTile, kCbMaxBlocks); }
 
-__device__ __forceinline__ double link_mean(int link, double z) { return link == 0 ? z : 1.0 / (1.0 + exp(-z)); }
-
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void combine_stats_kernel(TableList T, int S, const int32_t *__restrict__ uid,
                                                                const int32_t *__restrict__ iid, const float *__restrict__ rating,

@@ -1,5 +1,5 @@
 // rank_count.h -- exact full-catalogue ranks of (user, item) pairs under an ensemble, written once for every scorer policy of
-// rec_select.h (mf_rank.hip: the MF dot products; nmf_rank.hip: the NeuMF forward).
+// rec_select.h (mf_rank.hip: the MF dot products; nmf_rank.hip: the NeuMF forward; mf_combine_rank.hip: the shard combiner).
 //
 // rank(q, t) = the number of items j of [0, n_item) outside query row q's exclusion list whose key
 // rec_key(score(u, j), j) is greater than the target's key rec_key(score(u, t), t) (rec_score.h: the keys are unique).  An

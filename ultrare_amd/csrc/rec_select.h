@@ -1,5 +1,5 @@
 // rec_select.h -- full-catalogue top-k selection from an ensemble, written once for every scorer (mf_recommend.hip: the MF dot
-// products of rec_score.h; nmf_rank.hip: the NeuMF forward).
+// products of rec_score.h; nmf_rank.hip: the NeuMF forward; mf_combine_rank.hip: the MF dot products under the shard combiner).
 //
 // One fused pass scores and selects; the score matrix never reaches HBM.  A workgroup owns a tile of
 // QT = 4 * QW users (QW per wave) and streams the item tiles of its split: the scorer gives each lane the

@@ -1,13 +1,15 @@
 // score_dot.h -- the scaffold of the ensemble-scoring kernels (mf_eval.hip, mf_combine.hip): the LPR = d / 4 lanes of a group hold
 // one float4 each of a user row and an item row; the lane's four products are one fmaf chain and the lanes are added by the
 // group's xor butterfly (group_sum), so every lane of the group ends with the score.  Here, once: the lane-group coordinates
-// (PairLanes), the dot (pair_dot), the squared-error partials ure_eval_reduce and the host read (sq_partials), and on the host
+// (PairLanes), the dot (pair_dot), the combiner's link (link_mean, which rec_score.h's weighted scorer calls too), the
+// squared-error partials ure_eval_reduce and the host read (sq_partials), and on the host
 // the model list, the grid size and the width dispatch (group_width.h).
 // NOT here: the gather of four models' rows, which score_kernel, combine_stats_kernel and score_weighted_kernel each spell out.
 // As one inlined function it changed their loops' code (the row offset scaled to bytes ahead of the loop, the blocks laid out
 // in another order) and measured 1-2 % slower in score_kernel and combine_stats_kernel.
 #pragma once
 #include <algorithm>
+#include <cmath>
 
 #include "group_width.h"
 #include "ure_internal.h"
@@ -58,6 +60,11 @@ __device__ __forceinline__ float pair_dot(const float4 a, const float4 b)
     p = fmaf(a.w, b.w, p);
     return group_sum<LPR>(p);
 }
+
+// The mean of the combiner's generalised linear model (mf_combine.hip) at z: link 0 the identity, link 1 the logistic function.
+// Here, once, for ure_combine_stats, ure_score_weighted and the weighted scorer of rec_score.h: their floats agree bit for bit
+// because they are this function's.
+__device__ __forceinline__ double link_mean(int link, double z) { return link == 0 ? z : 1.0 / (1.0 + exp(-z)); }
 
 // The squared errors of a launch, sq per thread, as sse[URE_SCORE_PARTIALS]: one partial per workgroup -- its waves' butterfly
 // sums added in double, in order -- and zeros behind the last workgroup's.  No atomics: thousands of waves adding to ONE address

@@ -1150,10 +1150,28 @@ def exclusion_rows(csr, users):
     return off, (np.concatenate(rows) if rows else np.zeros(0, dtype=np.int32)).astype(np.int32)
 
 
-def recommend(tables, d, users, k, excl=None, stream=None):
+def _ranking_weights(weights, S, what):
+    """(link code, W, group_of_user) of the weights = (link, W, group_of_user or None) of a ranking call, checked as score_weighted
+    checks them: W a device float64 [G, S + 1] tensor, group_of_user a device int32 tensor or None (row 0 for every user)."""
+    if not isinstance(weights, (tuple, list)) or len(weights) != 3:
+        raise ValueError(f'{what}: weights = (link, W, group_of_user or None)')
+    link, W, gou = weights
+    code = _link_code(link)
+    if not 1 <= S <= nv.MAX_MODELS_PER_CALL:
+        raise ValueError(f'{what} takes 1 .. {nv.MAX_MODELS_PER_CALL} models under weights, not {S}')
+    if not (torch.is_tensor(W) and W.is_cuda and W.dtype == torch.float64 and W.dim() == 2 and W.shape[1] == S + 1 and W.shape[0] >= 1):
+        raise ValueError(f'W must be a device float64 [G, {S + 1}] tensor')
+    if gou is not None and not (torch.is_tensor(gou) and gou.is_cuda and gou.dtype == torch.int32 and gou.is_contiguous() and gou.numel() >= 1):
+        raise ValueError('group_of_user must be a contiguous, non-empty device torch.int32 tensor')
+    return code, W.contiguous(), gou
+
+
+def recommend(tables, d, users, k, excl=None, stream=None, weights=None):
     """Top-k items of every user of `users` over the whole catalogue (ure_recommend_topk): tables = [(U, V)] device tensors of
     width d, the scores those of ure_score over the same list (the ensemble mean of baseTest), excl = (off, items) from
-    exclusion_rows or None.  Returns (scores [n, k] float32, items [n, k] int64) on the device; padding is (NaN, -1)."""
+    exclusion_rows or None.  Returns (scores [n, k] float32, items [n, k] int64) on the device; padding is (NaN, -1).
+    weights = (link, W, group_of_user or None) on the device: the scores are score_weighted's for the same pairs instead (the
+    learned shard combiner, ure_recommend_topk_weighted; at most 32 models), ordered by the same key."""
     users = users.detach().cpu().numpy() if torch.is_tensor(users) else np.asarray(users)
     users = users.astype(np.int64).reshape(-1)
     if not tables:
@@ -1183,12 +1201,24 @@ def recommend(tables, d, users, k, excl=None, stream=None):
         e_off = to_device_async(off, dev)
         e_items = to_device_async(items if items.size else np.zeros(1, dtype=np.int32), dev)
     L = nv.lib()
-    nbytes = int(L.ure_recommend_scratch(n, n_item, k))
+    if weights is not None:
+        code, W, gou = _ranking_weights(weights, len(tables), 'recommend')
+        nbytes = int(L.ure_recommend_weighted_scratch(n, n_item, k, d, len(tables), code, int(W.shape[0])))
+        if nbytes < 0:
+            raise ValueError(f'ure_recommend_weighted_scratch refused n_query = {n}, n_item = {n_item}, k = {k}, d = {d}')
+    else:
+        nbytes = int(L.ure_recommend_scratch(n, n_item, k))
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     scores = torch.empty(n, k, dtype=torch.float32, device=dev)
     items_out = torch.empty(n, k, dtype=torch.int32, device=dev)
     Up = (ctypes.c_void_p * len(tables))(*[U.data_ptr() for U, _ in tables])
     Vp = (ctypes.c_void_p * len(tables))(*[V.data_ptr() for _, V in tables])
+    if weights is not None:
+        nv.check(L.ure_recommend_topk_weighted(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(e_off), nv.ptr(e_items), k, nv.ptr(scores),
+                                               nv.ptr(items_out), nv.ptr(scratch), scratch.numel(), nv.stream_handle(stream), code, nv.ptr(W),
+                                               int(W.shape[0]), nv.ptr(gou), int(gou.numel()) if gou is not None else 0),
+                 'ure_recommend_topk_weighted')
+        return scores, items_out.long()
     nv.check(L.ure_recommend_topk(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(e_off), nv.ptr(e_items), k, nv.ptr(scores),
                                   nv.ptr(items_out), nv.ptr(scratch), scratch.numel(), nv.stream_handle(stream)), 'ure_recommend_topk')
     return scores, items_out.long()
@@ -1205,12 +1235,13 @@ def _check_rows(off, items, n_rows, n_item, what):
     return off, items.astype(np.int32)
 
 
-def rank_pairs(tables, d, users, targets, excl=None, stream=None):
+def rank_pairs(tables, d, users, targets, excl=None, stream=None, weights=None):
     """Exact full-catalogue rank of every (user, target item) pair (ure_rank_pairs): tables = [(U, V)] device tensors of width d,
     targets = (off [n + 1], items) with query row q's targets items[off[q]:off[q + 1]] (any order, duplicates, empty rows),
     excl = (off, items) from exclusion_rows or None.  rank = the number of non-excluded items whose (score, id) key beats the
     target's -- the position recommend would give it -- or -1 for an excluded target.  Returns ranks [len(items)] int32 on the
-    device, in input order."""
+    device, in input order.  weights = (link, W, group_of_user or None) on the device: the ranks under score_weighted's scores,
+    as recommend(..., weights=) orders them (ure_rank_pairs_weighted)."""
     users = users.detach().cpu().numpy() if torch.is_tensor(users) else np.asarray(users)
     users = users.astype(np.int64).reshape(-1)
     if not tables:
@@ -1229,6 +1260,8 @@ def rank_pairs(tables, d, users, targets, excl=None, stream=None):
         assert U.shape == (n_user, d) and V.shape == (n_item, d) and U.is_contiguous() and V.is_contiguous() and U.dtype == V.dtype == torch.float32
     dev = tables[0][0].device
     n, n_t = len(users), len(t_items)
+    if weights is not None:
+        code, W, gou = _ranking_weights(weights, len(tables), 'rank_pairs')
     ranks = torch.empty(max(n_t, 1), dtype=torch.int32, device=dev)
     if n_t == 0:
         return ranks[:0]
@@ -1239,12 +1272,18 @@ def rank_pairs(tables, d, users, targets, excl=None, stream=None):
         e_off = to_device_async(e_off_h, dev)
         e_items = to_device_async(e_items_h if e_items_h.size else np.zeros(1, dtype=np.int32), dev)
     L = nv.lib()
-    nbytes = int(L.ure_rank_pairs_scratch(n, n_t, n_item, d))
+    nbytes = int(L.ure_rank_pairs_scratch(n, n_t, n_item, d) if weights is None else
+                 L.ure_rank_pairs_weighted_scratch(n, n_t, n_item, d, len(tables), code, int(W.shape[0])))
     if nbytes < 0:
         raise ValueError(f'ure_rank_pairs_scratch refused n_query = {n}, n_targets = {n_t}, n_item = {n_item}, d = {d}')
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     Up = (ctypes.c_void_p * len(tables))(*[U.data_ptr() for U, _ in tables])
     Vp = (ctypes.c_void_p * len(tables))(*[V.data_ptr() for _, V in tables])
+    if weights is not None:
+        nv.check(L.ure_rank_pairs_weighted(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(d_off), nv.ptr(d_items), nv.ptr(e_off),
+                                           nv.ptr(e_items), nv.ptr(ranks), nv.ptr(scratch), nbytes, nv.stream_handle(stream), code, nv.ptr(W),
+                                           int(W.shape[0]), nv.ptr(gou), int(gou.numel()) if gou is not None else 0), 'ure_rank_pairs_weighted')
+        return ranks
     nv.check(L.ure_rank_pairs(Up, Vp, len(tables), nv.ptr(uid), n, n_item, d, nv.ptr(d_off), nv.ptr(d_items), nv.ptr(e_off), nv.ptr(e_items),
                               nv.ptr(ranks), nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_rank_pairs')
     return ranks

@@ -255,8 +255,7 @@ class Sisa(Scratch):
         """Sisa.test with the fitted weights: (rmse, ndcg, hr), kept in self.log0c and saved as log0c.npy beside log0.npy.
         Sisa.test and log0 stay the mean's."""
         self._refuse_nmf('test_combined')
-        if getattr(self, 'combiner', None) is None:
-            raise ValueError('no combiner: call fit_combiner after learn / unlearn (a deletion drops the fitted weights)')
+        self._need_combiner()
         rmse, ndcg, hr = baseTest(test_data, self.model_list, nn.MSELoss(reduction='sum'), self.device, verbose, combiner=self.combiner)
         self.log0c = {'total_rmse': rmse, 'total_ndcg': ndcg, 'total_hr': hr}
         if len(save_dir) > 0:
@@ -264,6 +263,12 @@ class Sisa(Scratch):
         return rmse, ndcg, hr
 
     # ------------------------------------------------------------------ helpers
+    def _need_combiner(self):
+        """self.combiner, or the ValueError of every call that scores with the fitted weights."""
+        if getattr(self, 'combiner', None) is None:
+            raise ValueError('no combiner: call fit_combiner after learn / unlearn (a deletion drops the fitted weights)')
+        return self.combiner
+
     def _rows_dev(self, i):
         """group_index[i] as a device int64 tensor; all groups go up together, once per (group_index object, its group sizes, device):
         the reference reads self.group_index at every merge (sisa.py:55-56), so a reassigned list or another current device must not
@@ -666,24 +671,27 @@ class Sisa(Scratch):
         return logs
 
     # ------------------------------------------------------------------ unlearn
-    def recommend(self, users, top_k=10, exclude=None):
+    def recommend(self, users, top_k=10, exclude=None, combined=False):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers
         from the retrained shards.  Every rank of a parallel run holds the merged models and answers its own queries.
-        The 'nmf' backbone is answered by recommend_nmf."""
+        The 'nmf' backbone is answered by recommend_nmf.  combined=True ranks under self.combiner's weights (the ensemble
+        test_combined reports) and raises test_combined's ValueError without one: learn, unlearn, fold_in and
+        attribute_unlearn drop it."""
         self._refuse_nmf('recommend')
-        return recommend(self.model_list, users, top_k, exclude)
+        return recommend(self.model_list, users, top_k, exclude, combiner=self._need_combiner() if combined else None)
 
     def recommend_nmf(self, users, top_k=10, exclude=None):
         """recommend for the 'nmf' backbone (utils.recommend_nmf over self.model_list): the same return values and padding, the
         scores those baseTest gives a NeuMF ensemble; after unlearn it answers from the retrained shards."""
         return utils.recommend_nmf(self.model_list, users, top_k, exclude)
 
-    def rank_eval(self, test_data, exclude=None, ks=(10, 20)):
+    def rank_eval(self, test_data, exclude=None, ks=(10, 20), combined=False):
         """Full-ranking HR@K / Recall@K / NDCG@K / MRR of the current ensemble on a test loader (utils.rank_eval over
         self.model_list): after unlearn it evaluates the retrained shards.  Every rank of a parallel run holds the merged models
-        and answers for itself.  The 'nmf' backbone is evaluated by rank_eval_nmf."""
+        and answers for itself.  The 'nmf' backbone is evaluated by rank_eval_nmf.  combined=True: under self.combiner's
+        weights, as recommend(combined=True)."""
         self._refuse_nmf('rank_eval')
-        return rank_eval(self.model_list, test_data, exclude, ks)
+        return rank_eval(self.model_list, test_data, exclude, ks, combiner=self._need_combiner() if combined else None)
 
     def rank_eval_nmf(self, test_data, exclude=None, ks=(10, 20)):
         """rank_eval for the 'nmf' backbone (utils.rank_eval_nmf over self.model_list): the same metrics over the whole catalogue;

@@ -380,17 +380,32 @@ def als_sweeps(model, train_data, l2, l2_n=0.0, sweeps=1):
     return MF.from_tables(U[:, :k].clone().contiguous(), V[:, :k].clone().contiguous()), np.asarray(objectives, dtype=np.float64)
 
 
-def recommend(models, users, top_k=10, exclude=None):
+def _ranking_weights(combiner, models, users, who):
+    """What recommend / rank_eval check of a combiner before any device work (ValueError): NeuMF models by name, the number of
+    models it was fitted on, and under the logistic link a query user in no group.  -> a function of the padded tables that
+    gives engine's weights = (link, W, group_of_user) on their device."""
+    refuse_nmf(models, f'{who}(combiner=)')
+    n_user = int(models[0].user_mat.weight.shape[0]) if len(models) else 0
+    combiner.check_query(len(models), users, n_user)
+    return lambda tabs: (combiner.link_code, *combiner.on_device_for_query(tabs[0][0].device, int(tabs[0][0].shape[0])))
+
+
+def recommend(models, users, top_k=10, exclude=None, combiner=None):
     """The top_k items of each user in `users` over the whole catalogue, by the score baseTest gives the pair (the mean of
     `models`, bit for bit), ties by ascending item id.  exclude: a scipy CSR with user ids as rows (read.readSparseMat of the
     training set) whose items are never returned.  Returns (scores [n, top_k], items [n, top_k] int64) on the device; a user
     with fewer eligible items than top_k gets (NaN, -1) at the end.  The full model is recommend([model], ...).
-    NeuMF models are answered by recommend_nmf."""
+    NeuMF models are answered by recommend_nmf.
+    combiner (fit_combiner's result, optional): the score is baseTest(..., combiner=)'s for the pair instead, bit for bit, and
+    the order is by that float (under the logistic link many items can share 1.0f: ties by item id).  ValueError before any
+    device work for a combiner fitted on another number of models and, under the logistic link, for a query user in no group
+    (under the linear link such a user takes the mean weights)."""
     refuse_nmf(models, 'recommend')
-    tabs = [padded_tables(m) for m in models]
     users = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
+    weights = _ranking_weights(combiner, models, users, 'recommend') if combiner is not None else None
+    tabs = [padded_tables(m) for m in models]
     excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
-    return engine.recommend([(U, V) for U, V, _ in tabs], tabs[0][2], users, top_k, excl)
+    return engine.recommend([(U, V) for U, V, _ in tabs], tabs[0][2], users, top_k, excl, weights=weights and weights(tabs))
 
 
 def relevant_pairs(test_data, n_item):
@@ -442,18 +457,23 @@ def rank_metrics(off, ranks, ks=(10, 20)):
     return out
 
 
-def rank_eval(models, test_data, exclude=None, ks=(10, 20)):
+def rank_eval(models, test_data, exclude=None, ks=(10, 20), combiner=None):
     """Full-ranking evaluation of the ensemble mean of `models` (the score baseTest gives a pair, bit for bit): every distinct
     (user, item) pair of `test_data` (a test loader, as baseTest takes) is ranked among ALL items the user has not trained on
     -- exclude: a scipy CSR with user ids as rows, read.readSparseMat of the training set -- by (score, id) as recommend orders
     them, and HR@K, Recall@K, NDCG@K and MRR are taken from those ranks (rank_metrics; every test pair is relevant, no rating
     threshold).  These are NOT baseTest's HR@10 / NDCG@10, which rank a user's test items only against each other.  A test pair
-    that is also in `exclude` does not count.  Returns the dict of rank_metrics.  NeuMF models are evaluated by rank_eval_nmf."""
+    that is also in `exclude` does not count.  Returns the dict of rank_metrics.  NeuMF models are evaluated by rank_eval_nmf.
+    combiner (optional): the ranks under the fitted weights, as recommend(..., combiner=) orders the items, with its refusals."""
     refuse_nmf(models, 'rank_eval')
+    if combiner is not None:
+        n_item = int(models[0].item_mat.weight.shape[0]) if len(models) else 0
+        weights = _ranking_weights(combiner, models, relevant_pairs(test_data, n_item)[0], 'rank_eval')
     tabs = [padded_tables(m) for m in models]
     users, off, items = relevant_pairs(test_data, int(tabs[0][1].shape[0]))
     excl = engine.exclusion_rows(exclude, users) if exclude is not None else None
-    ranks = engine.rank_pairs([(U, V) for U, V, _ in tabs], tabs[0][2], users, (off, items), excl)
+    ranks = engine.rank_pairs([(U, V) for U, V, _ in tabs], tabs[0][2], users, (off, items), excl,
+                              weights=weights(tabs) if combiner is not None else None)
     return rank_metrics(off, ranks, ks)
 
 

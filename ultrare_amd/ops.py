@@ -59,6 +59,10 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         (new)             recommend_topk under a NeuMF ensemble of one stack
     torch.ops.ultrare.nmf_rank_pairs(Us, Vs, denses, k, layers, users, tgt_off, tgt_items, excl_off, excl_items)
                                                         (new)             rank_pairs under a NeuMF ensemble of one stack
+    torch.ops.ultrare.recommend_topk_weighted(Us, Vs, users, excl_off, excl_items, k, link, W, group_of_user)
+                                                        (new)             recommend_topk under the learned shard combiner's scores
+    torch.ops.ultrare.rank_pairs_weighted(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items, link, W, group_of_user)
+                                                        (new)             rank_pairs under the learned shard combiner's scores
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -170,6 +174,43 @@ def rank_pairs(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.Tens
 
 @rank_pairs.register_fake
 def _(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items):
+    return Us[0].new_empty(tgt_items.numel(), dtype=torch.int32)
+
+
+def _weights(link, W, group_of_user):
+    return link, W.to(torch.float64).contiguous(), None if group_of_user is None else group_of_user.to(torch.int32).contiguous()
+
+
+@torch.library.custom_op('ultrare::recommend_topk_weighted', mutates_args=())
+def recommend_topk_weighted(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.Tensor, excl_off: Optional[torch.Tensor],
+                            excl_items: Optional[torch.Tensor], k: int, link: int, W: torch.Tensor,
+                            group_of_user: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """engine.recommend(..., weights=(link, W, group_of_user)): (scores [n, k], items [n, k] int64) under score_weighted's scores."""
+    _dev(*Us, *Vs, users, W, *[t for t in (excl_off, excl_items, group_of_user) if t is not None])
+    assert len(Us) == len(Vs) and (excl_off is None) == (excl_items is None)
+    excl = None if excl_off is None else (excl_off.cpu().numpy(), excl_items.cpu().numpy())
+    return engine.recommend(list(zip(Us, Vs)), Us[0].shape[1], users, k, excl, weights=_weights(link, W, group_of_user))
+
+
+@recommend_topk_weighted.register_fake
+def _(Us, Vs, users, excl_off, excl_items, k, link, W, group_of_user):
+    return Us[0].new_empty(users.numel(), k), Us[0].new_empty(users.numel(), k, dtype=torch.int64)
+
+
+@torch.library.custom_op('ultrare::rank_pairs_weighted', mutates_args=())
+def rank_pairs_weighted(Us: List[torch.Tensor], Vs: List[torch.Tensor], users: torch.Tensor, tgt_off: torch.Tensor, tgt_items: torch.Tensor,
+                        excl_off: Optional[torch.Tensor], excl_items: Optional[torch.Tensor], link: int, W: torch.Tensor,
+                        group_of_user: Optional[torch.Tensor]) -> torch.Tensor:
+    """engine.rank_pairs(..., weights=(link, W, group_of_user)): ranks int32 [len(tgt_items)] under score_weighted's scores."""
+    _dev(*Us, *Vs, users, tgt_off, tgt_items, W, *[t for t in (excl_off, excl_items, group_of_user) if t is not None])
+    assert len(Us) == len(Vs) and (excl_off is None) == (excl_items is None)
+    excl = None if excl_off is None else (excl_off.cpu().numpy(), excl_items.cpu().numpy())
+    return engine.rank_pairs(list(zip(Us, Vs)), Us[0].shape[1], users, (tgt_off.cpu().numpy(), tgt_items.cpu().numpy()), excl,
+                             weights=_weights(link, W, group_of_user))
+
+
+@rank_pairs_weighted.register_fake
+def _(Us, Vs, users, tgt_off, tgt_items, excl_off, excl_items, link, W, group_of_user):
     return Us[0].new_empty(tgt_items.numel(), dtype=torch.int32)
 
 
