@@ -789,5 +789,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_nmf_rank.h"
 /* Full-catalogue top-k and exact ranks under the learned shard combiner (csrc/mf_combine_rank.hip): ure_score_weighted's floats, ranked. */
 #include "ultrare_combine_rank.h"
+/* In-training attribute unlearning (csrc/attr_train.hip): a step's rows selected on the device, the MMD / u2u losses at device counts. */
+#include "ultrare_attr_train.h"
 
 #endif /* ULTRARE_HIP_H */

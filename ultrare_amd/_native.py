@@ -252,6 +252,21 @@ _COMBINE_RANK_PROTOTYPES = {
 }
 COMBINE_RANK_EXPORTS = tuple(_COMBINE_RANK_PROTOTYPES)
 
+# include/ultrare_attr_train.h (in-training attribute unlearning, csrc/attr_train.hip): a table of its own, as the header is;
+# tests/test_cpu_attr_train.py holds the table, the header and the library to each other, tests/test_gpu_attr_train.py runs every entry that takes outputs or scratch in guard zones (the in-place hand-off on a poisoned table).
+_STEP_ROWS = [_vp, _i64, _i32, _vp, _vp, _i64, _i64]          # X, ld, d, rows, counts, cap1, cap2
+_ATTR_TRAIN_PROTOTYPES = {
+    'ure_attr_step_masks': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    'ure_attr_select_scratch': (_i64, [_i64]),
+    'ure_attr_select': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'ure_attr_scratch': (_i64, [_i64, _i32]),
+    'ure_attr_bandwidth': (ctypes.c_int, _STEP_ROWS + [_f64, _vp, _vp, _vp, _i64, _vp]),
+    'ure_attr_mmd_loss_grad': (ctypes.c_int, _STEP_ROWS + [_f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'ure_attr_u2u_loss_grad': (ctypes.c_int, _STEP_ROWS + [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'ure_attr_add_grad': (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, ctypes.c_float, _vp]),
+}
+ATTR_TRAIN_EXPORTS = tuple(_ATTR_TRAIN_PROTOTYPES)
+
 _lib = None
 
 
@@ -268,7 +283,7 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES,
-                                  **_COMBINE_RANK_PROTOTYPES}.items():
+                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -14,6 +14,9 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
                                              artifacts under LightGCN_bpr_*)
   +   InsParam(..., unlearn='retrain')       optional unlearning route of runGroup ('influence': Sisa.unlearn_influence, Newton steps on the
                                              affected shards instead of retraining them; model='mf' with loss='mse' only)
+  +   InsParam(..., dis_type='nor', attr=[], dis_eta=1.0) optional in-training attribute unlearning ('d2d' / 'u2u': the per-batch MMD /
+                                             Laplacian term over the user groups attr = (id1, id2), ultrare_amd/attr_train.py; needs
+                                             model='lightgcn', gcn_layers=0 being plain MF; artifacts under LightGCN_<dis_type>_*)
   +   dataset 'toy' is usable end to end     (the reference only has its batch size)
 """
 import os
@@ -38,9 +41,15 @@ DATASETS = {
 
 class InsParam(object):
     def __init__(self, dataset='toy', epochs=50, n_worker=24, layers=[32], n_group=2, del_per=2, del_type='test',
-                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2, loss='mse', unlearn='retrain'):
+                 k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2, loss='mse', unlearn='retrain',
+                 dis_type='nor', attr=[], dis_eta=1.0):
         if unlearn not in ('retrain', 'influence'):
             raise ValueError(f"unlearn {unlearn!r}: 'retrain' or 'influence'")
+        from .attr_train import DIS_TYPES
+        if dis_type not in DIS_TYPES:
+            raise ValueError(f"dis_type {dis_type!r}: one of {DIS_TYPES}")
+        if unlearn == 'influence' and dis_type != 'nor':
+            raise ValueError(f"unlearn='influence' takes Newton steps on the plain MSE objective: dis_type={dis_type!r} is not supported with it")
         if unlearn == 'influence':
             from .influence import check_model
             check_model(model, loss)
@@ -87,6 +96,18 @@ class InsParam(object):
         self.model = model                      # the backbone: 'mf', 'lightgcn' (ultrare_amd/lightgcn.py) or 'nmf' (ultrare_amd/nmf.py)
         self.gcn_layers = check_layers(gcn_layers)   # propagations per side of the 'lightgcn' backbone (`layers` above is the 'nmf' backbone's stack)
 
+        if dis_type != 'nor':                   # the per-batch attribute term (ultrare_amd/attr_train.py); the groups are checked below
+            from .attr_train import check_eta, check_k
+            if model == 'mf':
+                raise NotImplementedError(f"dis_type={dis_type!r} trains with model='lightgcn' only (utils.py:66-81 reads a table the MF model "
+                                          "does not have): --model lightgcn --gcn-layers 0 is plain MF with the term")
+            if model == 'nmf':
+                raise ValueError(f"dis_type={dis_type!r} trains with model='lightgcn' only, not model='nmf'")
+            check_k(k)
+            self.dis_eta = check_eta(dis_eta)   # (set only off the default: the saved param of a plain run keeps its bytes)
+        elif len(attr):
+            raise ValueError("attr goes with dis_type 'd2d' or 'u2u': dis_type='nor' trains without it")
+
         # dataset-varied param
         self.del_rating = []  # 2d array/list [[uid, iid], ...]
         self.dataset = dataset
@@ -106,6 +127,12 @@ class InsParam(object):
                 self.del_user = np.random.choice(self.n_user, n_del, replace=False)
         else:
             raise ValueError(f'unknown dataset {dataset!r}; known: {sorted(DATASETS)}')
+        if dis_type != 'nor':
+            from .attr_unlearn import check_groups
+            if len(attr) != 2:
+                raise ValueError(f"dis_type={dis_type!r} needs attr = (id1, id2), two groups of user ids")
+            rows, n1, _ = check_groups(attr[0], attr[1], self.n_user)
+            self.dis_type, self.attr = dis_type, [rows[:n1].tolist(), rows[n1:].tolist()]
 
     def info(self):
         print(self.dataset, '-----------')
@@ -239,7 +266,9 @@ class Instance(object):
         """(model_type, artifact prefix) of the backbone the parameters name."""
         model = getattr(self.param, 'model', 'mf')
         prefix = {'mf': 'MF_', 'lightgcn': 'LightGCN_', 'nmf': 'NMF_'}[model]
-        return model, prefix + ('bpr_' if getattr(self.param, 'loss', 'mse') == 'bpr' else '')
+        prefix += 'bpr_' if getattr(self.param, 'loss', 'mse') == 'bpr' else ''
+        dis_type = getattr(self.param, 'dis_type', 'nor')
+        return model, prefix + (dis_type + '_' if dis_type != 'nor' else '')
 
     def runFull(self, is_save=True, verbose=1):
         '''model MF (or the backbone of param.model)'''

@@ -2187,6 +2187,171 @@ def bpr_loss_grad(graph, tag, step, U, V, neg, index=None, coef=None, stream=Non
     return Gu, Gi, loss, w, x, sp, sn
 
 
+# ---- in-training attribute unlearning (csrc/attr_train.hip, include/ultrare_attr_train.h; the contract is attr_train.py) ----------
+class StepGroups:
+    """Two attribute groups of a shard's users for the per-batch term: group_of_user int8 [n_user] on the device (0, 1, 2) and the
+    capacities cap1, cap2 -- the groups' sizes among the users WITH entries, which bound every step's counts.  Checked once on the
+    host (attr_unlearn.check_groups); cap1 or cap2 may be 0 here (a shard without one group), which the callers decide about."""
+
+    def __init__(self, graph, id1, id2):
+        from .attr_unlearn import check_groups
+        rows, n1, _ = check_groups(id1, id2, graph.n_user)
+        self.graph, self.n_user, self.device = graph, graph.n_user, graph.device
+        self.host = np.zeros(graph.n_user, dtype=np.int8)
+        self.host[rows[:n1]], self.host[rows[n1:]] = 1, 2
+        has = np.diff(graph.host.off_u) > 0
+        self.cap1, self.cap2 = int((has & (self.host == 1)).sum()), int((has & (self.host == 2)).sum())
+        self.group = to_device_async(self.host, self.device)
+
+    @property
+    def cap(self):
+        return self.cap1 + self.cap2
+
+
+def _attr_caps(cap1, cap2, who):
+    cap1, cap2 = int(cap1), int(cap2)
+    if cap1 < 1 or cap2 < 1:
+        raise ValueError(f'{who}: both capacities must be at least 1, not {cap1} and {cap2}')
+    return cap1, cap2
+
+
+def _attr_words(steps):
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError(f'steps must be positive, not {steps}')
+    return steps, (steps + 31) // 32
+
+
+def _attr_masks(graph, tag, group, steps, masks, st):
+    nv.check(nv.lib().ure_attr_step_masks(nv.ptr(graph.off_u), nv.ptr(tag), nv.ptr(group), graph.n_user, graph.nnz, steps, nv.ptr(masks), st),
+             'ure_attr_step_masks')
+
+
+def attr_step_masks(graph, tag, group, steps, stream=None):
+    """ure_attr_step_masks: per user of the GcnGraph a bitset over an epoch's steps, uint32 [n_user, ceil(steps / 32)] (returned as
+    int32 bit patterns) -- bit s set iff the user is in a group (group: int8 [n_user] device tensor, 0 / 1 / 2) and has a CSR entry
+    with tag == s (tag: gcn_step_tags).  Nothing synchronises."""
+    steps, words = _attr_words(steps)
+    _bpr_int_vector(tag, graph, 'tag')
+    if not (torch.is_tensor(group) and group.is_cuda and group.dtype == torch.int8 and group.shape == (graph.n_user,) and group.device == graph.device):
+        raise ValueError(f'group must be an int8 [{graph.n_user}] tensor on {graph.device}')
+    masks = torch.empty(graph.n_user, words, dtype=torch.int32, device=graph.device)
+    _attr_masks(graph, tag, group, steps, masks, nv.stream_handle(stream))
+    _csr_held_for(stream, masks)
+    return masks
+
+
+def _attr_select(masks, group, n_user, steps, step, cap1, cap2, rows, counts, scratch, st):
+    nv.check(nv.lib().ure_attr_select(nv.ptr(masks), nv.ptr(group), n_user, steps, int(step), cap1, cap2, nv.ptr(rows), nv.ptr(counts), nv.ptr(scratch),
+                                      scratch.numel(), st), 'ure_attr_select')
+
+
+def attr_select(masks, group, steps, step, cap1, cap2, stream=None):
+    """ure_attr_select: the step's rows, an ordered compaction of attr_step_masks -- (rows int32 [cap1 + cap2], counts int32 [2]) on the
+    device, equal to attr_train.batch_groups_ref integer for integer (-1 behind the selected rows).  Nothing synchronises."""
+    steps, words = _attr_words(steps)
+    cap1, cap2 = _attr_caps(cap1, cap2, 'attr_select')
+    if not (torch.is_tensor(masks) and masks.is_cuda and masks.dtype == torch.int32 and masks.dim() == 2 and masks.shape[1] == words and masks.is_contiguous()):
+        raise ValueError(f'masks must be a contiguous int32 [n_user, {words}] device tensor (attr_step_masks)')
+    n_user = int(masks.shape[0])
+    if not (torch.is_tensor(group) and group.dtype == torch.int8 and group.shape == (n_user,) and group.device == masks.device):
+        raise ValueError(f'group must be an int8 [{n_user}] tensor on {masks.device}')
+    if not 0 <= int(step) < steps:
+        raise ValueError(f'step {step} outside 0 .. {steps - 1}')
+    dev = masks.device
+    rows = torch.empty(cap1 + cap2, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(nv.lib().ure_attr_select_scratch(n_user)), dtype=torch.uint8, device=dev)
+    _attr_select(masks, group, n_user, steps, step, cap1, cap2, rows, counts, scratch, nv.stream_handle(stream))
+    _csr_held_for(stream, rows, counts, scratch)
+    return rows, counts
+
+
+def _attr_step_table(X, rows, counts, cap1, cap2, what):
+    from .attr_unlearn import check_width
+    cap1, cap2 = _attr_caps(cap1, cap2, what)
+    if not (torch.is_tensor(X) and X.is_cuda):
+        raise nv.NativeError(f'{what} runs on the HIP device only (no CPU fallback)')
+    if not (X.dtype == torch.float32 and X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]):
+        raise ValueError(f'{what}: X must be a float32 [rows, d] device tensor with unit column stride, not {tuple(X.shape)} {X.dtype}')
+    if not (torch.is_tensor(rows) and rows.dtype == torch.int32 and rows.shape == (cap1 + cap2,) and rows.device == X.device and rows.is_contiguous()):
+        raise ValueError(f'{what}: rows must be a contiguous int32 [{cap1 + cap2}] tensor on {X.device}')
+    if not (torch.is_tensor(counts) and counts.dtype == torch.int32 and counts.shape == (2,) and counts.device == X.device):
+        raise ValueError(f'{what}: counts must be an int32 [2] tensor on {X.device}')
+    d = check_width(X.shape[1], X.stride(0))
+    nbytes = int(nv.lib().ure_attr_scratch(cap1 + cap2, d))
+    if nbytes < 0:
+        raise ValueError(f'ure_attr_scratch refused cap = {cap1 + cap2}, d = {d}')
+    return cap1, cap2, d, int(X.stride(0)), nbytes
+
+
+def _attr_acc(t, dtype, what, dev):
+    if t is not None and not (torch.is_tensor(t) and t.dtype == dtype and t.numel() == 1 and t.device == dev):
+        raise ValueError(f'{what} must be a {dtype} device tensor of one value on {dev}')
+    return t
+
+
+def mmd_loss_grad_dev(X, rows, counts, cap1, cap2, kernel_mul=2.0, kernel_num=5, fix_sigma=None, acc=None, skipped=None, stream=None):
+    """ure_attr_mmd_loss_grad: mmd_bandwidth + mmd_loss_grad at counts that live on the device (rows, counts: attr_select) ->
+    (sums float64 [4], grad float32 [cap1 + cap2, d], valid int32 [1], bandwidth float64 0-d), all on the device; the loss is added
+    to acc (float64 device tensor of one value) when the step is valid, skipped (int32) is advanced when it is not.  Nothing
+    synchronises."""
+    from .attr_unlearn import check_mmd_args
+    kernel_mul, kernel_num, fix_sigma = check_mmd_args(kernel_mul, kernel_num, fix_sigma)
+    cap1, cap2, d, ld, nbytes = _attr_step_table(X, rows, counts, cap1, cap2, 'mmd_loss_grad_dev')
+    dev = X.device
+    _attr_acc(acc, torch.float64, 'acc', dev)
+    _attr_acc(skipped, torch.int32, 'skipped', dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sums, bw = torch.empty(4, dtype=torch.float64, device=dev), torch.empty((), dtype=torch.float64, device=dev)
+    grad, valid = torch.empty(cap1 + cap2, d, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_attr_mmd_loss_grad(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(counts), cap1, cap2, kernel_mul, kernel_num, fix_sigma or 0.0,
+                                             bw.data_ptr(), nv.ptr(sums), nv.ptr(grad), nv.ptr(valid), nv.ptr(acc), nv.ptr(skipped), nv.ptr(scratch), nbytes,
+                                             nv.stream_handle(stream)), 'ure_attr_mmd_loss_grad')
+    _csr_held_for(stream, scratch, sums, bw, grad, valid)
+    return sums, grad, valid, bw
+
+
+def u2u_loss_grad_dev(X, rows, counts, cap1, cap2, acc=None, skipped=None, stream=None):
+    """ure_attr_u2u_loss_grad: u2u_loss_grad at device counts -> (value float64 0-d, grad float32 [cap1 + cap2, d], valid int32 [1]) on
+    the device; acc and skipped as mmd_loss_grad_dev's.  Nothing synchronises."""
+    cap1, cap2, d, ld, nbytes = _attr_step_table(X, rows, counts, cap1, cap2, 'u2u_loss_grad_dev')
+    dev = X.device
+    _attr_acc(acc, torch.float64, 'acc', dev)
+    _attr_acc(skipped, torch.int32, 'skipped', dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    value = torch.empty((), dtype=torch.float64, device=dev)
+    grad, valid = torch.empty(cap1 + cap2, d, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_attr_u2u_loss_grad(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(counts), cap1, cap2, value.data_ptr(), nv.ptr(grad), nv.ptr(valid),
+                                             nv.ptr(acc), nv.ptr(skipped), nv.ptr(scratch), nbytes, nv.stream_handle(stream)), 'ure_attr_u2u_loss_grad')
+    _csr_held_for(stream, scratch, value, grad, valid)
+    return value, grad, valid
+
+
+def _attr_add(G, ld, n_rows, d, rows, counts, cap, valid, grad, eta, st):
+    nv.check(nv.lib().ure_attr_add_grad(nv.ptr(G), ld, n_rows, d, nv.ptr(rows), nv.ptr(counts), cap, nv.ptr(valid), nv.ptr(grad), float(np.float32(eta)), st),
+             'ure_attr_add_grad')
+
+
+def attr_add_grad(G, rows, counts, valid, grad, eta, stream=None):
+    """ure_attr_add_grad, in place: G[rows[i]][c] = fl(G[rows[i]][c] + fl(eta grad[i][c])) for i < counts[0] + counts[1] and only when
+    valid; every other byte of G (float32 [n_rows, >= d], unit column stride) keeps its value.  Nothing synchronises."""
+    from .attr_train import check_eta
+    eta = check_eta(eta)
+    for t in (G, grad):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise nv.NativeError('attr_add_grad runs on the HIP device only (no CPU fallback)')
+    cap, d = int(grad.shape[0]), int(grad.shape[1])
+    if not (grad.dtype == torch.float32 and grad.is_contiguous() and G.dtype == torch.float32 and G.dim() == 2 and G.stride(1) == 1 and G.shape[1] >= d
+            and G.stride(0) >= G.shape[1]):
+        raise ValueError('G must be a float32 [n_rows, >= d] tensor with unit column stride and grad a contiguous float32 [cap, d] tensor')
+    if not (rows.dtype == torch.int32 and rows.shape == (cap,) and counts.dtype == torch.int32 and counts.shape == (2,) and valid.dtype == torch.int32
+            and valid.numel() == 1 and rows.device == counts.device == valid.device == grad.device == G.device):
+        raise ValueError(f'rows int32 [{cap}], counts int32 [2] and valid int32 [1] must lie on {G.device}')
+    _attr_add(G, int(G.stride(0)), int(G.shape[0]), d, rows, counts, cap, valid, grad, eta, nv.stream_handle(stream))
+    return G
+
+
 class _GraphJob:
     """What the trainers over a GcnGraph share (GcnJob, NmfJob): the checks of batch, epochs and orders, the float32 schedule and
     scalars, the epoch bookkeeping, and the three launches a step of either makes beside its own -- the gather of the epoch's table
@@ -2268,16 +2433,32 @@ class GcnJob(_GraphJob):
     loss instead: the negatives (under `key`, bpr.stream_key) and their index are made on the device at each epoch's first step,
     and the coefficient pass and the two BPR walks stand where the residual pass and the masked walks stand.
 
+    attr=(id1, id2) with dis_type 'd2d' / 'u2u' (attr_train.train_ref) adds eta times the MMD / Laplacian term over the
+    batch's distinct users of the two groups to every step: the step masks are made at each epoch's first step, and the selection, the
+    loss at device counts and the hand-off into the user gradient stand between the loss fold and the backward propagations.  The
+    kernels of that term are held to bounds, not bits.  Without attr the job makes exactly the launches it made before.
+
     graph  : GcnGraph
     init   : (P0 [n_user, k], Q0 [n_item, k]) float32 numpy arrays or tensors
     orders : int32 [epochs, N] -- per epoch the file positions in training order (batch t = orders[e][t B : (t + 1) B])"""
 
     _TABLES = ('W', 'M', 'G', 'S', 'Xa', 'Xb', 'Star')
 
-    def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50, loss='mse', key=0):
-        from . import lightgcn
+    def __init__(self, graph, init, orders, k, layers, batch, epochs, lr, lam, momentum, lr_decay=1.0, lr_step=50, loss='mse', key=0, attr=None,
+                 dis_type='nor', eta=1.0, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
+        from . import attr_train, lightgcn
         if loss not in ('mse', 'bpr'):
             raise ValueError(f"loss {loss!r}: 'mse' or 'bpr'")
+        if dis_type not in attr_train.DIS_TYPES:
+            raise ValueError(f"dis_type {dis_type!r}: one of {attr_train.DIS_TYPES}")
+        if (attr is None) != (dis_type == 'nor'):
+            raise ValueError("attr=(id1, id2) goes with dis_type 'd2d' or 'u2u', attr=None with 'nor'")
+        self.dis_type, self._attr = dis_type, None
+        if attr is not None:
+            if len(attr) != 2:
+                raise ValueError('attr must be the pair (id1, id2)')
+            _, _, self.eta, self._kernel_mul, self._kernel_num, self._fix_sigma = attr_train.check_train_args(
+                graph.n_user, k, attr[0], attr[1], dis_type, eta, kernel_mul, kernel_num, fix_sigma)
         if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= key < 2 ** 64:
             raise ValueError(f'key must be an integer in 0 .. 2^64 - 1, not {key!r}')
         self.loss, self.key = loss, int(key)
@@ -2310,6 +2491,41 @@ class GcnJob(_GraphJob):
                              w=torch.zeros(graph.nnz, dtype=torch.float32, device=dev),
                              scratch=torch.zeros(int(nv.lib().ure_bpr_index_scratch(graph.nnz, graph.n_item)), dtype=torch.uint8, device=dev))
         self._star_at = -1       # the step count Star belongs to
+        if attr is not None:
+            self._attr_buffers(StepGroups(graph, *attr))
+
+    def _attr_buffers(self, groups):
+        """The per-batch term's device memory: the step masks of one epoch, a step's rows, counts, gradient and validity word, the
+        scratch of the loss entries (planned from the capacities), and per epoch the summed loss values and the skipped steps."""
+        if groups.cap1 < 1 or groups.cap2 < 1:
+            raise ValueError(f'the shard has {groups.cap1} users of group 1 and {groups.cap2} of group 2 with entries: both groups need one '
+                             "(train such a shard with dis_type='nor')")
+        dev, L, E = self.device, nv.lib(), max(self.epochs, 1)
+        nbytes = int(L.ure_attr_scratch(groups.cap, self.k))
+        if nbytes < 0:
+            raise ValueError(f'ure_attr_scratch refused cap = {groups.cap}, d = {self.k}')
+        a = dict(groups=groups, masks=torch.zeros(self.graph.n_user, (self.steps + 31) // 32, dtype=torch.int32, device=dev),
+                 rows=torch.zeros(groups.cap, dtype=torch.int32, device=dev), counts=torch.zeros(2, dtype=torch.int32, device=dev),
+                 grad=torch.zeros(groups.cap, self.k, dtype=torch.float32, device=dev), valid=torch.zeros(1, dtype=torch.int32, device=dev),
+                 out=torch.zeros(4, dtype=torch.float64, device=dev), scratch=torch.zeros(nbytes, dtype=torch.uint8, device=dev),
+                 sel=torch.zeros(int(L.ure_attr_select_scratch(self.graph.n_user)), dtype=torch.uint8, device=dev),
+                 dis=torch.zeros(E, dtype=torch.float64, device=dev), skipped=torch.zeros(E, dtype=torch.int32, device=dev))
+        self._attr = a
+
+    def _attr_term(self, e, s, U, Gu, st):
+        """Gu[rows] += eta g of the step's MMD / u2u term on U[rows]: the selection, the loss at device counts, the hand-off."""
+        a, g, L = self._attr, self._attr['groups'], nv.lib()
+        if s == 0:
+            _attr_masks(self.graph, self._tag, g.group, self.steps, a['masks'], st)
+        _attr_select(a['masks'], g.group, self.graph.n_user, self.steps, s, g.cap1, g.cap2, a['rows'], a['counts'], a['sel'], st)
+        front = (U.data_ptr(), self.d, self.k, nv.ptr(a['rows']), nv.ptr(a['counts']), g.cap1, g.cap2)
+        back = (nv.ptr(a['grad']), nv.ptr(a['valid']), a['dis'][e:].data_ptr(), a['skipped'][e:].data_ptr(), nv.ptr(a['scratch']), a['scratch'].numel(), st)
+        if self.dis_type == 'd2d':
+            nv.check(L.ure_attr_mmd_loss_grad(*front, self._kernel_mul, self._kernel_num, self._fix_sigma or 0.0, None, nv.ptr(a['out']), *back),
+                     'ure_attr_mmd_loss_grad')
+        else:
+            nv.check(L.ure_attr_u2u_loss_grad(*front, nv.ptr(a['out']), *back), 'ure_attr_u2u_loss_grad')
+        _attr_add(Gu, self.d, self.graph.n_user, self.k, a['rows'], a['counts'], g.cap, a['valid'], a['grad'], self.eta, st)
 
     # ---- launches ------------------------------------------------------------------------------------------------------
     def _sides(self, t):
@@ -2361,6 +2577,8 @@ class GcnJob(_GraphJob):
         else:
             _gcn_mse_walks(g, self._tag, s, U, V, self.d, self._err, None, Gu, Gi, self._row_loss, st)
         self._fold_loss(e, s, st)
+        if self._attr is not None:
+            self._attr_term(e, s, U, Gu, st)
         src = t['G']
         for l in range(self.layers):                        # Horner: H^l = G + A H^(l-1)
             dst = t['Xa'] if l % 2 == 0 else t['Xb']
@@ -2395,8 +2613,23 @@ class GcnJob(_GraphJob):
         """Per-epoch sum of the steps' batch losses, whatever the loss (host float64 array; synchronises)."""
         return super().epoch_sse(s)
 
+    def _attr_log(self, name):
+        if self._attr is None:
+            raise ValueError("the job trains without the attribute term (dis_type='nor')")
+        return self._attr[name][:self.epochs].cpu().numpy()
+
+    def epoch_dis(self, s=0):
+        """Per epoch the sum of the applied steps' MMD / u2u values, before eta (host float64 array; synchronises)."""
+        assert s == 0
+        return self._attr_log('dis')
+
+    def epoch_skipped(self, s=0):
+        """Per epoch the steps whose term was skipped: a group absent from the batch, or no usable bandwidth (host array; synchronises)."""
+        assert s == 0
+        return self._attr_log('skipped').astype(np.int64)
+
     def close(self):
-        self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = self._bpr = None
+        self._pool = self._t = self._file_tags = self._tag = self._err = self._row_loss = self._sse = self._bpr = self._attr = None
 
 
 # ---------------------------------------------------------------------------

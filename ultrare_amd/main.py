@@ -58,6 +58,9 @@ parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn'
 parser.add_argument('--gcn-layers', type=int, default=2, help="propagations per side of the 'lightgcn' backbone (0 .. 8)")
 parser.add_argument('--loss', type=str, default='mse', choices=['mse', 'bpr'], help="'mse' (reference) or 'bpr' (needs --model lightgcn)")
 parser.add_argument('--unlearn', type=str, default='retrain', choices=['retrain', 'influence'], help="'retrain' (reference) or 'influence' (Newton steps, no retraining; --model mf --loss mse)")
+parser.add_argument('--dis-type', type=str, default='nor', choices=['nor', 'd2d', 'u2u'], help="'nor' (plain loss), or the per-batch attribute term 'd2d' (MMD) / 'u2u' (Laplacian); needs --attr-file and --model lightgcn (--gcn-layers 0 is plain MF)")
+parser.add_argument('--attr-file', type=str, default=None, help="an .npz with id1 and id2: the global user ids of the two attribute groups of --dis-type")
+parser.add_argument('--dis-eta', type=float, default=1.0, help='weight of the --dis-type term')
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -68,6 +71,21 @@ def layer_ints(layer):
         return [int(i) for i in layer]
     except ValueError:
         raise ValueError(f'--layer takes integers, not {layer!r}') from None
+
+
+def attr_groups(dis_type, attr_file):
+    """--attr-file as InsParam's attr: [] under 'nor' (a file is then refused), else [id1, id2] of the .npz."""
+    import numpy as np
+    if dis_type == 'nor':
+        if attr_file is not None:
+            raise ValueError("--attr-file goes with --dis-type d2d or u2u")
+        return []
+    if attr_file is None:
+        raise ValueError(f'--dis-type {dis_type} needs --attr-file (an .npz with id1 and id2)')
+    with np.load(attr_file) as z:
+        if 'id1' not in z.files or 'id2' not in z.files:
+            raise ValueError(f'{attr_file} must hold the arrays id1 and id2, not {sorted(z.files)}')
+        return [z['id1'], z['id2']]
 
 
 def main(argv=None):
@@ -106,7 +124,8 @@ def main(argv=None):
     torch.manual_seed(42)   # the reference never seeds the CPU generator; a fixed run needs it
     param = InsParam(args.dataset, args.epoch, args.worker, args.layer, args.group, args.delper, args.deltype,
                      k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr,
-                     model=args.model, gcn_layers=args.gcn_layers, loss=args.loss, unlearn=args.unlearn)
+                     model=args.model, gcn_layers=args.gcn_layers, loss=args.loss, unlearn=args.unlearn,
+                     dis_type=args.dis_type, attr=attr_groups(args.dis_type, args.attr_file), dis_eta=args.dis_eta)
     ins = Instance(param, save_dir=args.save_dir)
 
     if args.group == 0:

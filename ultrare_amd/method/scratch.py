@@ -101,11 +101,10 @@ class Scratch(object):
         self.betas = tuple(getattr(param, 'betas', (0.9, 0.999)))
         self.eps = getattr(param, 'eps', 1e-8)
         self.device = 'cuda'
-        # InsParam never sets dis_type / attr; 'nor' is the only branch that
-        # works with MF (utils.py:64-65)
+        # the reference's InsParam never sets dis_type / attr.  'nor' is the plain loss; 'd2d' / 'u2u' add the per-batch
+        # MMD / Laplacian term of utils.py:66-81 over the attribute groups attr = (id1, id2) (ultrare_amd/attr_train.py), on the
+        # 'lightgcn' backbone (gcn_layers = 0 is plain MF); checked below, once the backbone is known
         self.dis_type = getattr(param, 'dis_type', 'nor')
-        if self.dis_type != 'nor':
-            raise NotImplementedError("only dis_type='nor' exists for the MF model (utils.py:66-81 needs a non-MF model)")
         self.attr = []
 
         # log (one dict per object, appended by every shard it trains)
@@ -141,8 +140,29 @@ class Scratch(object):
             raise ValueError(f"loss {self.loss!r}: 'mse' or 'bpr'")
         if self.loss == 'bpr' and self.model_type != 'lightgcn':
             raise ValueError("loss='bpr' trains with model='lightgcn' only: --model lightgcn --gcn-layers 0 is BPR-MF")
+        self._check_dis_type(param)
         self.loss_fn = nn.MSELoss(reduction='sum')
         self.is_rmse = True
+
+    def _check_dis_type(self, param):
+        from ..attr_train import DIS_TYPES, check_eta, check_k
+        from ..attr_unlearn import check_groups
+        if self.dis_type not in DIS_TYPES:
+            raise ValueError(f"dis_type {self.dis_type!r}: one of {DIS_TYPES}")
+        if self.dis_type == 'nor':
+            return
+        if self.model_type == 'mf':
+            raise NotImplementedError(f"dis_type={self.dis_type!r} trains with model='lightgcn' only (utils.py:66-81 reads a table the MF model "
+                                      "does not have): --model lightgcn --gcn-layers 0 is plain MF with the term")
+        if self.model_type == 'nmf':
+            raise ValueError(f"dis_type={self.dis_type!r} trains with model='lightgcn' only, not the 'nmf' backbone")
+        attr = getattr(param, 'attr', [])
+        if len(attr) != 2:
+            raise ValueError(f"dis_type={self.dis_type!r} needs attr = (id1, id2), two groups of user ids")
+        rows, n1, _ = check_groups(attr[0], attr[1], self.n_user)
+        check_k(self.k)
+        self.attr = (rows[:n1].astype(np.int64), rows[n1:].astype(np.int64))
+        self.dis_eta = check_eta(getattr(param, 'dis_eta', 1.0))
 
     def _optimizer_args(self):
         """What a TrainJob of this object takes beyond the reference's parameters."""
@@ -289,9 +309,10 @@ class Scratch(object):
     def _train_loss(self, job, n_train):
         """The train_loss series of a job: sqrt(sse / N) (utils.py:101-103), or under BPR the reference's is_rmse == False
         reporting, loss_sum / N (utils.py:104-106)."""
+        dis = self.dis_eta * job.epoch_dis() if getattr(job, 'dis_type', 'nor') != 'nor' else 0.0      # utils.py:78-82: the term is part of the loss
         if self.loss == 'bpr':
-            return job.epoch_loss(0) / n_train
-        return np.sqrt(job.epoch_sse(0) / n_train)
+            return (job.epoch_loss(0) + dis) / n_train
+        return np.sqrt(np.maximum(job.epoch_sse(0) + dis, 0.0) / n_train)
 
     def _gcn_job(self, train_data, has_total, given_model, id=0):
         """prepare_shard and the job of a LightGCN request: the RNG stream is the MF request's (rng.mf_init, then the epochs' seeds),
@@ -309,6 +330,14 @@ class Scratch(object):
         if self.loss == 'bpr':
             from ..bpr import stream_key
             extra = dict(loss='bpr', key=stream_key(self.seed, id))
+        if self.dis_type != 'nor':
+            groups = engine.StepGroups(graph, *self.attr)
+            if groups.cap1 < 1 or groups.cap2 < 1:          # (a SISA shard may hold one group only)
+                import warnings
+                warnings.warn(f"shard {id}: {groups.cap1} users of group 1 and {groups.cap2} of group 2 have ratings here: dis_type={self.dis_type!r} "
+                              "needs both, so this shard trains as dis_type='nor' does")
+            else:
+                extra.update(attr=self.attr, dis_type=self.dis_type, eta=self.dis_eta)
         return engine.GcnJob(graph, init, orders, self.k, self.gcn_layers, loader.batch_size, self.epochs, self.lr, self.lam, self.momentum,
                              self.lr_decay, **extra)
 

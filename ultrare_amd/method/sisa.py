@@ -755,6 +755,8 @@ class Sisa(Scratch):
         refused before any device work.  unlearn itself is untouched and may follow.
         '''
         from ..influence import check_model
+        if getattr(self, 'dis_type', 'nor') != 'nor':
+            raise ValueError(f"unlearn_influence takes Newton steps on the plain MSE objective: dis_type={self.dis_type!r} is not supported with it")
         check_model(self.model_type, getattr(self, 'loss', 'mse'))
         dist = _dist()
         if dist is not None and dist.get_world_size() > 1:

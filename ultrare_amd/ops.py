@@ -45,6 +45,9 @@ to resident shards -- and stays behind engine.TrainJob.
     torch.ops.ultrare.gcn_propagate(off, idx, s_src, s_dst, X, add)
                                                         (new)             one LightGCN propagation over a device CSR / CSC:
                                                                           out[r] = [add[r] +] s_dst[r] sum_j s_src[j] X[j]
+    torch.ops.ultrare.attr_select(masks, group, steps, step, cap1, cap2)
+                                                        (new)             (rows, counts): a step's users of two attribute groups, an
+                                                                          ordered compaction on the device (ultrare_amd/attr_train.py)
     torch.ops.ultrare.bpr_negatives(off_d, col_d, row_u, pos, n_item, key, epoch)
                                                         (new)             neg [nnz]: one epoch's BPR negatives, uniform over the
                                                                           items a CSR entry's user has none of (ultrare_amd/bpr.py)
@@ -445,6 +448,19 @@ def gcn_propagate(off: torch.Tensor, idx: torch.Tensor, s_src: torch.Tensor, s_d
 @gcn_propagate.register_fake
 def _(off, idx, s_src, s_dst, X, add=None):
     return X.new_empty(off.numel() - 1, X.shape[1])
+
+
+@torch.library.custom_op('ultrare::attr_select', mutates_args=())
+def attr_select(masks: torch.Tensor, group: torch.Tensor, steps: int, step: int, cap1: int, cap2: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """engine.attr_select: the rows of one step of in-training attribute unlearning from the per-user step masks
+    (engine.attr_step_masks: int32 [n_user, ceil(steps / 32)]) and group int8 [n_user] -> (rows int32 [cap1 + cap2], counts int32 [2])."""
+    _dev(masks, group)
+    return engine.attr_select(masks.contiguous(), group.contiguous(), steps, step, cap1, cap2)
+
+
+@attr_select.register_fake
+def _(masks, group, steps, step, cap1, cap2):
+    return masks.new_empty(cap1 + cap2, dtype=torch.int32), masks.new_empty(2, dtype=torch.int32)
 
 
 @torch.library.custom_op('ultrare::bpr_negatives', mutates_args=())
