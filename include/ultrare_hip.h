@@ -791,5 +791,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_combine_rank.h"
 /* In-training attribute unlearning (csrc/attr_train.hip): a step's rows selected on the device, the MMD / u2u losses at device counts. */
 #include "ultrare_attr_train.h"
+/* The attribute-inference attacker (csrc/attack.hip): a cross-validated MLP probe on selected rows, exact AUC pair counts. */
+#include "ultrare_attack.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -267,6 +267,21 @@ _ATTR_TRAIN_PROTOTYPES = {
 }
 ATTR_TRAIN_EXPORTS = tuple(_ATTR_TRAIN_PROTOTYPES)
 
+# include/ultrare_attack.h (the attribute-inference attacker, csrc/attack.hip): a table of its own, as the header is;
+# tests/test_cpu_attack.py holds the table, the header and the library to each other, tests/test_gpu_attack.py runs every entry that takes outputs or scratch in guard zones.
+_f32 = ctypes.c_float
+_PROBE_ROWS = [_vp, _i64, _i32, _vp, _vp, _i64]               # X, ld, d, rows, fold_of, m
+_ATTACK_PROTOTYPES = {
+    'ure_attack_scratch': (_i64, [_i64, _i32, _i32, _i32]),
+    'ure_attack_standardize': (ctypes.c_int, _PROBE_ROWS + [_i32, _vp, _vp]),
+    'ure_attack_train': (ctypes.c_int, _PROBE_ROWS + [_i64, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'ure_attack_score': (ctypes.c_int, _PROBE_ROWS + [_i32, _i32, _vp, _vp, _vp, _vp]),
+    'ure_auc_scratch': (_i64, [_i64, _i64]),
+    'ure_auc_counts': (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'ure_confusion_counts': (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp]),
+}
+ATTACK_EXPORTS = tuple(_ATTACK_PROTOTYPES)
+
 _lib = None
 
 
@@ -283,7 +298,7 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES,
-                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES}.items():
+                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES, **_ATTACK_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

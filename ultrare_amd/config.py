@@ -185,6 +185,21 @@ class Instance(object):
         os.makedirs(save_dir, exist_ok=True)
         return save_dir
 
+    def _attack(self, run, save_dir, id=0):
+        """main.py --attack: self.attack = dict(id1, id2, hidden, folds), set by the caller after construction (it is no part of the
+        saved parameters).  The attribute-inference attacker (utils.attribute_attack) on the final user table of the stage: its AUC /
+        BAcc / F1 are printed and, with a save_dir, the dict is stored as attack<id>.npy beside log<id>.npy.  Without it nothing runs."""
+        a = getattr(self, 'attack', None)
+        if a is None:
+            return None
+        res = run(a)
+        print('attribute attacker (hidden %d, %d folds): AUC %.4f  BAcc %.4f  F1 %.4f' % (res['settings']['hidden'], res['settings']['folds'],
+                                                                                        res['auc'], res['bacc'], res['f1']))
+        if save_dir and dist_rank()[0] == 0:      # (every rank holds the merged models and computes the same dict; one writes it)
+            np.save(save_dir + '/attack' + str(id), res)
+        self.last_attack = res
+        return res
+
     # sub function of self.runFull (config.py:99-120)
     def _full(self, is_save, saving_name, model_type='mf', is_del=False, verbose=1):
         print(self.name, saving_name, 'begin:')
@@ -194,6 +209,7 @@ class Instance(object):
         save_dir = self._save_dir(is_save, saving_name)
         model = Scratch(self.param, model_type)
         trained = model.train(train_data, test_data, [], verbose, save_dir)
+        self._attack(lambda a: model.attribute_attack(trained, a['id1'], a['id2'], hidden=a['hidden'], folds=a['folds']), save_dir)
         print('End of training', self.name, saving_name)
         print()
         return trained
@@ -256,6 +272,7 @@ class Instance(object):
                 model.unlearn_influence(model_list, train_dlist, test_data, del_user, verbose, save_dir)
             else:
                 model.unlearn(model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir)
+        self._attack(lambda a: model.attribute_attack(a['id1'], a['id2'], hidden=a['hidden'], folds=a['folds']), save_dir)
         self.last = model
         return model.model_list
 

@@ -1848,6 +1848,14 @@ class GroupRows:
         self.rows = to_device_async(self.host, device or _device())
 
     @classmethod
+    def checked(cls, rows, n1, n2, n_rows, device):
+        """From what attr_unlearn.check_groups returned already (rows int32 [n1 + n2]): nothing is checked again."""
+        g = cls.__new__(cls)
+        g.host, g.n1, g.n2, g.n_rows = rows, int(n1), int(n2), int(n_rows)
+        g.rows = to_device_async(rows, device or _device())
+        return g
+
+    @classmethod
     def leading(cls, n1, n2, device):
         """Rows 0 .. n1 + n2 - 1 of a table that holds the source rows and then the target rows."""
         g = cls.__new__(cls)
@@ -1953,6 +1961,147 @@ def mmd_matrix(X, groups, bandwidth, kernel_mul=2.0, kernel_num=5, stream=None):
                                      nv.stream_handle(stream)), 'ure_mmd_matrix')
     _csr_held_for(stream, K)
     return K
+
+
+# ---------------------------------------------------------------------------
+# The attribute-inference attacker (csrc/attack.hip, include/ultrare_attack.h; the contract and the argument checks are attack.py)
+# ---------------------------------------------------------------------------
+class AttackFit:
+    """A cross-validated probe on the device: params float32 [folds, P], stats float32 [folds, 2, d], fold_of int32 [m], scores
+    float32 [m] (out of fold, by position of groups.rows), loss float64 [folds, epochs]; fold_host is fold_of on the host."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _attack_stream(stream):
+    """Uploads go on torch's current stream: a launch stream of the caller's waits for them."""
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+
+
+def attack_fit(X, groups, hidden=100, folds=5, epochs=None, lr=None, l2=1e-4, seed=0, stream=None, params0=None, fold_of=None):
+    """Fit the probe of attack.py on the rows of `groups` (class 1 = the first group) of the device table X, read in place:
+    ure_attack_standardize, ure_attack_train and ure_attack_score, back to back on one stream -> AttackFit.  The fold plan and the
+    initial parameters come from attack.fold_plan / attack.init_params under `seed` (params0, fold_of: given ones, for tests).
+    Nothing is read back and nothing synchronises."""
+    from . import adam, attack as A
+    d, ld = _attr_table(X, groups, 'attack_fit')
+    n1, n2, m = groups.n1, groups.n2, groups.m
+    H, folds, epochs, lr, l2 = A.check_settings(d, n1, n2, hidden, folds, epochs, lr, l2)
+    P = A.n_params(d, H)
+    fold_host = A.fold_plan(n1, n2, folds, seed) if fold_of is None else np.ascontiguousarray(fold_of, dtype=np.int32)
+    p0 = A.init_params(d, H, folds, seed) if params0 is None else np.ascontiguousarray(params0, dtype=np.float32)
+    if fold_host.shape != (m,) or p0.shape != (folds, P):
+        raise ValueError(f'fold_of must have shape ({m},) and params0 ({folds}, {P}), not {fold_host.shape} and {p0.shape}')
+    y = np.arange(m) < n1
+    fw = np.zeros((folds, 4), dtype=np.float32)
+    for f in range(folds):
+        cw, m_train = A.class_weights(y, fold_host != f)
+        fw[f, :2], fw[f, 2] = cw, m_train
+    if not np.isfinite(fw).all():
+        raise ValueError('a fold trains on one class only: the fold plan must leave both classes in every training part')
+    b1, b2, eps = adam.betas32(A.BETAS, A.EPS)
+    dev, L, st = X.device, nv.lib(), nv.stream_handle(stream)
+    nbytes = int(L.ure_attack_scratch(m, d, H, folds))
+    if nbytes < 0:
+        raise ValueError(f'ure_attack_scratch refused m = {m}, d = {d}, H = {H}, folds = {folds}')
+    fold_d, p0_d, fw_d, sc_d = (to_device_async(a, dev) for a in (fold_host, p0, fw, A.scalars(epochs, lr)))
+    _attack_stream(stream)
+    stats = torch.empty(folds, 2, d, dtype=torch.float32, device=dev)
+    params = torch.empty(folds, P, dtype=torch.float32, device=dev)
+    loss = torch.empty(folds, epochs, dtype=torch.float64, device=dev)
+    scores = torch.empty(m, dtype=torch.float32, device=dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rows = groups.rows
+    nv.check(L.ure_attack_standardize(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(fold_d), m, folds, nv.ptr(stats), st), 'ure_attack_standardize')
+    nv.check(L.ure_attack_train(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(fold_d), m, n1, folds, H, nv.ptr(stats), nv.ptr(fw_d), nv.ptr(sc_d), epochs,
+                                b1, b2, eps, float(np.float32(l2)), nv.ptr(p0_d), nv.ptr(params), nv.ptr(loss), nv.ptr(scratch), nbytes, st),
+             'ure_attack_train')
+    nv.check(L.ure_attack_score(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(fold_d), m, folds, H, nv.ptr(stats), nv.ptr(params), nv.ptr(scores), st),
+             'ure_attack_score')
+    _csr_held_for(stream, fold_d, p0_d, fw_d, sc_d, stats, params, loss, scores, scratch)
+    return AttackFit(params=params, stats=stats, fold_of=fold_d, fold_host=fold_host, scores=scores, loss=loss, d=d, hidden=H, folds=folds,
+                     epochs=epochs, lr=lr, l2=l2, seed=seed, n1=n1, n2=n2)
+
+
+def _index_list(idx, n, dev, name):
+    """An index list into n scores as an int32 device tensor; every entry is checked to lie in [0, n) (a device tensor: on the
+    device, which reads one flag back)."""
+    if torch.is_tensor(idx) and idx.is_cuda:
+        if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 1 or idx.numel() < 1:
+            raise ValueError(f'{name} must be a non-empty 1-d integer tensor')
+        if not bool(((idx >= 0) & (idx < n)).all()):
+            raise ValueError(f'{name} holds indices outside [0, {n})')
+        return idx.to(torch.int32).contiguous()
+    a = np.asarray(idx.cpu().numpy() if torch.is_tensor(idx) else idx).reshape(-1)
+    if a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f'{name} must be a non-empty list of integer indices')
+    if a.min() < 0 or a.max() >= n:
+        raise ValueError(f'{name} holds indices outside [0, {n})')
+    return to_device_async(a.astype(np.int32), dev)
+
+
+def _scores_arg(scores, what):
+    if not (torch.is_tensor(scores) and scores.is_cuda):
+        raise nv.NativeError(f'{what} runs on the HIP device only (no CPU fallback)')
+    if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous() or not 1 <= scores.numel() < 2 ** 31:
+        raise ValueError(f'{what}: scores must be a contiguous float32 [n] device tensor, not {tuple(scores.shape)} {scores.dtype}')
+    return scores
+
+
+def attack_scores(fit, X, rows, fold=0, stream=None):
+    """ure_attack_score with ONE parameter set of a fit (its fold `fold`: weights and statistics) on the rows `rows` of a device
+    table X -- fit on one table, score another -> float32 [len(rows)] on the device."""
+    if not (torch.is_tensor(X) and X.is_cuda):
+        raise nv.NativeError('attack_scores runs on the HIP device only (no CPU fallback)')
+    if not (X.dtype == torch.float32 and X.dim() == 2 and X.stride(1) == 1 and X.shape[1] == fit.d and X.stride(0) >= fit.d):
+        raise ValueError(f'attack_scores: X must be a float32 [n, {fit.d}] device tensor with unit column stride, not {tuple(X.shape)} {X.dtype}')
+    fold = int(fold)
+    if not 0 <= fold < fit.folds:
+        raise ValueError(f'fold must be in 0 .. {fit.folds - 1}, not {fold!r}')
+    rows_d = _index_list(rows, X.shape[0], X.device, 'rows')
+    _attack_stream(stream)
+    m = rows_d.numel()
+    scores = torch.empty(m, dtype=torch.float32, device=X.device)
+    nv.check(nv.lib().ure_attack_score(X.data_ptr(), int(X.stride(0)), fit.d, nv.ptr(rows_d), None, m, 1, fit.hidden, nv.ptr(fit.stats[fold]),
+                                       nv.ptr(fit.params[fold]), nv.ptr(scores), nv.stream_handle(stream)), 'ure_attack_score')
+    _csr_held_for(stream, rows_d, scores)
+    return scores
+
+
+def auc_counts(scores, pos, neg, stream=None):
+    """ure_auc_counts: (counts int64 [2] = (pairs with s_p > s_n, pairs with s_p == s_n), nan_flag int32 [1]) on the device, for the
+    index lists pos / neg into the float32 device tensor scores.  Never sorts; nothing of size n1 x n2 is written."""
+    scores = _scores_arg(scores, 'auc_counts')
+    dev = scores.device
+    pos_d, neg_d = _index_list(pos, scores.numel(), dev, 'pos'), _index_list(neg, scores.numel(), dev, 'neg')
+    _attack_stream(stream)
+    n1, n2 = pos_d.numel(), neg_d.numel()
+    nbytes = int(nv.lib().ure_auc_scratch(n1, n2))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_auc_counts(nv.ptr(scores), nv.ptr(pos_d), n1, nv.ptr(neg_d), n2, nv.ptr(counts), nv.ptr(flag), nv.ptr(scratch), nbytes,
+                                     nv.stream_handle(stream)), 'ure_auc_counts')
+    _csr_held_for(stream, pos_d, neg_d, scratch, counts, flag)
+    return counts, flag
+
+
+def confusion_counts(scores, pos, neg, thr=0.5, stream=None):
+    """ure_confusion_counts: int64 [4] = (tp, fn, tn, fp) on the device; a score > thr predicts class 1."""
+    scores = _scores_arg(scores, 'confusion_counts')
+    thr = float(thr)
+    if thr != thr:
+        raise ValueError('thr is NaN')
+    dev = scores.device
+    pos_d, neg_d = _index_list(pos, scores.numel(), dev, 'pos'), _index_list(neg, scores.numel(), dev, 'neg')
+    _attack_stream(stream)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    nv.check(nv.lib().ure_confusion_counts(nv.ptr(scores), nv.ptr(pos_d), pos_d.numel(), nv.ptr(neg_d), neg_d.numel(), thr, nv.ptr(counts),
+                                           nv.stream_handle(stream)), 'ure_confusion_counts')
+    _csr_held_for(stream, pos_d, neg_d, counts)
+    return counts
 
 
 # ---------------------------------------------------------------------------

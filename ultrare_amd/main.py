@@ -34,6 +34,10 @@ Same flags, defaults and assertions; additions are optional:
   --unlearn      'retrain' (default: the affected shards are retrained, Sisa.unlearn) or 'influence': damped Newton steps on the remaining
                  data of every affected shard, no retraining (Sisa.unlearn_influence, ultrare_amd/influence.py, csrc/influence.hip,
                  DESIGN 4.25): approximate.  Needs --model mf --loss mse
+  --attack       after every stage, the attribute-inference attacker (utils.attribute_attack, csrc/attack.hip) on the stage's
+                 final user table over the two groups of --attr-file (refused without one): a cross-validated MLP probe of
+                 --attack-hidden units (default 100; 0 is logistic regression) and --attack-folds folds (default 5).  Prints its AUC /
+                 BAcc / F1 and saves attack<id>.npy beside log<id>.npy; without the flag no file appears and no artifact changes
   --data-dir / --save-dir  roots of data/ and result/ (default: ./data, ./result)
 """
 import argparse
@@ -61,6 +65,9 @@ parser.add_argument('--unlearn', type=str, default='retrain', choices=['retrain'
 parser.add_argument('--dis-type', type=str, default='nor', choices=['nor', 'd2d', 'u2u'], help="'nor' (plain loss), or the per-batch attribute term 'd2d' (MMD) / 'u2u' (Laplacian); needs --attr-file and --model lightgcn (--gcn-layers 0 is plain MF)")
 parser.add_argument('--attr-file', type=str, default=None, help="an .npz with id1 and id2: the global user ids of the two attribute groups of --dis-type")
 parser.add_argument('--dis-eta', type=float, default=1.0, help='weight of the --dis-type term')
+parser.add_argument('--attack', action='store_true', help="after every stage, run the attribute-inference attacker on the final user table over the groups of --attr-file (needs it); prints AUC / BAcc / F1, saves attack<id>.npy")
+parser.add_argument('--attack-hidden', type=int, default=100, help='hidden units of the --attack probe (0: logistic regression)')
+parser.add_argument('--attack-folds', type=int, default=5, help='cross-validation folds of the --attack probe')
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -88,8 +95,26 @@ def attr_groups(dis_type, attr_file):
         return [z['id1'], z['id2']]
 
 
+def attack_setting(attack, attr_file, hidden=100, folds=5):
+    """--attack as Instance.attack: None without the flag, else dict(id1, id2, hidden, folds) of --attr-file (refused without one)."""
+    import numpy as np
+    if not attack:
+        return None
+    if attr_file is None:
+        raise ValueError('--attack needs --attr-file (an .npz with id1 and id2): the two attribute groups the attacker tells apart')
+    from .attack import MAX_FOLDS, MAX_H, _int
+    hidden, folds = _int('--attack-hidden', hidden, 0, MAX_H), _int('--attack-folds', folds, 2, MAX_FOLDS)
+    with np.load(attr_file) as z:
+        if 'id1' not in z.files or 'id2' not in z.files:
+            raise ValueError(f'{attr_file} must hold the arrays id1 and id2, not {sorted(z.files)}')
+        return dict(id1=z['id1'], id2=z['id2'], hidden=hidden, folds=folds)
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
+    attack = attack_setting(args.attack, args.attr_file, args.attack_hidden, args.attack_folds)
+    if attack is not None and args.model == 'nmf':
+        raise ValueError("--attack reads one user table: with --model nmf pass one of its two tables to utils.attribute_attack instead")
 
     assert args.dataset in ['ml1m', 'toy']
     assert args.epoch > 0
@@ -125,8 +150,15 @@ def main(argv=None):
     param = InsParam(args.dataset, args.epoch, args.worker, args.layer, args.group, args.delper, args.deltype,
                      k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr,
                      model=args.model, gcn_layers=args.gcn_layers, loss=args.loss, unlearn=args.unlearn,
-                     dis_type=args.dis_type, attr=attr_groups(args.dis_type, args.attr_file), dis_eta=args.dis_eta)
+                     dis_type=args.dis_type, attr=attr_groups(args.dis_type, None if attack is not None and args.dis_type == 'nor' else args.attr_file),
+                     dis_eta=args.dis_eta)
+    if attack is not None:
+        # the groups against the table the attacker will read, before any training: a bad file costs no run
+        from .attack import check_attack_args
+        check_attack_args(param.n_user, args.k, attack['id1'], attack['id2'], attack['hidden'], attack['folds'])
     ins = Instance(param, save_dir=args.save_dir)
+    if attack is not None:
+        ins.attack = attack
 
     if args.group == 0:
         ins.runFull(is_save=True, verbose=args.verbose)

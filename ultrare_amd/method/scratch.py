@@ -16,6 +16,7 @@ from torch import nn
 
 from .. import engine, rng
 from ..read import as_loader
+from . import utils
 from .utils import MF, NMF, padded_tables, seed_all
 
 PERM_THREADS = rng.perm_threads()
@@ -163,6 +164,15 @@ class Scratch(object):
         check_k(self.k)
         self.attr = (rows[:n1].astype(np.int64), rows[n1:].astype(np.int64))
         self.dis_eta = check_eta(getattr(param, 'dis_eta', 1.0))
+
+    def attribute_attack(self, model, id1, id2, **kw):
+        """The attribute-inference attacker on the user table of a model this object trained (utils.attribute_attack; its keywords
+        pass through).  It changes nothing.  The 'nmf' backbone has two user tables: pass one (or a torch.cat of both) to
+        utils.attribute_attack."""
+        if not hasattr(model, 'user_mat'):
+            raise ValueError("attribute_attack reads model.user_mat; for the 'nmf' backbone pass user_mat_mf.weight, user_mat_mlp.weight or a "
+                             "torch.cat of both (at most 128 columns) to utils.attribute_attack")
+        return utils.attribute_attack(model, id1, id2, **kw)
 
     def _optimizer_args(self):
         """What a TrainJob of this object takes beyond the reference's parameters."""

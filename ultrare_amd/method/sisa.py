@@ -670,6 +670,15 @@ class Sisa(Scratch):
         self.combiner = None
         return logs
 
+    def attribute_attack(self, id1, id2, **kw):
+        """How well an adversary tells the attribute groups id1 and id2 apart from the merged user table (utils.attribute_attack; its
+        keywords pass through): the cross-validated probe's out-of-fold AUC / BAcc / F1.  It changes no state: the tables keep their
+        bytes, no forget_rows, and a fitted combiner is kept.  The 'nmf' backbone has two user tables: pass one (or a torch.cat of
+        both) to utils.attribute_attack."""
+        if not self.model_list:
+            raise ValueError('attribute_attack needs trained models: call learn first')
+        return Scratch.attribute_attack(self, self.model_list[0], id1, id2, **kw)
+
     # ------------------------------------------------------------------ unlearn
     def recommend(self, users, top_k=10, exclude=None, combined=False):
         """Top-k items per user from the current ensemble (utils.recommend over self.model_list): after unlearn it answers

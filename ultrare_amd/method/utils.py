@@ -1091,6 +1091,48 @@ def attribute_unlearn(model, id1, id2, var='d2d', eta=1.0, alpha=0.0, lr=0.1, st
     return {'dis': host[0].tolist(), 'reg': host[1].tolist(), 'bandwidth': host[2].tolist()}
 
 
+def attribute_attack(model_or_table, id1, id2, hidden=100, folds=5, epochs=None, lr=None, l2=1e-4, seed=0):
+    """How much of a binary attribute the user embeddings still carry (the contract is attack.train_ref): a probe with one
+    hidden layer of `hidden` relu units (0: logistic regression) is trained on the standardised rows id1 (class 1) and id2 (class 0)
+    of the user table by full-batch Adam, `folds`-fold cross-validated, and every row is scored by the fold that held it out.
+    model_or_table: a model with user_mat (MF, LightGCN's parameters), or any float32 [n, d <= 128] device tensor with unit column
+    stride (final embeddings, one of NeuMF's two user tables, or a torch.cat of both).  The table is read in place and not changed.
+    epochs / lr None: attack.DEFAULT_EPOCHS / attack.DEFAULT_LR, chosen on the numpy contract's two synthetic cases and UNTUNED on
+    real attribute data.  Everything runs in csrc/attack.hip on one stream; one device-to-host copy, at the end.
+    -> dict: auc, bacc, f1 (pooled, out of fold), fold_auc [folds], counts (gt, eq, tp, fn, tn, fp, and per fold gt / eq / n1 / n2),
+    loss (first and last epoch, per fold) and settings.  ValueError before any device work for bad groups or settings."""
+    from .. import attack as A
+    X = model_or_table.user_mat.weight.detach() if hasattr(model_or_table, 'user_mat') else model_or_table
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise ValueError('attribute_attack takes a model with user_mat or a 2-d float32 device tensor')
+    rows, n1, n2, H, folds, epochs, lr, l2 = A.check_attack_args(X.shape[0], X.shape[1], id1, id2, hidden, folds, epochs, lr, l2)
+    if not X.is_cuda:
+        raise nv.NativeError('the table is not on the HIP device (call model.to("cuda")): no CPU fallback')
+    groups = engine.GroupRows.checked(rows, n1, n2, X.shape[0], X.device)
+    fit = engine.attack_fit(X, groups, H, folds, epochs, lr, l2, seed)
+    pos, neg = np.arange(n1), np.arange(n1, n1 + n2)
+    out = [engine.auc_counts(fit.scores, pos, neg), engine.confusion_counts(fit.scores, pos, neg)]
+    sizes = []
+    for f in range(folds):
+        held = np.flatnonzero(fit.fold_host == f)
+        p, n = held[held < n1], held[held >= n1]
+        sizes.append((len(p), len(n)))
+        out.append(engine.auc_counts(fit.scores, p, n))
+    flat = torch.cat([out[0][0], out[0][1].long(), out[1]] + [torch.cat([c, b.long()]) for c, b in out[2:]] +
+                     [fit.loss[:, 0].contiguous().view(torch.int64), fit.loss[:, -1].contiguous().view(torch.int64)]).cpu().numpy()
+    if flat[2] or any(flat[7 + 3 * f + 2] for f in range(folds)):
+        raise ValueError('the probe produced a NaN score: the selected rows of the table are not finite')
+    gt, eq, tp, fn, tn, fp = (int(v) for v in (flat[0], flat[1], flat[3], flat[4], flat[5], flat[6]))
+    res = A.metrics(gt, eq, tp, fn, tn, fp)
+    per = [(int(flat[7 + 3 * f]), int(flat[7 + 3 * f + 1])) + sizes[f] for f in range(folds)]
+    res['fold_auc'] = [(g + e / 2.0) / (float(a) * float(b)) for g, e, a, b in per]
+    res['counts'] = dict(gt=gt, eq=eq, tp=tp, fn=fn, tn=tn, fp=fp, folds=[dict(gt=g, eq=e, n1=a, n2=b) for g, e, a, b in per])
+    loss = flat[7 + 3 * folds:].view(np.float64).reshape(2, folds)
+    res['loss'] = dict(first=loss[0].tolist(), last=loss[1].tolist())
+    res['settings'] = dict(hidden=H, folds=folds, epochs=epochs, lr=lr, l2=l2, seed=seed, n1=n1, n2=n2, d=int(X.shape[1]))
+    return res
+
+
 def newton_unlearn_check(model_type='mf', loss='mse', l2=None, batch=None, lam=None, damping=None, curvature='full', steps=1, iters=512, tol=1e-8,
                          n_rows=0):
     """The settings of newton_unlearn, checked on the host (ValueError) -> (l2, damping).  l2 None: trainer_l2(n_rows, batch, lam)."""

@@ -422,6 +422,36 @@ def _(X, rows, n1):
     return X.new_empty((), dtype=torch.float64), X.new_empty(rows.numel(), X.shape[1])
 
 
+@torch.library.custom_op('ultrare::auc_counts', mutates_args=())
+def auc_counts(scores: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """engine.auc_counts: (int64 [2] = pairs with s_p > s_n, pairs with s_p == s_n; int32 [1] = a selected score is NaN)."""
+    _dev(scores, pos, neg)
+    return engine.auc_counts(scores, pos, neg)
+
+
+@auc_counts.register_fake
+def _(scores, pos, neg):
+    return scores.new_empty(2, dtype=torch.int64), scores.new_empty(1, dtype=torch.int32)
+
+
+@torch.library.custom_op('ultrare::attack_scores', mutates_args=())
+def attack_scores(X: torch.Tensor, rows: torch.Tensor, params: torch.Tensor, stats: torch.Tensor, hidden: int) -> torch.Tensor:
+    """engine.attack_scores with one packed parameter set (float32 [P]) and its statistics (float32 [2, d]) given as tensors."""
+    from . import attack
+    _dev(X, rows, params, stats)
+    d = int(X.shape[1]) if X.dim() == 2 else -1
+    if params.dtype != torch.float32 or stats.dtype != torch.float32 or not 1 <= d <= attack.MAX_D or not 0 <= hidden <= attack.MAX_H or \
+            tuple(params.shape) != (attack.n_params(d, hidden),) or tuple(stats.shape) != (2, d):
+        raise ValueError(f'attack_scores: params float32 [P(d, hidden)] and stats float32 [2, d] are needed for X {tuple(X.shape)}, hidden = {hidden}')
+    fit = engine.AttackFit(params=params.contiguous()[None], stats=stats.contiguous()[None], d=d, hidden=int(hidden), folds=1)
+    return engine.attack_scores(fit, X, rows)
+
+
+@attack_scores.register_fake
+def _(X, rows, params, stats, hidden):
+    return X.new_empty(rows.numel())
+
+
 @torch.library.custom_op('ultrare::gcn_propagate', mutates_args=())
 def gcn_propagate(off: torch.Tensor, idx: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor, X: torch.Tensor,
                   add: Optional[torch.Tensor] = None) -> torch.Tensor:
