@@ -793,5 +793,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_attr_train.h"
 /* The attribute-inference attacker (csrc/attack.hip): a cross-validated MLP probe on selected rows, exact AUC pair counts. */
 #include "ultrare_attack.h"
+/* Adversarial attribute unlearning (csrc/adv.hip): the gradient of that probe's loss with respect to its input rows. */
+#include "ultrare_adv.h"
 
 #endif /* ULTRARE_HIP_H */

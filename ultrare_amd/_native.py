@@ -282,6 +282,13 @@ _ATTACK_PROTOTYPES = {
 }
 ATTACK_EXPORTS = tuple(_ATTACK_PROTOTYPES)
 
+# include/ultrare_adv.h (adversarial attribute unlearning, csrc/adv.hip): a table of its own, as the header is;
+# tests/test_cpu_adv.py holds the table, the header and the library to each other, tests/test_gpu_adv.py runs the entry in guard zones.
+_ADV_PROTOTYPES = {
+    'ure_adv_input_grad': (ctypes.c_int, _PROBE_ROWS + [_i64, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+}
+ADV_EXPORTS = tuple(_ADV_PROTOTYPES)
+
 _lib = None
 
 
@@ -298,7 +305,7 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES,
-                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES, **_ATTACK_PROTOTYPES}.items():
+                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES, **_ATTACK_PROTOTYPES, **_ADV_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -200,6 +200,41 @@ class Instance(object):
         self.last_attack = res
         return res
 
+    def _adv(self, table, run, attack_run, save_dir, id=0, owner=None):
+        """main.py --adv-unlearn: self.adv = dict(id1, id2, rounds, hidden), set by the caller after construction.  Adversarial
+        attribute unlearning (utils.adversarial_unlearn) on the final user table of the stage: run(adv) -> the list of logs, table()
+        -> the user table it moves.  A one-line summary is printed and, with a save_dir, adv<id>.npy is stored beside log<id>.npy:
+        the logs, the moved rows (ids, rows) and -- with --attack -- the attacker's result from before the move; attack<id>.npy is
+        then the attacker on the moved table.  The stage's table gets its trained bytes back afterwards: the saved model files
+        are training's and the next stage starts from the trained rows; a combiner fitted on them, which
+        Sisa.adversarial_unlearn drops, is put back on `owner` with them.  Without self.adv this is _attack alone."""
+        v = getattr(self, 'adv', None)
+        if v is None:
+            return self._attack(attack_run, save_dir, id)
+        import torch
+        a = getattr(self, 'attack', None)
+        before = attack_run(a) if a is not None else None
+        kept = table().detach().clone()
+        combiner = getattr(owner, 'combiner', None)
+        logs = run(v)
+        T = table().detach()
+        moved = [g for g in logs if 'skipped' not in g]
+        n = sum(sum(g['rows']) for g in moved)
+        first, last = (sum(g['auc'][k] * sum(g['rows']) for g in moved) / max(n, 1) for k in (0, -1))
+        rms = float(np.sqrt(sum(g['reg'][-1] for g in moved) / max(n, 1)))
+        print('adversarial unlearning (hidden %d, %d rounds): %d of %d parts moved, in-loop AUC %.4f -> %.4f, RMS row movement %.4f'
+              % (v['hidden'], v['rounds'], len(moved), len(logs), first, last, rms))
+        ids = np.concatenate([np.asarray(v['id1']), np.asarray(v['id2'])]).astype(np.int64)
+        res = dict(logs=logs, attack_before=before, ids=ids, rows=T[torch.from_numpy(ids).to(T.device)].cpu().numpy())
+        if save_dir and dist_rank()[0] == 0:
+            np.save(save_dir + '/adv' + str(id), res)
+        self._attack(attack_run, save_dir, id)
+        T.copy_(kept)
+        if combiner is not None:
+            owner.combiner = combiner
+        self.last_adv = res
+        return res
+
     # sub function of self.runFull (config.py:99-120)
     def _full(self, is_save, saving_name, model_type='mf', is_del=False, verbose=1):
         print(self.name, saving_name, 'begin:')
@@ -209,7 +244,10 @@ class Instance(object):
         save_dir = self._save_dir(is_save, saving_name)
         model = Scratch(self.param, model_type)
         trained = model.train(train_data, test_data, [], verbose, save_dir)
-        self._attack(lambda a: model.attribute_attack(trained, a['id1'], a['id2'], hidden=a['hidden'], folds=a['folds']), save_dir)
+        self._adv(lambda: trained.user_mat.weight,
+                  lambda v: [dict(model.adversarial_unlearn(trained, v['id1'], v['id2'], hidden=v['hidden'], rounds=v['rounds']),
+                                  rows=(len(v['id1']), len(v['id2'])))],
+                  lambda a: model.attribute_attack(trained, a['id1'], a['id2'], hidden=a['hidden'], folds=a['folds']), save_dir)
         print('End of training', self.name, saving_name)
         print()
         return trained
@@ -272,7 +310,9 @@ class Instance(object):
                 model.unlearn_influence(model_list, train_dlist, test_data, del_user, verbose, save_dir)
             else:
                 model.unlearn(model_list, train_dlist, test_dlist, test_data, del_user, verbose, save_dir)
-        self._attack(lambda a: model.attribute_attack(a['id1'], a['id2'], hidden=a['hidden'], folds=a['folds']), save_dir)
+        self._adv(lambda: model._merged_table(),
+                  lambda v: model.adversarial_unlearn(v['id1'], v['id2'], hidden=v['hidden'], rounds=v['rounds']),
+                  lambda a: model.attribute_attack(a['id1'], a['id2'], hidden=a['hidden'], folds=a['folds']), save_dir, owner=model)
         self.last = model
         return model.model_list
 

@@ -1985,44 +1985,172 @@ def attack_fit(X, groups, hidden=100, folds=5, epochs=None, lr=None, l2=1e-4, se
     ure_attack_standardize, ure_attack_train and ure_attack_score, back to back on one stream -> AttackFit.  The fold plan and the
     initial parameters come from attack.fold_plan / attack.init_params under `seed` (params0, fold_of: given ones, for tests).
     Nothing is read back and nothing synchronises."""
-    from . import adam, attack as A
-    d, ld = _attr_table(X, groups, 'attack_fit')
-    n1, n2, m = groups.n1, groups.n2, groups.m
-    H, folds, epochs, lr, l2 = A.check_settings(d, n1, n2, hidden, folds, epochs, lr, l2)
-    P = A.n_params(d, H)
-    fold_host = A.fold_plan(n1, n2, folds, seed) if fold_of is None else np.ascontiguousarray(fold_of, dtype=np.int32)
-    p0 = A.init_params(d, H, folds, seed) if params0 is None else np.ascontiguousarray(params0, dtype=np.float32)
-    if fold_host.shape != (m,) or p0.shape != (folds, P):
-        raise ValueError(f'fold_of must have shape ({m},) and params0 ({folds}, {P}), not {fold_host.shape} and {p0.shape}')
-    y = np.arange(m) < n1
-    fw = np.zeros((folds, 4), dtype=np.float32)
-    for f in range(folds):
-        cw, m_train = A.class_weights(y, fold_host != f)
-        fw[f, :2], fw[f, 2] = cw, m_train
-    if not np.isfinite(fw).all():
-        raise ValueError('a fold trains on one class only: the fold plan must leave both classes in every training part')
-    b1, b2, eps = adam.betas32(A.BETAS, A.EPS)
-    dev, L, st = X.device, nv.lib(), nv.stream_handle(stream)
-    nbytes = int(L.ure_attack_scratch(m, d, H, folds))
-    if nbytes < 0:
-        raise ValueError(f'ure_attack_scratch refused m = {m}, d = {d}, H = {H}, folds = {folds}')
-    fold_d, p0_d, fw_d, sc_d = (to_device_async(a, dev) for a in (fold_host, p0, fw, A.scalars(epochs, lr)))
-    _attack_stream(stream)
-    stats = torch.empty(folds, 2, d, dtype=torch.float32, device=dev)
-    params = torch.empty(folds, P, dtype=torch.float32, device=dev)
-    loss = torch.empty(folds, epochs, dtype=torch.float64, device=dev)
+    run = _ProbeRun(X, groups, hidden, folds, epochs, lr, l2, seed, params0, fold_of, stream, 'attack_fit')
+    dev, m = X.device, groups.m
+    stats = torch.empty(run.folds, 2, run.d, dtype=torch.float32, device=dev)
+    params = torch.empty(run.folds, run.P, dtype=torch.float32, device=dev)
+    loss = torch.empty(run.folds, run.epochs, dtype=torch.float64, device=dev)
     scores = torch.empty(m, dtype=torch.float32, device=dev)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rows = groups.rows
-    nv.check(L.ure_attack_standardize(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(fold_d), m, folds, nv.ptr(stats), st), 'ure_attack_standardize')
-    nv.check(L.ure_attack_train(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(fold_d), m, n1, folds, H, nv.ptr(stats), nv.ptr(fw_d), nv.ptr(sc_d), epochs,
-                                b1, b2, eps, float(np.float32(l2)), nv.ptr(p0_d), nv.ptr(params), nv.ptr(loss), nv.ptr(scratch), nbytes, st),
-             'ure_attack_train')
-    nv.check(L.ure_attack_score(X.data_ptr(), ld, d, nv.ptr(rows), nv.ptr(fold_d), m, folds, H, nv.ptr(stats), nv.ptr(params), nv.ptr(scores), st),
-             'ure_attack_score')
-    _csr_held_for(stream, fold_d, p0_d, fw_d, sc_d, stats, params, loss, scores, scratch)
-    return AttackFit(params=params, stats=stats, fold_of=fold_d, fold_host=fold_host, scores=scores, loss=loss, d=d, hidden=H, folds=folds,
-                     epochs=epochs, lr=lr, l2=l2, seed=seed, n1=n1, n2=n2)
+    run.standardize(X, stats)
+    run.train(X, stats, run.p0, params, loss)
+    nv.check(nv.lib().ure_attack_score(X.data_ptr(), run.ld, run.d, nv.ptr(groups.rows), nv.ptr(run.fold_of), m, run.folds, run.H, nv.ptr(stats),
+                                       nv.ptr(params), nv.ptr(scores), run.st), 'ure_attack_score')
+    _csr_held_for(stream, stats, params, loss, scores)
+    return AttackFit(params=params, stats=stats, fold_of=run.fold_of, fold_host=run.fold_host, scores=scores, loss=loss, d=run.d, hidden=run.H,
+                     folds=run.folds, epochs=run.epochs, lr=run.lr, l2=run.l2, seed=seed, n1=groups.n1, n2=groups.n2, fw=run.fw)
+
+
+class _ProbeRun:
+    """What every launch of a probe on fixed groups, folds and settings shares, checked and uploaded once: the fold plan, the initial
+    parameters, the folds' class weights, Adam's scalars and ure_attack_train's scratch.  attack_fit runs it once, the round loop of
+    adversarial_unlearn once per round."""
+
+    def __init__(self, X, groups, hidden, folds, epochs, lr, l2, seed, params0, fold_of, stream, what):
+        from . import adam, attack as A
+        from .adv_unlearn import fold_weights
+        self.d, self.ld = _attr_table(X, groups, what)
+        self.groups, self.stream = groups, stream
+        n1, n2, m, d = groups.n1, groups.n2, groups.m, self.d
+        self.H, self.folds, self.epochs, self.lr, self.l2 = A.check_settings(d, n1, n2, hidden, folds, epochs, lr, l2)
+        self.P = A.n_params(d, self.H)
+        self.fold_host = A.fold_plan(n1, n2, self.folds, seed) if fold_of is None else np.ascontiguousarray(fold_of, dtype=np.int32)
+        p0 = A.init_params(d, self.H, self.folds, seed) if params0 is None else np.ascontiguousarray(params0, dtype=np.float32)
+        if self.fold_host.shape != (m,) or p0.shape != (self.folds, self.P):
+            raise ValueError(f'fold_of must have shape ({m},) and params0 ({self.folds}, {self.P}), not {self.fold_host.shape} and {p0.shape}')
+        fw = fold_weights(n1, self.fold_host, self.folds)
+        if not np.isfinite(fw).all():
+            raise ValueError('a fold trains on one class only: the fold plan must leave both classes in every training part')
+        self.betas = adam.betas32(A.BETAS, A.EPS)
+        dev = X.device
+        self.nbytes = int(nv.lib().ure_attack_scratch(m, d, self.H, self.folds))
+        if self.nbytes < 0:
+            raise ValueError(f'ure_attack_scratch refused m = {m}, d = {d}, H = {self.H}, folds = {self.folds}')
+        self.fold_of, self.p0, self.fw, self.sc = (to_device_async(a, dev) for a in (self.fold_host, p0, fw, A.scalars(self.epochs, self.lr)))
+        _attack_stream(stream)
+        self.scratch = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.st = nv.stream_handle(stream)
+        # (the caller's table and rows too: freed or rebound right after an asynchronous call, their blocks must not be handed out
+        # again -- a small upload can land inside a freed table -- while the launch stream still reads them)
+        _csr_held_for(stream, X, groups.rows, self.fold_of, self.p0, self.fw, self.sc, self.scratch)
+
+    def standardize(self, X, stats):
+        g = self.groups
+        nv.check(nv.lib().ure_attack_standardize(X.data_ptr(), self.ld, self.d, nv.ptr(g.rows), nv.ptr(self.fold_of), g.m, self.folds, nv.ptr(stats),
+                                                 self.st), 'ure_attack_standardize')
+
+    def train(self, X, stats, p_in, p_out, loss):
+        """`epochs` epochs from p_in into p_out (the same tensor will do), the losses into loss [folds, epochs]."""
+        g = self.groups
+        b1, b2, eps = self.betas
+        nv.check(nv.lib().ure_attack_train(X.data_ptr(), self.ld, self.d, nv.ptr(g.rows), nv.ptr(self.fold_of), g.m, g.n1, self.folds, self.H,
+                                           nv.ptr(stats), nv.ptr(self.fw), nv.ptr(self.sc), self.epochs, b1, b2, eps, float(np.float32(self.l2)),
+                                           nv.ptr(p_in), nv.ptr(p_out), nv.ptr(loss), nv.ptr(self.scratch), self.nbytes, self.st), 'ure_attack_train')
+
+
+def _adv_plan(fit, dev):
+    """The fold groups of ure_adv_input_grad for a fit (adv_unlearn.fold_groups), made once and kept on it: from fold_host where the
+    fit has one, else on the device from fold_of (a stable sort and counts on torch's current stream; nothing is read back)."""
+    plan = getattr(fit, 'adv_plan', None)
+    if plan is None:
+        host = getattr(fit, 'fold_host', None)
+        if host is not None:
+            from .adv_unlearn import fold_groups
+            perm, off = fold_groups(host, fit.folds)
+            plan = (to_device_async(perm, dev), to_device_async(off, dev))
+        else:
+            fo = fit.fold_of.long()
+            key = torch.where((fo >= 0) & (fo < fit.folds), fo, torch.full_like(fo, fit.folds))
+            sizes = (key[:, None] == torch.arange(fit.folds + 1, device=dev)[None, :]).sum(0)         # (no bincount: it reads its size back)
+            off = torch.zeros(fit.folds + 2, dtype=torch.int32, device=dev)
+            off[1:] = torch.cumsum(sizes, 0)
+            plan = (torch.argsort(key, stable=True).to(torch.int32), off)
+        try:
+            fit.adv_plan = plan
+        except AttributeError:
+            pass
+    return plan
+
+
+def _adv_target(target):
+    t = np.asarray(target, dtype=np.float64).reshape(-1)
+    if t.shape != (2,) or not np.isfinite(t).all():
+        raise ValueError(f'target must be two finite numbers (the target p of class 0 and of class 1), not {target!r}')
+    return float(np.float32(t[0])), float(np.float32(t[1]))
+
+
+def attack_input_grad(fit, X, groups, target=(0.5, 0.5), want_p=True, stream=None):
+    """ure_adv_input_grad: the gradient of every selected row's own term of the probe's loss with respect to the row, under the
+    parameter set that held the row out -> (grad float32 [m, d], p float32 [m] or None) on the device.  fit: an AttackFit, or
+    anything with its params, stats, fold_of (None: set 0 serves every row), fw, d, hidden and folds.  target = the p wanted of class
+    0 and of class 1: (0, 1) is the attacker's own loss, (0.5, 0.5) the confusion target.  The contract is
+    adv_unlearn.input_grad_ref.  Nothing is read back and nothing synchronises."""
+    d, ld = _attr_table(X, groups, 'attack_input_grad')
+    t0, t1 = _adv_target(target)
+    P = fit.params.shape[-1]
+    if d != fit.d or tuple(fit.params.shape) != (fit.folds, P) or tuple(fit.stats.shape) != (fit.folds, 2, d) or tuple(fit.fw.shape) != (fit.folds, 4):
+        raise ValueError(f'attack_input_grad: the fit is of width {fit.d} with params {tuple(fit.params.shape)}, the table of width {d}')
+    if fit.fold_of is not None and tuple(fit.fold_of.shape) != (groups.m,):
+        raise ValueError(f'attack_input_grad: the fit holds {tuple(fit.fold_of.shape)} positions, the groups {groups.m}')
+    dev, m = X.device, groups.m
+    perm, off = _adv_plan(fit, dev) if fit.fold_of is not None else (None, None)
+    _attack_stream(stream)
+    grad = torch.empty(m, d, dtype=torch.float32, device=dev)
+    p = torch.empty(m, dtype=torch.float32, device=dev) if want_p else None
+    nv.check(nv.lib().ure_adv_input_grad(X.data_ptr(), ld, d, nv.ptr(groups.rows), nv.ptr(fit.fold_of), m, groups.n1, fit.folds, fit.hidden,
+                                         nv.ptr(fit.stats), nv.ptr(fit.params), nv.ptr(fit.fw), t0, t1, nv.ptr(grad), nv.ptr(p), nv.ptr(perm),
+                                         nv.ptr(off), nv.stream_handle(stream)), 'ure_adv_input_grad')
+    _csr_held_for(stream, X, groups.rows, fit.params, fit.stats, fit.fw, grad, *([p] if want_p else []), *([] if perm is None else [fit.fold_of, perm, off]))
+    return grad, p
+
+
+def adversarial_unlearn(X, groups, hidden=32, folds=5, rounds=100, disc_epochs=5, disc_lr=1e-2, l2=1e-4, lr=0.1, eta=1.0, alpha=0.0,
+                        target=(0.5, 0.5), seed=0, stream=None, params0=None, fold_of=None):
+    """The round loop of adv_unlearn.adversarial_unlearn_ref on the rows of `groups` of the device table X, IN PLACE: per round
+    ure_attack_standardize, ure_attack_train from the last round's parameters (disc_epochs epochs), ure_adv_input_grad, ure_auc_counts
+    on its p, and the elementwise update, back to back on one stream.  Nothing is read back: -> AttackFit of the last round
+    (params, stats, fold_of, fold_host, fw, scores = the last p) with the log on the device: loss float64 [rounds, folds, disc_epochs],
+    counts int64 [rounds, 2] = (gt, eq), nan_flags int32 [rounds], reg float64 [rounds] (sum |x - x*|^2 after the round's update)."""
+    from .adv_unlearn import check_loop
+    rounds, disc_epochs, disc_lr, l2, lr, eta, alpha, _ = check_loop(rounds, disc_epochs, disc_lr, l2, lr, eta, alpha)
+    t0, t1 = _adv_target(target)
+    run = _ProbeRun(X, groups, hidden, folds, disc_epochs, disc_lr, l2, seed, params0, fold_of, stream, 'adversarial_unlearn')
+    dev, m, n1, n2, L = X.device, groups.m, groups.n1, groups.n2, nv.lib()
+    fit = AttackFit(params=run.p0.clone(), stats=torch.empty(run.folds, 2, run.d, dtype=torch.float32, device=dev), fold_of=run.fold_of,
+                    fold_host=run.fold_host, fw=run.fw, d=run.d, hidden=run.H, folds=run.folds, epochs=disc_epochs, lr=disc_lr, l2=l2, seed=seed,
+                    n1=n1, n2=n2)
+    perm, off = _adv_plan(fit, dev)
+    pos, neg = torch.arange(n1, dtype=torch.int32, device=dev), torch.arange(n1, m, dtype=torch.int32, device=dev)
+    auc_bytes = int(L.ure_auc_scratch(n1, n2))
+    auc_ws = torch.empty(auc_bytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty(rounds, run.folds, disc_epochs, dtype=torch.float64, device=dev)
+    counts = torch.empty(rounds, 2, dtype=torch.int64, device=dev)
+    flags = torch.empty(rounds, dtype=torch.int32, device=dev)
+    reg = torch.empty(rounds, dtype=torch.float64, device=dev)
+    grad = torch.empty(m, run.d, dtype=torch.float32, device=dev)
+    p = torch.empty(m, dtype=torch.float32, device=dev)
+    at = groups.rows.long()                 # (before the launch stream's wait below, and held for it: every round reads it there)
+    _attack_stream(stream)
+    _csr_held_for(stream, fit.params, fit.stats, perm, off, pos, neg, auc_ws, loss, counts, flags, reg, grad, p, at)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        start = X.index_select(0, at).double()
+        for t in range(rounds):
+            run.standardize(X, fit.stats)
+            run.train(X, fit.stats, fit.params, fit.params, loss[t])
+            nv.check(L.ure_adv_input_grad(X.data_ptr(), run.ld, run.d, nv.ptr(groups.rows), nv.ptr(run.fold_of), m, n1, run.folds, run.H,
+                                          nv.ptr(fit.stats), nv.ptr(fit.params), nv.ptr(run.fw), t0, t1, nv.ptr(grad), nv.ptr(p), nv.ptr(perm),
+                                          nv.ptr(off), run.st), 'ure_adv_input_grad')
+            nv.check(L.ure_auc_counts(nv.ptr(p), nv.ptr(pos), n1, nv.ptr(neg), n2, counts[t].data_ptr(), flags[t].data_ptr(), nv.ptr(auc_ws), auc_bytes,
+                                      run.st), 'ure_auc_counts')
+            # x <- float32(x - lr (eta g + 2 alpha (x - x*))): the contract's operations one by one, in place (four float64 [m, d] at the peak)
+            cur = X.index_select(0, at).double()
+            step = grad.double().mul_(eta)
+            step.add_((cur - start).mul_(2.0 * alpha)).mul_(lr)
+            new = cur.sub_(step).float()
+            X.index_copy_(0, at, new)
+            delta = torch.sub(new, start, out=step)
+            reg[t] = delta.mul_(delta).sum()
+    fit.scores, fit.loss, fit.counts, fit.nan_flags, fit.reg, fit.grad = p, loss, counts, flags, reg, grad
+    return fit
 
 
 def _index_list(idx, n, dev, name):

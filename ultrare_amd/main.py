@@ -38,6 +38,13 @@ Same flags, defaults and assertions; additions are optional:
                  final user table over the two groups of --attr-file (refused without one): a cross-validated MLP probe of
                  --attack-hidden units (default 100; 0 is logistic regression) and --attack-folds folds (default 5).  Prints its AUC /
                  BAcc / F1 and saves attack<id>.npy beside log<id>.npy; without the flag no file appears and no artifact changes
+  --adv-unlearn  after every stage, adversarial attribute unlearning (utils.adversarial_unlearn, csrc/adv.hip) of the two groups of
+                 --attr-file (refused without one, and with --model nmf) on the stage's final user table: --adv-rounds rounds (default
+                 100) against a cross-validated discriminator of --adv-hidden units (default 32).  Prints a one-line summary and saves
+                 adv<id>.npy (the log, the moved rows and, with --attack, the attacker's result from BEFORE the move; attack<id>.npy is
+                 then the one after) beside log<id>.npy.  The saved model files are written by training and are NOT rewritten, and the
+                 next stage starts from the trained rows: the moved rows are in adv<id>.npy.  Without the flag no file appears and no
+                 artifact changes
   --data-dir / --save-dir  roots of data/ and result/ (default: ./data, ./result)
 """
 import argparse
@@ -68,6 +75,9 @@ parser.add_argument('--dis-eta', type=float, default=1.0, help='weight of the --
 parser.add_argument('--attack', action='store_true', help="after every stage, run the attribute-inference attacker on the final user table over the groups of --attr-file (needs it); prints AUC / BAcc / F1, saves attack<id>.npy")
 parser.add_argument('--attack-hidden', type=int, default=100, help='hidden units of the --attack probe (0: logistic regression)')
 parser.add_argument('--attack-folds', type=int, default=5, help='cross-validation folds of the --attack probe')
+parser.add_argument('--adv-unlearn', action='store_true', help="after every stage, adversarial attribute unlearning of the groups of --attr-file (needs it) on the final user table; prints a summary, saves adv<id>.npy with the moved rows.  The saved model files are written by training and are not rewritten")
+parser.add_argument('--adv-rounds', type=int, default=100, help='rounds of --adv-unlearn')
+parser.add_argument('--adv-hidden', type=int, default=32, help='hidden units of the --adv-unlearn discriminator (0: logistic regression)')
 parser.add_argument('--data-dir', type=str, default=None)
 parser.add_argument('--save-dir', type=str, default=None)
 
@@ -110,11 +120,30 @@ def attack_setting(attack, attr_file, hidden=100, folds=5):
         return dict(id1=z['id1'], id2=z['id2'], hidden=hidden, folds=folds)
 
 
+def adv_setting(adv, attr_file, model='mf', rounds=100, hidden=32):
+    """--adv-unlearn as Instance.adv: None without the flag, else dict(id1, id2, rounds, hidden) of --attr-file (refused without one,
+    and with --model nmf)."""
+    import numpy as np
+    if not adv:
+        return None
+    if attr_file is None:
+        raise ValueError('--adv-unlearn needs --attr-file (an .npz with id1 and id2): the two attribute groups to make indistinguishable')
+    if model == 'nmf':
+        raise ValueError('--adv-unlearn moves one user table: --model nmf has two (not supported)')
+    from .attack import MAX_H, _int
+    rounds, hidden = _int('--adv-rounds', rounds, 1, 1 << 20), _int('--adv-hidden', hidden, 0, MAX_H)
+    with np.load(attr_file) as z:
+        if 'id1' not in z.files or 'id2' not in z.files:
+            raise ValueError(f'{attr_file} must hold the arrays id1 and id2, not {sorted(z.files)}')
+        return dict(id1=z['id1'], id2=z['id2'], rounds=rounds, hidden=hidden)
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     attack = attack_setting(args.attack, args.attr_file, args.attack_hidden, args.attack_folds)
     if attack is not None and args.model == 'nmf':
         raise ValueError("--attack reads one user table: with --model nmf pass one of its two tables to utils.attribute_attack instead")
+    adv = adv_setting(args.adv_unlearn, args.attr_file, args.model, args.adv_rounds, args.adv_hidden)
 
     assert args.dataset in ['ml1m', 'toy']
     assert args.epoch > 0
@@ -150,15 +179,20 @@ def main(argv=None):
     param = InsParam(args.dataset, args.epoch, args.worker, args.layer, args.group, args.delper, args.deltype,
                      k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr,
                      model=args.model, gcn_layers=args.gcn_layers, loss=args.loss, unlearn=args.unlearn,
-                     dis_type=args.dis_type, attr=attr_groups(args.dis_type, None if attack is not None and args.dis_type == 'nor' else args.attr_file),
+                     dis_type=args.dis_type, attr=attr_groups(args.dis_type, None if (attack is not None or adv is not None) and args.dis_type == 'nor' else args.attr_file),
                      dis_eta=args.dis_eta)
     if attack is not None:
         # the groups against the table the attacker will read, before any training: a bad file costs no run
         from .attack import check_attack_args
         check_attack_args(param.n_user, args.k, attack['id1'], attack['id2'], attack['hidden'], attack['folds'])
+    if adv is not None:
+        from .adv_unlearn import DEFAULTS, check_adv_args
+        check_adv_args(param.n_user, args.k, adv['id1'], adv['id2'], adv['hidden'], DEFAULTS['folds'], adv['rounds'])
     ins = Instance(param, save_dir=args.save_dir)
     if attack is not None:
         ins.attack = attack
+    if adv is not None:
+        ins.adv = adv
 
     if args.group == 0:
         ins.runFull(is_save=True, verbose=args.verbose)

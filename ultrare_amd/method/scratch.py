@@ -174,6 +174,11 @@ class Scratch(object):
                              "torch.cat of both (at most 128 columns) to utils.attribute_attack")
         return utils.attribute_attack(model, id1, id2, **kw)
 
+    def adversarial_unlearn(self, model, id1, id2, **kw):
+        """Adversarial attribute unlearning of the user table of a model this object trained, in place (utils.adversarial_unlearn; its
+        keywords pass through) -> its log.  The 'nmf' backbone, with two user tables, is refused."""
+        return utils.adversarial_unlearn(model, id1, id2, **kw)
+
     def _optimizer_args(self):
         """What a TrainJob of this object takes beyond the reference's parameters."""
         return dict(optimizer=self.optimizer, betas=self.betas, eps=self.eps)

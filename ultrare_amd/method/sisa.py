@@ -670,6 +670,50 @@ class Sisa(Scratch):
         self.combiner = None
         return logs
 
+    def adversarial_unlearn(self, id1, id2, **kw):
+        """Adversarial attribute unlearning, shard by shard on the merged user table (utils.adversarial_unlearn; its keywords pass
+        through), exactly as attribute_unlearn goes: shard s plays the game on the rows of its OWN users only -- group_index[s] & id1
+        against group_index[s] & id2 -- so a row is moved by the shard that trained it and by no other, and retraining another
+        shard later stays exact.  A shard with fewer than `folds` users on either side is skipped with a reason (every held-out
+        part needs both classes).  Returns one entry per shard: utils.adversarial_unlearn's log plus 'rows' (n1, n2), or
+        {'skipped': reason, 'rows': (n1, n2)}.  A fitted combiner is dropped, also when a shard raises after rows have moved (a NaN
+        p is found at a shard's end: the shards before it keep their moved rows).  ValueError before any device work for bad groups
+        or settings."""
+        from ..adv_unlearn import DEFAULTS, check_loop
+        from ..attack import MAX_FOLDS, MAX_H, _int
+        from ..attr_unlearn import check_groups
+        self._refuse_nmf('adversarial_unlearn')
+        if not self.model_list:
+            raise ValueError('adversarial_unlearn needs trained models: call learn first')
+        unknown = set(kw) - set(DEFAULTS)
+        if unknown:
+            raise TypeError(f'adversarial_unlearn got unexpected keywords {sorted(unknown)}')
+        want = {**DEFAULTS, **kw}
+        check_loop(want['rounds'], want['disc_epochs'], want['disc_lr'], want['l2'], want['lr'], want['eta'], want['alpha'], want['target'])
+        _int('hidden', want['hidden'], 0, MAX_H)
+        folds = _int('folds', want['folds'], 2, MAX_FOLDS)
+        rows, n1, _ = check_groups(id1, id2, self.n_user)
+        a, b = rows[:n1].astype(np.int64), rows[n1:].astype(np.int64)
+        self._merged_table()
+        logs = []
+        try:
+            for s in range(self.n_group):
+                own = np.zeros(self.n_user, dtype=bool)
+                ids = np.asarray(self.group_index[s], dtype=np.int64)
+                own[ids[(ids >= 0) & (ids < self.n_user)]] = True
+                sa, sb = a[own[a]], b[own[b]]
+                if min(len(sa), len(sb)) < folds:
+                    logs.append({'skipped': f'shard {s} holds {len(sa)} users of id1 and {len(sb)} of id2: both sides need folds = {folds}',
+                                 'rows': (len(sa), len(sb))})
+                    continue
+                log = utils.adversarial_unlearn(self.model_list[s], sa, sb, **kw)
+                log['rows'] = (len(sa), len(sb))
+                logs.append(log)
+        finally:            # (a shard that raises at its end -- a NaN p -- has moved rows already, as may the shards before it)
+            self.forget_rows()
+            self.combiner = None
+        return logs
+
     def attribute_attack(self, id1, id2, **kw):
         """How well an adversary tells the attribute groups id1 and id2 apart from the merged user table (utils.attribute_attack; its
         keywords pass through): the cross-validated probe's out-of-fold AUC / BAcc / F1.  It changes no state: the tables keep their

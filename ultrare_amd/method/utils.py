@@ -1133,6 +1133,47 @@ def attribute_attack(model_or_table, id1, id2, hidden=100, folds=5, epochs=None,
     return res
 
 
+def adversarial_unlearn(model, id1, id2, hidden=32, folds=5, rounds=100, disc_epochs=5, disc_lr=1e-2, l2=1e-4, lr=0.1, eta=1.0, alpha=0.0,
+                        target='confuse', seed=0):
+    """Adversarial attribute unlearning (the contract is adv_unlearn.adversarial_unlearn_ref): `rounds` rounds of a game
+    between a discriminator -- attribute_attack's probe, `hidden` relu units, `folds`-fold cross-validated, warm-started and trained
+    `disc_epochs` full-batch Adam epochs (disc_lr, l2) per round -- and the rows id1 + id2 of model.user_mat.weight, which take one
+    step U_i -= lr (eta g_i + 2 alpha (U_i - U*_i)) per round, IN PLACE: g_i the gradient of the discriminator's cross-entropy on row
+    i against the target p = 1 / 2 ('confuse'), under the fold that never trained on row i; U* the table at entry.  Every other row
+    and the item table keep their bytes.  target='reverse' (ascending the discriminator's loss) is refused: it diverges.
+    The defaults are chosen on two synthetic tables (a planted direction and a null table, DESIGN 4.31's sweep) and are UNTUNED on
+    real attribute data.  Judge the result with a FRESH attribute_attack on the moved table, not with the in-loop AUC.
+    Everything runs in csrc/attack.hip and csrc/adv.hip on one stream and nothing is read back per round: the log -- dict of
+    disc_loss (first and last epoch: [rounds][folds]), auc [rounds] (the in-loop, out-of-fold AUC before the round's step), counts (gt,
+    eq per round), reg [rounds] (sum |U - U*|^2 after the round's step) and settings -- comes to the host in one copy at the end.
+    ValueError before any device work for bad groups or settings, and at the end when a p was NaN (the rows are not finite)."""
+    from ..adv_unlearn import check_adv_args
+    refuse_nmf(model, 'adversarial_unlearn')
+    W = model.user_mat.weight
+    rows, n1, n2, H, folds, rounds, disc_epochs, disc_lr, l2, lr, eta, alpha, tgt = check_adv_args(
+        W.shape[0], W.shape[1], id1, id2, hidden, folds, rounds, disc_epochs, disc_lr, l2, lr, eta, alpha, target)
+    U = W.detach()
+    if not U.is_cuda:
+        raise nv.NativeError('model tables are not on the HIP device (call model.to("cuda")): no CPU fallback')
+    if U.dtype != torch.float32 or U.stride(1) != 1:
+        raise ValueError('the user table must be float32 with unit column stride')
+    groups = engine.GroupRows.checked(rows, n1, n2, U.shape[0], U.device)
+    fit = engine.adversarial_unlearn(U, groups, H, folds, rounds, disc_epochs, disc_lr, l2, lr, eta, alpha, tgt, seed)
+    flat = torch.cat([fit.counts.reshape(-1), fit.nan_flags.long(), fit.reg.view(torch.int64), fit.loss[:, :, 0].contiguous().view(torch.int64).reshape(-1),
+                      fit.loss[:, :, -1].contiguous().view(torch.int64).reshape(-1)]).cpu().numpy()
+    counts, flags = flat[:2 * rounds].reshape(rounds, 2), flat[2 * rounds:3 * rounds]
+    if flags.any():
+        raise ValueError('the discriminator produced a NaN p: the selected rows of the table are not finite')
+    reg = flat[3 * rounds:4 * rounds].view(np.float64)
+    loss = flat[4 * rounds:].view(np.float64).reshape(2, rounds, folds)
+    return {'disc_loss': dict(first=loss[0].tolist(), last=loss[1].tolist()),
+            'auc': [(int(g) + int(e) / 2.0) / (float(n1) * float(n2)) for g, e in counts],
+            'counts': dict(gt=[int(g) for g in counts[:, 0]], eq=[int(e) for e in counts[:, 1]]),
+            'reg': reg.tolist(),
+            'settings': dict(hidden=H, folds=folds, rounds=rounds, disc_epochs=disc_epochs, disc_lr=disc_lr, l2=l2, lr=lr, eta=eta, alpha=alpha,
+                             target=target, seed=seed, n1=n1, n2=n2, d=int(U.shape[1]))}
+
+
 def newton_unlearn_check(model_type='mf', loss='mse', l2=None, batch=None, lam=None, damping=None, curvature='full', steps=1, iters=512, tol=1e-8,
                          n_rows=0):
     """The settings of newton_unlearn, checked on the host (ValueError) -> (l2, damping).  l2 None: trainer_l2(n_rows, batch, lam)."""

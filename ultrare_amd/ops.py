@@ -452,6 +452,30 @@ def _(X, rows, params, stats, hidden):
     return X.new_empty(rows.numel())
 
 
+@torch.library.custom_op('ultrare::attack_input_grad', mutates_args=())
+def attack_input_grad(X: torch.Tensor, rows: torch.Tensor, n1: int, fold_of: Optional[torch.Tensor], params: torch.Tensor, stats: torch.Tensor,
+                      fw: torch.Tensor, hidden: int, target0: float, target1: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """engine.attack_input_grad with the probe given as tensors: params float32 [folds, P], stats float32 [folds, 2, d], fw float32
+    [folds, 4], fold_of int32 [m] (None: set 0 serves every row) -> (grad float32 [m, d], p float32 [m])."""
+    from . import attack
+    _dev(X, rows, params, stats, fw, *([] if fold_of is None else [fold_of]))
+    d = int(X.shape[1]) if X.dim() == 2 else -1
+    folds = int(params.shape[0]) if params.dim() == 2 else -1
+    if [params.dtype, stats.dtype, fw.dtype] != [torch.float32] * 3 or not 1 <= d <= attack.MAX_D or not 0 <= hidden <= attack.MAX_H or \
+            not 1 <= folds <= attack.MAX_FOLDS or tuple(params.shape) != (folds, attack.n_params(d, hidden)) or tuple(stats.shape) != (folds, 2, d) or \
+            tuple(fw.shape) != (folds, 4) or (fold_of is not None and (fold_of.dtype != torch.int32 or tuple(fold_of.shape) != (rows.numel(),))):
+        raise ValueError(f'attack_input_grad: params float32 [folds, P(d, hidden)], stats float32 [folds, 2, d], fw float32 [folds, 4] and fold_of '
+                         f'int32 [m] or None are needed for X {tuple(X.shape)}, hidden = {hidden}')
+    fit = engine.AttackFit(params=params.contiguous(), stats=stats.contiguous(), fw=fw.contiguous(), d=d, hidden=int(hidden), folds=folds,
+                           fold_of=None if fold_of is None else fold_of.contiguous())
+    return engine.attack_input_grad(fit, X, _group_rows(X, rows, n1), (target0, target1))
+
+
+@attack_input_grad.register_fake
+def _(X, rows, n1, fold_of, params, stats, fw, hidden, target0, target1):
+    return X.new_empty(rows.numel(), X.shape[1]), X.new_empty(rows.numel())
+
+
 @torch.library.custom_op('ultrare::gcn_propagate', mutates_args=())
 def gcn_propagate(off: torch.Tensor, idx: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor, X: torch.Tensor,
                   add: Optional[torch.Tensor] = None) -> torch.Tensor:
