@@ -12,6 +12,9 @@
                 m = 773, folds = 5 missed this rule by a factor of 1.2 at the parameters after one Adam step.)
   training      the same rule on the out-of-fold scores (absolute: they lie in [0, 1]) of the planted, null and logistic cases, and
                 the device's AUC within the bound derived from it.
+  recorded      the bytes of tests/probe_cases.py's cases (training, scoring, the input gradient) equal to the digests recorded in
+                tests/golden/probe_parent_bytes.json before attack.hip and adv.hip shared probe.h: the rule above bounds an error,
+                this pins the summation orders.
 """
 import ctypes
 import os
@@ -279,6 +282,22 @@ def test_equal_bytes_on_streams_calls_and_junk(nv):
     got = engine.attack_scores(fits[0], torch.from_numpy(W).cuda()[:, :d], rows[::-1].copy(), fold=1).cpu().numpy()
     want = A.score_ref(W[:, :d], rows[::-1], None, fits[0].params.cpu().numpy()[1:2], fits[0].stats.cpu().numpy()[1:2], H)
     assert np.abs(got - want).max() <= 4 * ULP32
+
+
+def test_probe_bytes_are_the_recorded_ones(nv):
+    """Every case of tests/probe_cases.py gives the bytes recorded in tests/golden/probe_parent_bytes.json from the commit before
+    attack.hip and adv.hip shared probe.h: a refactor of the probe's kernels that reorders a chain shows here, not under the rule above."""
+    import json
+    import probe_cases as PC
+    with open(os.path.join(G, 'probe_parent_bytes.json')) as f:
+        want = json.load(f)
+    assert sorted(want['cases']) == sorted(PC.name(case) for case in PC.CASES)
+    off = []
+    for case in PC.CASES:
+        got = PC.digests(nv, _train_raw, case)
+        assert set(got) == set(want['cases'][PC.name(case)])
+        off += [(PC.name(case), k) for k in sorted(got) if got[k] != want['cases'][PC.name(case)][k]]
+    assert not off, f"recorded under HIP {want['torch_version_hip']}, run under {torch.version.hip}: {off}"
 
 
 # ---- the memory contract ------------------------------------------------------------------------------------------------------------

@@ -1,12 +1,11 @@
 // attack.hip -- the attribute-inference attacker on selected rows of a float32 table, for gfx950 (the arithmetic is
 // stated in numpy in ultrare_amd/attack.py, the entries in include/ultrare_attack.h).
 //
-// A probe is one hidden layer of H relu units (H = 0: logistic regression, run as ONE linear hidden unit whose output is the
-// logit) trained by full-batch Adam to tell the first n1 selected rows from the rest, one parameter set per cross-validation fold.
+// The probe of probe.h is trained by full-batch Adam to tell the first n1 selected rows from the rest, one parameter set per
+// cross-validation fold.
 //   attack_train_kernel   workgroup (chunk, fold) owns kChunk = 256 consecutive positions.  The fold's packed parameters are staged
-//                         in LDS once (W1 transposed: the lanes of a forward read consecutive hidden units), then the chunk is
-//                         walked kTile = 32 positions at a time: rows standardised into LDS, the forward chains on a 16 x 16
-//                         thread grid (2 rows x HQ units per thread), the logit / p / coef of a row on one lane each, and the
+//                         in LDS once, then the chunk is walked kTile = 32 positions at a time: probe.h's standardisation,
+//                         forward (2 rows x HQ units per thread) and logit, then p / coef / loss of a row on one lane each, and the
 //                         gradient chains continued in registers (thread (ty, tx) owns units ty + 16 i and columns tx + 16 j).
 //                         A position the fold holds out (and the tail behind m) has coef = +0.0: its terms are zeros, which
 //                         leave a chain that started from +0.0 as it was.  The chunk's sums go to scratch.
@@ -16,35 +15,16 @@
 //
 // The AUC is the exact count of (positive, negative) pairs with s_p > s_n and s_p == s_n: auc_tile_kernel holds one positive per
 // lane and walks the negatives through LDS, kAucNeg at a time; integer partial counts per workgroup, summed by auc_sum_kernel.
-#include "ure_internal.h"
+#include "probe.h"
 
 namespace ure {
 
-constexpr int kAtkMaxD = URE_ATTACK_MAX_D, kAtkMaxH = URE_ATTACK_MAX_H, kAtkMaxFolds = URE_ATTACK_MAX_FOLDS;
-constexpr int kChunk = URE_ATTACK_CHUNK, kTile = 32;
+constexpr int kChunk = URE_ATTACK_CHUNK, kTile = kProbeTile;
 constexpr int kAucPos = URE_AUC_TILE_POS, kAucNeg = URE_AUC_TILE_NEG, kAucMaxSplit = 128;
 static_assert(kChunk == kBlock && kAucPos == kBlock && kChunk % kTile == 0, "one thread per position of a chunk");
 
-struct AtkShape {
-    int d, H, He, linear;       // He = max(H, 1) hidden units as the kernels run them
-    int P, at_b1, at_w2, at_b2;
-};
-
-static AtkShape atk_shape(int d, int H)
-{
-    AtkShape s;
-    s.d = d, s.H = H, s.He = H > 0 ? H : 1, s.linear = H == 0;
-    s.at_b1 = s.He * d, s.at_w2 = s.at_b1 + s.He, s.at_b2 = s.at_w2 + s.He;
-    s.P = H > 0 ? s.at_b2 + 1 : d + 1;
-    return s;
-}
-
-static bool atk_shape_ok(int64_t m, int d, int H, int folds)
-{
-    return d >= 1 && d <= kAtkMaxD && H >= 0 && H <= kAtkMaxH && folds >= 2 && folds <= kAtkMaxFolds && m >= folds && m <= URE_ATTACK_MAX_ROWS;
-}
-
-__host__ __device__ inline bool atk_is_weight(const AtkShape &s, int e) { return e < s.at_b1 || (!s.linear && e >= s.at_w2 && e < s.at_b2); }
+// training and its statistics want two folds and a row per fold
+static bool atk_shape_ok(int64_t m, int d, int H, int folds) { return probe_shape_ok(m, d, H, folds, 2, folds, URE_ATTACK_MAX_ROWS); }
 
 // scratch of ure_attack_train: [part_loss double folds x chunks | l2sum double folds | part_grad float folds x chunks x P | mom | var float folds x P]
 struct AtkPlan {
@@ -63,79 +43,60 @@ static AtkPlan atk_plan(int64_t m, const AtkShape &s, int folds)
     return p;
 }
 
-// LDS of the training kernel, in floats behind kBlock + kTile doubles
-__host__ __device__ inline int atk_lds_floats(int d, int He) { return d * He + 2 * He + 4 + 2 * d + kTile * (d + 1) + kTile * (He + 1) + kTile; }
-static size_t atk_lds_bytes(int d, int He) { return 8 * (kBlock + kTile) + 4 * (size_t)atk_lds_floats(d, He); }
+// LDS of the training kernel: kBlock + kTile doubles (the fold's tree, the tile's row losses) in front of probe.h's layout, plain strides
+static size_t atk_lds_bytes(int d, int He) { return 8 * (kBlock + kTile) + 4 * (size_t)probe_lds(d, He, 0).floats; }
 
-// p = 1 / (1 + exp(-t)) evaluated in float64 and rounded to float32 ONCE: the correctly rounded sigmoid of the float32 logit (but for
-// the last bit of the float64 exp), so the contract's numpy line gives the same float32.  noinline: one copy of the float64 exp.
-__device__ __noinline__ float atk_sigmoid(float t) { return (float)(1.0 / (1.0 + exp(-(double)t))); }
 // (noinline: one copy of the float64 exp / log1p, outside the training kernel's register budget)
 __device__ __noinline__ double atk_softplus(double v) { return fmax(v, 0.0) + log1p(exp(-fabs(v))); }
-
-// double tree over the 256 threads of a workgroup: red[t] += red[t + w], w = 128 .. 1 (lightgcn.fold_256's fold)
-__device__ __forceinline__ double atk_fold(double *red, double v)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if (t < w) red[t] = red[t] + red[t + w];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
-}
 
 // ---- statistics: workgroup = one column, every fold at once ------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void attack_stats_kernel(const float *__restrict__ X, int64_t ld, const int32_t *__restrict__ rows,
                                                               const int32_t *__restrict__ fold_of, int64_t m, int folds, int d, float *__restrict__ stats)
 {
     __shared__ double red[kBlock];
-    __shared__ double mean_s[kAtkMaxFolds];
-    __shared__ int ntrain[kAtkMaxFolds];
+    __shared__ double mean_s[kProbeMaxFolds];
+    __shared__ int ntrain[kProbeMaxFolds];
     const int t = threadIdx.x, c = blockIdx.x;
-    if (t < kAtkMaxFolds) ntrain[t] = 0;
+    if (t < kProbeMaxFolds) ntrain[t] = 0;
     __syncthreads();
-    double acc[kAtkMaxFolds];
-    int cnt[kAtkMaxFolds];
+    double acc[kProbeMaxFolds];
+    int cnt[kProbeMaxFolds];
 #pragma unroll
-    for (int f = 0; f < kAtkMaxFolds; ++f) acc[f] = 0.0, cnt[f] = 0;
+    for (int f = 0; f < kProbeMaxFolds; ++f) acc[f] = 0.0, cnt[f] = 0;
     for (int64_t i = t; i < m; i += kBlock) {
         const double x = (double)ldg(X + (int64_t)ldg(rows + i) * ld + c);
         const int fo = ldg(fold_of + i);
 #pragma unroll
-        for (int f = 0; f < kAtkMaxFolds; ++f) {
+        for (int f = 0; f < kProbeMaxFolds; ++f) {
             acc[f] = acc[f] + (fo != f ? x : 0.0);
             cnt[f] += fo != f;
         }
     }
 #pragma unroll
-    for (int f = 0; f < kAtkMaxFolds; ++f) {
+    for (int f = 0; f < kProbeMaxFolds; ++f) {
         if (f < folds) {                  // (uniform)
             atomicAdd(&ntrain[f], cnt[f]);
-            const double s = atk_fold(red, acc[f]);
+            const double s = block_fold(red, acc[f]);
             if (t == 0) mean_s[f] = s / (double)ntrain[f];
         }
     }
     __syncthreads();
-    double mean[kAtkMaxFolds];
+    double mean[kProbeMaxFolds];
 #pragma unroll
-    for (int f = 0; f < kAtkMaxFolds; ++f) mean[f] = f < folds ? mean_s[f] : 0.0, acc[f] = 0.0;
+    for (int f = 0; f < kProbeMaxFolds; ++f) mean[f] = f < folds ? mean_s[f] : 0.0, acc[f] = 0.0;
     for (int64_t i = t; i < m; i += kBlock) {
         const double x = (double)ldg(X + (int64_t)ldg(rows + i) * ld + c);
         const int fo = ldg(fold_of + i);
 #pragma unroll
-        for (int f = 0; f < kAtkMaxFolds; ++f) {
+        for (int f = 0; f < kProbeMaxFolds; ++f) {
             const double dv = x - mean[f];
             acc[f] = acc[f] + (fo != f ? dv * dv : 0.0);
         }
     }
 #pragma unroll
-    for (int f = 0; f < kAtkMaxFolds; ++f) {
+    for (int f = 0; f < kProbeMaxFolds; ++f) {
         if (f < folds) {
-            const double var = atk_fold(red, acc[f]) / (double)ntrain[f];
+            const double var = block_fold(red, acc[f]) / (double)ntrain[f];
             if (t == 0) {
                 stats[((int64_t)f * 2 + 0) * d + c] = (float)mean[f];
                 stats[((int64_t)f * 2 + 1) * d + c] = var > 0.0 ? (float)(1.0 / sqrt(var)) : 0.0f;
@@ -155,36 +116,21 @@ __global__ __launch_bounds__(kBlock) void attack_train_kernel(const float *__res
     extern __shared__ double atk_lds[];
     const int d = s.d, He = s.He;
     double *red = atk_lds, *rloss = red + kBlock;
-    float *W1T = reinterpret_cast<float *>(rloss + kTile);      // [d][He]
-    float *b1 = W1T + d * He, *w2 = b1 + He, *b2 = w2 + He;     // b2: 4 floats
-    float *mean = b2 + 4, *inv = mean + d;
-    float *zs = inv + d;                                         // [kTile][d + 1]
-    float *rs = zs + kTile * (d + 1);                            // [kTile][He + 1]
-    float *coef = rs + kTile * (He + 1);                         // [kTile]
+    const ProbeLds L = probe_lds(d, He, 0, reinterpret_cast<float *>(rloss + kTile));
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     const int f = blockIdx.y, chunk = blockIdx.x;
-    const float *w = win + (int64_t)f * s.P;
 
-    for (int e = tid; e < He * d; e += kBlock) W1T[(e % d) * He + e / d] = ldg(w + e);
-    for (int h = tid; h < He; h += kBlock) {
-        b1[h] = ldg(w + s.at_b1 + h);
-        w2[h] = s.linear ? 1.0f : ldg(w + s.at_w2 + h);
-    }
-    if (tid == 0) b2[0] = s.linear ? 0.0f : ldg(w + s.at_b2);
-    for (int c = tid; c < d; c += kBlock) {
-        mean[c] = ldg(stats + ((int64_t)f * 2 + 0) * d + c);
-        inv[c] = ldg(stats + ((int64_t)f * 2 + 1) * d + c);
-    }
+    probe_stage(L, s, win + (int64_t)f * s.P, stats + (int64_t)f * 2 * d);
     __syncthreads();
 
     if (chunk == 0) {       // l2sum[f]: the 256-lane fold over the packed index of float64 w^2, the biases adding nothing
         double sq = 0.0;
         for (int e = tid; e < s.P; e += kBlock)
             if (atk_is_weight(s, e)) {
-                const double v = (double)(e < s.at_b1 ? W1T[(e % d) * He + e / d] : w2[e - s.at_w2]);
+                const double v = (double)(e < s.at_b1 ? L.W1T[(e % d) * L.HP + e / d] : L.w2[e - s.at_w2]);
                 sq = sq + v * v;
             }
-        const double tot = atk_fold(red, sq);
+        const double tot = block_fold(red, sq);
         if (tid == 0) l2sum[f] = tot;
     }
 
@@ -193,13 +139,9 @@ __global__ __launch_bounds__(kBlock) void attack_train_kernel(const float *__res
     int hh[HQ], cc[DQ];
     float w2r[HQ];
 #pragma unroll
-    for (int i = 0; i < HQ; ++i) hh[i] = min(ty + 16 * i, He - 1), w2r[i] = w2[hh[i]];
+    for (int i = 0; i < HQ; ++i) hh[i] = min(ty + 16 * i, He - 1), w2r[i] = L.w2[hh[i]];
 #pragma unroll
     for (int j = 0; j < DQ; ++j) cc[j] = min(tx + 16 * j, d - 1);
-    int hf[HQ];             // the units of this thread in the forward
-    float b1f[HQ];
-#pragma unroll
-    for (int j = 0; j < HQ; ++j) hf[j] = min(tx + 16 * j, He - 1), b1f[j] = b1[hf[j]];
 
     float acc[HQ][DQ], gb1[HQ], gw2[HQ], gb2 = 0.0f;
 #pragma unroll
@@ -213,61 +155,26 @@ __global__ __launch_bounds__(kBlock) void attack_train_kernel(const float *__res
     const int base = chunk * kChunk;
 #pragma unroll 1
     for (int p0 = base; p0 < base + kChunk && p0 < m; p0 += kTile) {
-        // 1. the tile's rows, standardised
-#pragma unroll 1
-        for (int e = tid; e < kTile * d; e += kBlock) {
-            const int r = e / d, c = e - r * d, i = p0 + r;
-            float z = 0.0f;
-            if (i < m) z = (ldg(X + (int64_t)ldg(rows + i) * ld + c) - mean[c]) * inv[c];
-            zs[r * (d + 1) + c] = z;
-        }
+        // 1. the tile's rows, standardised (the tail behind m: dead slots)
+        probe_standardize(L, d, X, ld, [&](int r, int &row) { return p0 + r < m && (row = ldg(rows + p0 + r), true); });
         __syncthreads();
         // 2. forward: rows ty and ty + 16, units tx + 16 j
-        {
-            float t0[HQ], t1[HQ];
-#pragma unroll
-            for (int j = 0; j < HQ; ++j) t0[j] = 0.0f, t1[j] = 0.0f;
-            const float *z0 = zs + ty * (d + 1), *z1 = zs + (ty + 16) * (d + 1);
-#pragma unroll 4
-            for (int c = 0; c < d; ++c) {
-                const float a0 = z0[c], a1 = z1[c];
-#pragma unroll
-                for (int j = 0; j < HQ; ++j) {
-                    const float wv = W1T[c * He + hf[j]];
-                    t0[j] = t0[j] + wv * a0;
-                    t1[j] = t1[j] + wv * a1;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < HQ; ++j)
-                if (tx + 16 * j < He) {
-                    const float a0 = t0[j] + b1f[j], a1 = t1[j] + b1f[j];
-                    rs[ty * (He + 1) + hf[j]] = s.linear ? a0 : (a0 <= 0.0f ? 0.0f : a0);
-                    rs[(ty + 16) * (He + 1) + hf[j]] = s.linear ? a1 : (a1 <= 0.0f ? 0.0f : a1);
-                }
-        }
+        probe_forward<HQ>(L, s, 0);
         __syncthreads();
         // 3. one lane per row: the logit, p, coef and the row's loss
         if (tid < kTile) {
             const int i = p0 + tid;
-            const float *r = rs + tid * (He + 1);
-            float t = r[0];
-            if (!s.linear) {
-                t = 0.0f;
-#pragma unroll 4
-                for (int h = 0; h < He; ++h) t = t + w2[h] * r[h];
-                t = t + b2[0];
-            }
+            const float t = probe_logit(L, s, tid);
             float cf = 0.0f;
             double lo = 0.0;
             if (i < m && ldg(fold_of + i) != f) {
                 const bool pos = i < n1;
                 const float wc = pos ? wc1 : wc0;
-                cf = wc * (atk_sigmoid(t) - (pos ? 1.0f : 0.0f));
+                cf = wc * (probe_sigmoid(t) - (pos ? 1.0f : 0.0f));
                 const double sgn = pos ? -(double)t : (double)t;
                 lo = (double)wc * atk_softplus(sgn);
             }
-            coef[tid] = cf;
+            L.coef[tid] = cf;
             rloss[tid] = lo;
         }
         __syncthreads();
@@ -276,11 +183,11 @@ __global__ __launch_bounds__(kBlock) void attack_train_kernel(const float *__res
             for (int r = 0; r < kTile; ++r) closs = closs + rloss[r];
 #pragma unroll 2
         for (int r = 0; r < kTile; ++r) {
-            const float cf = coef[r];
+            const float cf = L.coef[r];
             float dl[HQ];
 #pragma unroll
             for (int i = 0; i < HQ; ++i) {
-                const float rv = rs[r * (He + 1) + hh[i]];
+                const float rv = L.rs[r * L.RS + hh[i]];
                 dl[i] = s.linear ? cf : (rv > 0.0f ? cf * w2r[i] : 0.0f);
                 if (tx == 0) {
                     gb1[i] = gb1[i] + dl[i];
@@ -290,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void attack_train_kernel(const float *__res
             if (tid == 0) gb2 = gb2 + cf;
 #pragma unroll
             for (int j = 0; j < DQ; ++j) {
-                const float z = zs[r * (d + 1) + cc[j]];
+                const float z = L.zs[r * L.ZS + cc[j]];
 #pragma unroll
                 for (int i = 0; i < HQ; ++i) acc[i][j] = acc[i][j] + dl[i] * z;
             }
@@ -332,7 +239,7 @@ __global__ __launch_bounds__(kBlock) void attack_update_kernel(AtkShape s, int c
     if (blockIdx.x == 0) {
         double v = 0.0;
         for (int j = threadIdx.x; j < chunks; j += kBlock) v = v + ldg(part_loss + (int64_t)f * chunks + j);
-        const double tot = atk_fold(red, v);
+        const double tot = block_fold(red, v);
         if (threadIdx.x == 0) loss[(int64_t)f * epochs + epoch] = tot / (double)m_train + 0.5 * (double)l2 * ldg(l2sum + f);
     }
     if (e >= s.P) return;
@@ -392,25 +299,11 @@ __global__ __launch_bounds__(kBlock) void attack_score_kernel(const float *__res
             }
             t = t + ldg(w + s.at_b2);
         }
-        if (lane == 0) scores[i] = atk_sigmoid(t);
+        if (lane == 0) scores[i] = probe_sigmoid(t);
     }
 }
 
 // ---- pair counts ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t auc_fold_i64(int64_t *red, int64_t v)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    const int64_t out = red[0];
-    __syncthreads();
-    return out;
-}
-
 __global__ __launch_bounds__(kBlock) void auc_tile_kernel(const float *__restrict__ scores, const int32_t *__restrict__ pos, int64_t n1,
                                                           const int32_t *__restrict__ neg, int64_t n2, int64_t neg_tiles, int64_t *__restrict__ part,
                                                           int32_t *__restrict__ flags)
@@ -447,7 +340,7 @@ __global__ __launch_bounds__(kBlock) void auc_tile_kernel(const float *__restric
         gt += g32, eq += e32;
     }
     if (bad) atomicOr(&nan_s, 1);
-    const int64_t G = auc_fold_i64(red, gt), E = auc_fold_i64(red, eq);
+    const int64_t G = block_fold(red, gt), E = block_fold(red, eq);
     if (t == 0) {
         const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
         part[2 * blk] = G, part[2 * blk + 1] = E;
@@ -461,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void auc_sum_kernel(const int64_t *__restri
     __shared__ int64_t red[kBlock];
     int64_t g = 0, e = 0, b = 0;
     for (int64_t k = threadIdx.x; k < n_part; k += kBlock) g += ldg(part + 2 * k), e += ldg(part + 2 * k + 1), b |= ldg(flags + k) != 0;
-    const int64_t G = auc_fold_i64(red, g), E = auc_fold_i64(red, e), B = auc_fold_i64(red, b);
+    const int64_t G = block_fold(red, g), E = block_fold(red, e), B = block_fold(red, b);
     if (threadIdx.x == 0) counts[0] = G, counts[1] = E, *nan_flag = B != 0;
 }
 
@@ -472,7 +365,7 @@ __global__ __launch_bounds__(kBlock) void confusion_kernel(const float *__restri
     int64_t tp = 0, fp = 0;
     for (int64_t k = threadIdx.x; k < n1; k += kBlock) tp += ldg(scores + ldg(pos + k)) > thr;
     for (int64_t k = threadIdx.x; k < n2; k += kBlock) fp += ldg(scores + ldg(neg + k)) > thr;
-    const int64_t TP = auc_fold_i64(red, tp), FP = auc_fold_i64(red, fp);
+    const int64_t TP = block_fold(red, tp), FP = block_fold(red, fp);
     if (threadIdx.x == 0) counts[0] = TP, counts[1] = n1 - TP, counts[2] = n2 - FP, counts[3] = FP;
 }
 
@@ -573,7 +466,7 @@ int ure_attack_score(const float *X, int64_t ld, int32_t d, const int32_t *rows,
                      const float *stats, const float *params, float *scores, void *stream)
 {
     URE_ARG(X && rows && stats && params && scores);
-    URE_ARG(d >= 1 && d <= kAtkMaxD && H >= 0 && H <= kAtkMaxH && folds >= 1 && folds <= kAtkMaxFolds && m >= 1 && m <= INT32_MAX);
+    URE_ARG(probe_shape_ok(m, d, H, folds, 1, 1, INT32_MAX));
     URE_ARG(ld >= d);
     const unsigned blocks = (unsigned)std::min<int64_t>((m + kWavesPerBlock - 1) / kWavesPerBlock, 8192);
     attack_score_kernel<<<blocks, kBlock, 0, static_cast<hipStream_t>(stream)>>>(X, ld, rows, fold_of, m, folds, atk_shape(d, H), stats, params, scores);

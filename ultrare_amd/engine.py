@@ -2103,6 +2103,19 @@ def attack_input_grad(fit, X, groups, target=(0.5, 0.5), want_p=True, stream=Non
     return grad, p
 
 
+def unlearn_row_step(X, at, start, grad, lr, eta, alpha):
+    """x <- float32(x - lr (eta g + 2 alpha (x - x*))) on the rows `at` (int64) of the device table X, in place; x* = `start` (float64
+    [m, d]), g = `grad` (float32 [m, d], left as it is).  The contract's float64 operations one by one, rounded once, written in place (four float64 [m, d] at the
+    peak) -> (the new rows, float32; a float64 [m, d] buffer the caller may reuse).  utils.attribute_unlearn's step and the round of
+    adversarial_unlearn."""
+    cur = X.index_select(0, at).double()
+    step = grad.double().mul_(eta)
+    step.add_((cur - start).mul_(2.0 * alpha)).mul_(lr)
+    new = cur.sub_(step).float()
+    X.index_copy_(0, at, new)
+    return new, step
+
+
 def adversarial_unlearn(X, groups, hidden=32, folds=5, rounds=100, disc_epochs=5, disc_lr=1e-2, l2=1e-4, lr=0.1, eta=1.0, alpha=0.0,
                         target=(0.5, 0.5), seed=0, stream=None, params0=None, fold_of=None):
     """The round loop of adv_unlearn.adversarial_unlearn_ref on the rows of `groups` of the device table X, IN PLACE: per round
@@ -2141,13 +2154,8 @@ def adversarial_unlearn(X, groups, hidden=32, folds=5, rounds=100, disc_epochs=5
                                           nv.ptr(off), run.st), 'ure_adv_input_grad')
             nv.check(L.ure_auc_counts(nv.ptr(p), nv.ptr(pos), n1, nv.ptr(neg), n2, counts[t].data_ptr(), flags[t].data_ptr(), nv.ptr(auc_ws), auc_bytes,
                                       run.st), 'ure_auc_counts')
-            # x <- float32(x - lr (eta g + 2 alpha (x - x*))): the contract's operations one by one, in place (four float64 [m, d] at the peak)
-            cur = X.index_select(0, at).double()
-            step = grad.double().mul_(eta)
-            step.add_((cur - start).mul_(2.0 * alpha)).mul_(lr)
-            new = cur.sub_(step).float()
-            X.index_copy_(0, at, new)
-            delta = torch.sub(new, start, out=step)
+            new, spare = unlearn_row_step(X, at, start, grad, lr, eta, alpha)
+            delta = torch.sub(new, start, out=spare)
             reg[t] = delta.mul_(delta).sum()
     fit.scores, fit.loss, fit.counts, fit.nan_flags, fit.reg, fit.grad = p, loss, counts, flags, reg, grad
     return fit

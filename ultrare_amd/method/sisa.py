@@ -637,6 +637,15 @@ class Sisa(Scratch):
         self.combiner = None
 
     # ------------------------------------------------------------------ attribute unlearning
+    def _own_sides(self, rows, n1):
+        """(s, sa, sb) per shard: the users of rows[:n1] and of rows[n1:] that group_index[s] lists, in the order given."""
+        a, b = rows[:n1].astype(np.int64), rows[n1:].astype(np.int64)
+        for s in range(self.n_group):
+            own = np.zeros(self.n_user, dtype=bool)
+            ids = np.asarray(self.group_index[s], dtype=np.int64)
+            own[ids[(ids >= 0) & (ids < self.n_user)]] = True
+            yield s, a[own[a]], b[own[b]]
+
     def attribute_unlearn(self, id1, id2, **kw):
         """Make the user rows of the attribute groups id1 and id2 indistinguishable, shard by shard, without retraining
         (utils.attribute_unlearn; its keywords pass through).  Shard s fine-tunes the rows of its OWN users only --
@@ -651,15 +660,10 @@ class Sisa(Scratch):
         if not self.model_list:
             raise ValueError('attribute_unlearn needs trained models: call learn first')
         rows, n1, _ = check_groups(id1, id2, self.n_user)
-        a, b = rows[:n1].astype(np.int64), rows[n1:].astype(np.int64)
         utils.attribute_unlearn_check(**kw)
         self._merged_table()
         logs = []
-        for s in range(self.n_group):
-            own = np.zeros(self.n_user, dtype=bool)
-            ids = np.asarray(self.group_index[s], dtype=np.int64)
-            own[ids[(ids >= 0) & (ids < self.n_user)]] = True
-            sa, sb = a[own[a]], b[own[b]]
+        for s, sa, sb in self._own_sides(rows, n1):
             if len(sa) == 0 or len(sb) == 0:
                 logs.append({'skipped': f'shard {s} holds {len(sa)} users of id1 and {len(sb)} of id2: both sides need one', 'rows': (len(sa), len(sb))})
                 continue
@@ -693,15 +697,10 @@ class Sisa(Scratch):
         _int('hidden', want['hidden'], 0, MAX_H)
         folds = _int('folds', want['folds'], 2, MAX_FOLDS)
         rows, n1, _ = check_groups(id1, id2, self.n_user)
-        a, b = rows[:n1].astype(np.int64), rows[n1:].astype(np.int64)
         self._merged_table()
         logs = []
         try:
-            for s in range(self.n_group):
-                own = np.zeros(self.n_user, dtype=bool)
-                ids = np.asarray(self.group_index[s], dtype=np.int64)
-                own[ids[(ids >= 0) & (ids < self.n_user)]] = True
-                sa, sb = a[own[a]], b[own[b]]
+            for s, sa, sb in self._own_sides(rows, n1):
                 if min(len(sa), len(sb)) < folds:
                     logs.append({'skipped': f'shard {s} holds {len(sa)} users of id1 and {len(sb)} of id2: both sides need folds = {folds}',
                                  'rows': (len(sa), len(sb))})

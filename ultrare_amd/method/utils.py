@@ -1083,7 +1083,7 @@ def attribute_unlearn(model, id1, id2, var='d2d', eta=1.0, alpha=0.0, lr=0.1, st
         reg_log.append((delta * delta).sum())
         bw_log.append(bw)
         if t < steps:
-            U.index_copy_(0, at, (cur - lr * (eta * grad.double() + (2.0 * alpha) * delta)).float())
+            engine.unlearn_row_step(U, at, start, grad, lr, eta, alpha)
     host = torch.stack(dis_log + reg_log + bw_log).cpu().numpy().reshape(3, steps + 1)
     if var == 'd2d':
         for b in host[2]:
