@@ -795,5 +795,7 @@ int ure_host_kmeans_assign(const float *dist_nk, int64_t n, int32_t k, int64_t c
 #include "ultrare_attack.h"
 /* Adversarial attribute unlearning (csrc/adv.hip): the gradient of that probe's loss with respect to its input rows. */
 #include "ultrare_adv.h"
+/* Weighted matrix factorisation for implicit feedback (csrc/wmf.hip): the Gram matrix of a fixed table, weighted ridge rows that add it. */
+#include "ultrare_wmf.h"
 
 #endif /* ULTRARE_HIP_H */

@@ -289,6 +289,17 @@ _ADV_PROTOTYPES = {
 }
 ADV_EXPORTS = tuple(_ADV_PROTOTYPES)
 
+# include/ultrare_wmf.h (weighted matrix factorisation for implicit feedback, csrc/wmf.hip): a table of its own, as the header is;
+# tests/test_cpu_wmf.py holds the table, the header and the library to each other, tests/test_gpu_wmf.py runs both entries in guard zones.
+_WMF_PROTOTYPES = {
+    'ure_gram_scratch': (_i64, [_i64, ctypes.c_int]),
+    'ure_gram': (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _i64, _vp]),
+    'ure_wridge_rows_scratch': (_i64, [_i64, ctypes.c_int]),
+    'ure_wridge_rows': (ctypes.c_int, [_vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, ctypes.c_double, ctypes.c_double,
+                                       _vp, _vp, _vp, _i64, _vp]),
+}
+WMF_EXPORTS = tuple(_WMF_PROTOTYPES)
+
 _lib = None
 
 
@@ -305,7 +316,7 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_CSR_PAIR_PROTOTYPES, **_GCN_PROTOTYPES, **_BPR_PROTOTYPES, **_INF_PROTOTYPES, **_NMF_PROTOTYPES, **_NMF_RANK_PROTOTYPES,
-                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES, **_ATTACK_PROTOTYPES, **_ADV_PROTOTYPES}.items():
+                                  **_COMBINE_RANK_PROTOTYPES, **_ATTR_TRAIN_PROTOTYPES, **_ATTACK_PROTOTYPES, **_ADV_PROTOTYPES, **_WMF_PROTOTYPES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

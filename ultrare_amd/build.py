@@ -15,7 +15,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libultrare_hip.so')
-SOURCES = ['ure_common.hip', 'block_cache.cpp', 'mf_train.hip', 'tag_prep.hip', 'mf_eval.hip', 'mf_combine.hip', 'mf_ridge.hip', 'mf_recommend.hip', 'mf_rank.hip', 'pair_dist.hip', 'job_io.hip', 'perm_tags.hip', 'perm_chain.hip', 'mf_init.hip', 'ot.hip', 'ot_sinkhorn.hip', 'csr_group.hip', 'csr_kmeans.hip', 'gcn.hip', 'bpr.hip', 'influence.hip', 'nmf.hip', 'nmf_rank.hip', 'mf_combine_rank.hip', 'mmd.hip', 'attr_train.hip', 'attack.hip', 'adv.hip', 'ot_solver.cpp', 'host_rng.cpp', 'mt_jump.cpp', 'host_layout.cpp']
+SOURCES = ['ure_common.hip', 'block_cache.cpp', 'mf_train.hip', 'tag_prep.hip', 'mf_eval.hip', 'mf_combine.hip', 'mf_ridge.hip', 'mf_recommend.hip', 'mf_rank.hip', 'pair_dist.hip', 'job_io.hip', 'perm_tags.hip', 'perm_chain.hip', 'mf_init.hip', 'ot.hip', 'ot_sinkhorn.hip', 'csr_group.hip', 'csr_kmeans.hip', 'gcn.hip', 'bpr.hip', 'influence.hip', 'nmf.hip', 'nmf_rank.hip', 'mf_combine_rank.hip', 'mmd.hip', 'attr_train.hip', 'attack.hip', 'adv.hip', 'wmf.hip', 'ot_solver.cpp', 'host_rng.cpp', 'mt_jump.cpp', 'host_layout.cpp']
 # -amdgpu-kernarg-preload-count: gfx950 delivers the first kernel arguments in SGPRs at wave launch, which
 # removes the first of the step kernel's dependent scalar-load rounds (bench: 13.1 -> 12.6 us per launch)
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-shared', '-munsafe-fp-atomics',
@@ -45,7 +45,7 @@ def source_hash(extra=()):
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.startswith('.')) + \
-        [os.path.join(ROOT, 'include', h) for h in ('ultrare_hip.h', 'ultrare_csr_pair.h', 'ultrare_gcn.h', 'ultrare_bpr.h', 'ultrare_influence.h', 'ultrare_nmf.h', 'ultrare_nmf_rank.h', 'ultrare_combine_rank.h', 'ultrare_attr_train.h', 'ultrare_attack.h', 'ultrare_adv.h')]
+        [os.path.join(ROOT, 'include', h) for h in ('ultrare_hip.h', 'ultrare_csr_pair.h', 'ultrare_gcn.h', 'ultrare_bpr.h', 'ultrare_influence.h', 'ultrare_nmf.h', 'ultrare_nmf_rank.h', 'ultrare_combine_rank.h', 'ultrare_attr_train.h', 'ultrare_attack.h', 'ultrare_adv.h', 'ultrare_wmf.h')]
     for path in files:
         h.update(os.path.basename(path).encode() + b'\0')
         with open(path, 'rb') as f:

@@ -17,6 +17,11 @@ Differences from the reference, all defect fixes or optional additions (SURVEY.m
   +   InsParam(..., dis_type='nor', attr=[], dis_eta=1.0) optional in-training attribute unlearning ('d2d' / 'u2u': the per-batch MMD /
                                              Laplacian term over the user groups attr = (id1, id2), ultrare_amd/attr_train.py; needs
                                              model='lightgcn', gcn_layers=0 being plain MF; artifacts under LightGCN_<dis_type>_*)
+  +   InsParam(..., model='wmf', wmf_alpha=40.0, wmf_l2=0.1) optional implicit-feedback backbone (weighted MF by alternating least squares,
+                                             ultrare_amd/wmf.py, csrc/wmf.hip; artifacts under WMF_*): `epochs` counts sweeps, every triple is an
+                                             observation of confidence 1 + wmf_alpha * rating / 5, wmf_l2 is the ridge; both defaults are
+                                             UNTUNED.  optimizer='adam', loss='bpr', unlearn='influence', dis_type != 'nor', more than one rank
+                                             and given_model are refused; parallel=True warns and trains the shards one after the other
   +   dataset 'toy' is usable end to end     (the reference only has its batch size)
 """
 import os
@@ -42,12 +47,26 @@ DATASETS = {
 class InsParam(object):
     def __init__(self, dataset='toy', epochs=50, n_worker=24, layers=[32], n_group=2, del_per=2, del_type='test',
                  k=16, parallel=False, data_dir=None, optimizer='sgd', lr=None, model='mf', gcn_layers=2, loss='mse', unlearn='retrain',
-                 dis_type='nor', attr=[], dis_eta=1.0):
+                 dis_type='nor', attr=[], dis_eta=1.0, wmf_alpha=40.0, wmf_l2=0.1):
         if unlearn not in ('retrain', 'influence'):
             raise ValueError(f"unlearn {unlearn!r}: 'retrain' or 'influence'")
         from .attr_train import DIS_TYPES
         if dis_type not in DIS_TYPES:
             raise ValueError(f"dis_type {dis_type!r}: one of {DIS_TYPES}")
+        from .wmf import DEFAULT_ALPHA, DEFAULT_L2, check_backbone, check_wmf_args
+        if model == 'wmf':                      # implicit-feedback ALS (ultrare_amd/wmf.py): what it cannot be combined with, by name
+            if optimizer not in ('sgd', 'adam'):
+                raise ValueError(f"optimizer {optimizer!r}: 'sgd' or 'adam'")
+            if loss not in ('mse', 'bpr'):
+                raise ValueError(f"loss {loss!r}: 'mse' or 'bpr'")
+            check_backbone(optimizer, loss, unlearn, dis_type)
+            wmf_alpha, wmf_l2, _, _ = check_wmf_args(wmf_alpha, wmf_l2, 0.0, epochs if isinstance(epochs, int) and epochs >= 0 else 0)
+            if wmf_alpha != DEFAULT_ALPHA:      # (set only off the defaults, as the other options are)
+                self.wmf_alpha = wmf_alpha
+            if wmf_l2 != DEFAULT_L2:
+                self.wmf_l2 = wmf_l2
+        elif wmf_alpha != DEFAULT_ALPHA or wmf_l2 != DEFAULT_L2:
+            raise ValueError(f"wmf_alpha and wmf_l2 go with model='wmf', not model={model!r}")
         if unlearn == 'influence' and dis_type != 'nor':
             raise ValueError(f"unlearn='influence' takes Newton steps on the plain MSE objective: dis_type={dis_type!r} is not supported with it")
         if unlearn == 'influence':
@@ -76,8 +95,8 @@ class InsParam(object):
         self.optimizer = optimizer  # 'adam': momentum is not used; betas / eps are torch.optim.Adam's defaults
         self.betas = (0.9, 0.999)
         self.eps = 1e-8
-        if model not in ('mf', 'lightgcn', 'nmf'):
-            raise ValueError(f"model {model!r}: 'mf', 'lightgcn' or 'nmf'")
+        if model not in ('mf', 'lightgcn', 'nmf', 'wmf'):
+            raise ValueError(f"model {model!r}: 'mf', 'lightgcn', 'nmf' or 'wmf'")
         if model == 'nmf':
             from .nmf import check_layers as check_stack
             if optimizer != 'sgd':
@@ -93,7 +112,7 @@ class InsParam(object):
             raise ValueError("loss='bpr' trains with model='lightgcn' only: --model lightgcn --gcn-layers 0 is BPR-MF")
         self.loss = loss                        # 'mse' (the reference's), or 'bpr' (ultrare_amd/bpr.py)
         from .lightgcn import check_layers
-        self.model = model                      # the backbone: 'mf', 'lightgcn' (ultrare_amd/lightgcn.py) or 'nmf' (ultrare_amd/nmf.py)
+        self.model = model                      # the backbone: 'mf', 'lightgcn' (ultrare_amd/lightgcn.py), 'nmf' (ultrare_amd/nmf.py) or 'wmf' (ultrare_amd/wmf.py)
         self.gcn_layers = check_layers(gcn_layers)   # propagations per side of the 'lightgcn' backbone (`layers` above is the 'nmf' backbone's stack)
 
         if dis_type != 'nor':                   # the per-batch attribute term (ultrare_amd/attr_train.py); the groups are checked below
@@ -322,7 +341,7 @@ class Instance(object):
     def _model(self):
         """(model_type, artifact prefix) of the backbone the parameters name."""
         model = getattr(self.param, 'model', 'mf')
-        prefix = {'mf': 'MF_', 'lightgcn': 'LightGCN_', 'nmf': 'NMF_'}[model]
+        prefix = {'mf': 'MF_', 'lightgcn': 'LightGCN_', 'nmf': 'NMF_', 'wmf': 'WMF_'}[model]
         prefix += 'bpr_' if getattr(self.param, 'loss', 'mse') == 'bpr' else ''
         dis_type = getattr(self.param, 'dis_type', 'nor')
         return model, prefix + (dis_type + '_' if dis_type != 'nor' else '')

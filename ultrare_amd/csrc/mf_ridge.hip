@@ -20,29 +20,12 @@
 //               spread over the 256 threads (2 barriers).
 //   solve       thread c < k carries entry c of the right-hand side in a register through R^T y = b and R x = y, column by
 //               column (1 barrier per column each).
+// The shape, the staging of a tile and the factor / solve / store stages are ridge_solve.h's, shared with wmf.hip.
 // No floating-point atomics and no sum that crosses workgroups: a row's bytes depend on its own segment alone -- not on the
 // stream, on `order`, or on what else is in the call.
-#include "ure_internal.h"
-
-#include <cfloat>
-#include <cmath>
+#include "ridge_solve.h"
 
 namespace ure {
-
-constexpr int kRrMaxD = 128;             // a padded 256 would need a 257 KiB triangle: refused
-
-template <int D>
-struct RrShape {
-    static constexpr int TB = D >= 16 ? D / 16 : 1;                 // edge of a thread's register block of G
-    static constexpr int NB = D / TB;                               // blocks per side: 16, or D below 16
-    static constexpr int NTRI = NB * (NB + 1) / 2;                  // threads that own a block (136 of 256 at D >= 16)
-    static constexpr int T = D <= 32 ? 64 : 2048 / D;               // rows per tile: at most 16 KiB of doubles
-    static constexpr int TRI = D * (D + 1) / 2;
-    static constexpr int MAIN = T * D > TRI ? T * D : TRI;          // the tile, later the packed triangle
-    static constexpr int DOUBLES = MAIN + T + 3 * D;                // + ratings | y, x | b | sqrt of the pivots
-};
-
-__device__ __forceinline__ int tri_row(int a, int k) { return a * k - a * (a - 1) / 2; }     // index of (a, a); (a, b) is + b - a
 
 template <int D>
 __global__ __launch_bounds__(kBlock) void ridge_rows_kernel(const float *__restrict__ F, int64_t n_fixed, int k,
@@ -51,7 +34,7 @@ __global__ __launch_bounds__(kBlock) void ridge_rows_kernel(const float *__restr
                                                             double l2, double l2_n, float *__restrict__ X, int32_t *__restrict__ status)
 {
     using S = RrShape<D>;
-    constexpr int TB = S::TB, NB = S::NB, NTRI = S::NTRI, T = S::T, Q = D / 4;
+    constexpr int TB = S::TB, T = S::T, Q = D / 4;
     extern __shared__ __attribute__((aligned(16))) char rr_lds[];
     double *tile = reinterpret_cast<double *>(rr_lds);
     double *rt = tile + S::MAIN, *ys = rt + T, *bs = ys + D, *dg = bs + D;
@@ -68,15 +51,9 @@ __global__ __launch_bounds__(kBlock) void ridge_rows_kernel(const float *__restr
     }
 
     // the block this thread owns: row-major over the upper triangle of NB x NB blocks, then the NB blocks of b
-    const bool is_g = tid < NTRI, is_b = tid >= NTRI && tid < NTRI + NB;
-    int bi = 0, bj = 0;
-    if (is_g) {
-        int r = tid;
-        while (r >= NB - bi) { r -= NB - bi; ++bi; }
-        bj = bi + r;
-    } else if (is_b) {
-        bi = bj = tid - NTRI;
-    }
+    bool is_g, is_b;
+    int bi, bj;
+    rr_owner<D>(tid, is_g, is_b, bi, bj);
     double acc[TB][TB];
 #pragma unroll
     for (int a = 0; a < TB; ++a)
@@ -91,16 +68,13 @@ __global__ __launch_bounds__(kBlock) void ridge_rows_kernel(const float *__restr
         for (int q = tid; q < cnt * Q; q += kBlock) {
             const int t = q / Q, c = (q % Q) * 4;
             const int64_t i = idx[t0 + t];
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i >= 0 && i < n_fixed)
-                v = ldg_f4(F + (size_t)i * D + c);
-            else
-                bad = 1;
             double *dst = tile + t * D + c;
-            dst[0] = c + 0 < k ? (double)v.x : 0.0;
-            dst[1] = c + 1 < k ? (double)v.y : 0.0;
-            dst[2] = c + 2 < k ? (double)v.z : 0.0;
-            dst[3] = c + 3 < k ? (double)v.w : 0.0;
+            if (i >= 0 && i < n_fixed) {
+                rr_stage4<D>(F, i, c, k, dst);
+            } else {
+                dst[0] = dst[1] = dst[2] = dst[3] = 0.0;
+                bad = 1;
+            }
         }
         if (tid < cnt) rt[tid] = (double)val[t0 + tid];
         __syncthreads();
@@ -146,50 +120,8 @@ __global__ __launch_bounds__(kBlock) void ridge_rows_kernel(const float *__restr
     }
     __syncthreads();
 
-    // ---- factor: G = R^T R, R over G's upper triangle (the diagonal of R in dg; G's own diagonal keeps the pivots)
-    bool failed = bad != 0;
-    for (int j = 0; j < k && !failed; ++j) {
-        const int rj = tri_row(j, k);
-        const double p = G[rj];                            // every thread reads the same word: the branch is uniform
-        if (!(p > 0.0 && p <= DBL_MAX)) {
-            failed = true;
-            break;
-        }
-        const double sq = sqrt(p);
-        if (tid == 0) dg[j] = sq;
-        for (int b = j + 1 + tid; b < k; b += kBlock) G[rj + b - j] = G[rj + b - j] / sq;
-        __syncthreads();
-        for (int a = j + 1 + (tid >> 4); a < k; a += kBlock / 16) {
-            const double ra = G[rj + a - j];
-            double *ga = G + tri_row(a, k) - a;
-            for (int b = a + (tid & 15); b < k; b += 16) ga[b] = fma(-ra, G[rj + b - j], ga[b]);
-        }
-        __syncthreads();
-    }
-
-    // ---- solve: R^T y = b forwards, R x = y backwards; thread c carries entry c
-    double v = 0.0;
-    if (!failed) {
-        if (tid < k) v = bs[tid];
-        for (int j = 0; j < k; ++j) {
-            if (tid == j) ys[j] = v / dg[j];
-            __syncthreads();
-            if (tid > j && tid < k) v = fma(-G[tri_row(j, k) + tid - j], ys[j], v);
-        }
-        if (tid < k) v = ys[tid];                          // (its own store)
-        for (int j = k - 1; j >= 0; --j) {
-            if (tid == j) ys[j] = v / dg[j];
-            __syncthreads();
-            if (tid < j) v = fma(-G[tri_row(tid, k) + j - tid], ys[j], v);
-        }
-        v = tid < k ? ys[tid] : 0.0;
-    }
-    if (__syncthreads_or(tid < k && !(fabs(v) <= DBL_MAX))) failed = true;
-    for (int c = tid; c < D; c += kBlock) xrow[c] = c >= k ? 0.f : failed ? __builtin_nanf("") : (float)ys[c];
-    if (failed && tid == 0) {
-        atomicAdd(status, 1);
-        atomicMin(reinterpret_cast<unsigned *>(status) + 1, (unsigned)s);
-    }
+    // ---- factor, solve, store (ridge_solve.h)
+    rr_factor_solve_store<D>(G, bs, ys, dg, k, bad != 0, xrow, status, s);
 }
 
 template <int D>

@@ -1654,6 +1654,90 @@ def ridge_rows(F, d, k, segs, l2, l2_n=0.0, stream=None, order='longest'):
 
 
 # ---------------------------------------------------------------------------
+# Weighted matrix factorisation for implicit feedback (csrc/wmf.hip, include/ultrare_wmf.h; the contract is wmf.py)
+# ---------------------------------------------------------------------------
+def _fixed_table(F, d, k, who):
+    from .ridge import MAX_D
+    if d > MAX_D:
+        raise ValueError(f'{who} serves padded widths up to {MAX_D}: the float64 triangle of width {d} does not fit in LDS')
+    if not 1 <= k <= d or d != pad_dim(d):
+        raise ValueError(f'need 1 <= k <= d with d a padded width, not k = {k}, d = {d}')
+    if not (torch.is_tensor(F) and F.is_cuda):
+        raise nv.NativeError(f'{who} runs on the HIP device only (no CPU fallback)')
+    if not (F.dtype == torch.float32 and F.dim() == 2 and F.shape[1] == d and F.is_contiguous() and F.shape[0] >= 1):
+        raise ValueError(f'F must be a contiguous float32 [n, {d}] tensor')
+
+
+def gram(F, d, k, stream=None):
+    """ure_gram: the Gram matrix of the first k columns of the device table F [n, d] as the packed upper triangle, float64
+    [k (k + 1) / 2] on the device -- wmf.gram_ref's bytes (a two-level chain: 256-row chunks, then the chunks in order), on any
+    stream.  wmf.tri_unpack gives the square matrix.  Nothing is read back."""
+    _fixed_table(F, d, k, 'gram')
+    n = int(F.shape[0])
+    need = int(nv.lib().ure_gram_scratch(n, k))
+    if need < 0:
+        raise ValueError(f'gram: n = {n}, k = {k} is refused')
+    G0 = torch.empty(k * (k + 1) // 2, dtype=torch.float64, device=F.device)
+    scratch = torch.empty(need, dtype=torch.uint8, device=F.device)
+    nv.check(nv.lib().ure_gram(nv.ptr(F), n, d, k, nv.ptr(G0), nv.ptr(scratch), need, nv.stream_handle(stream)), 'ure_gram')
+    if stream is not None:
+        scratch.record_stream(stream)
+    return G0
+
+
+def confidence(val, alpha):
+    """(wg, wb) float32 on the device of the float32 ratings `val` -- wmf.confidence_ref's bytes: wg = fl32(alpha32 * r),
+    wb = fl32(1 + wg); two elementwise float32 operations, each rounded once."""
+    a = torch.tensor(float(alpha), dtype=torch.float32, device=val.device)
+    wg = torch.mul(val, a)
+    return wg, torch.add(wg, torch.ones((), dtype=torch.float32, device=val.device))
+
+
+def wridge_rows(F, d, k, segs, wg, wb, G0, l2, l2_n=0.0, stream=None, order='longest'):
+    """ure_wridge_rows: ridge_rows with a confidence per entry and a Gram matrix added to every system.  X [m, d] float32, row s
+    the solution of (G0 + sum_j wg_j f_j f_j^T + (l2 + l2_n n_s) I) x = sum_j wb_j f_j over segment s of `segs` (a SegmentSet; its
+    ratings are not read) against the first k columns of the fixed device table F [n_fixed, d].  wg, wb: float32 device tensors
+    [nnz] in the set's CSR order (confidence(segs.val, alpha)); G0: gram()'s packed triangle, or None for no added matrix.  order,
+    the status read-back and the ValueError of a failed segment are ridge_rows's."""
+    from .ridge import check_ridge_args
+    l2, l2_n = check_ridge_args(l2, l2_n)
+    _fixed_table(F, d, k, 'wridge_rows')
+    if segs.max_other >= F.shape[0]:
+        raise ValueError(f'ids up to {segs.max_other} outside the fixed table of {F.shape[0]} rows')
+    dev = F.device
+    for name, w in (('wg', wg), ('wb', wb)):
+        if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 1 and w.is_contiguous() and w.numel() == segs.nnz):
+            raise ValueError(f'{name} must be a contiguous float32 device tensor of {segs.nnz} values, one per entry in CSR order')
+    if segs.nnz == 0:                                       # (a kernel argument must not be NULL)
+        wg = wb = torch.zeros(1, dtype=torch.float32, device=dev)
+    if G0 is not None and not (torch.is_tensor(G0) and G0.is_cuda and G0.dtype == torch.float64 and G0.is_contiguous() and G0.numel() == k * (k + 1) // 2):
+        raise ValueError(f'G0 must be a contiguous float64 device tensor of {k * (k + 1) // 2} values (the packed triangle of width {k}), or None')
+    if isinstance(order, str):
+        if order != 'longest':
+            raise ValueError(f"order must be 'longest', None or a list of segments, not {order!r}")
+        order = segs.order
+    elif order is not None and not torch.is_tensor(order):
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.shape != (segs.m,) or (np.sort(order) != np.arange(segs.m)).any():
+            raise ValueError('order must list every segment once')
+        order = torch.from_numpy(order).to(dev)
+    X = torch.empty(segs.m, d, dtype=torch.float32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    nv.check(nv.lib().ure_wridge_rows(nv.ptr(F), int(F.shape[0]), d, k, nv.ptr(segs.off), nv.ptr(segs.idx), nv.ptr(wg), nv.ptr(wb), segs.m,
+                                      nv.ptr(order), nv.ptr(G0), l2, l2_n, nv.ptr(X), nv.ptr(status), None, 0, nv.stream_handle(stream)),
+             'ure_wridge_rows')
+    if stream is not None:
+        stream.synchronize()
+    failed, first = (int(v) for v in status.cpu().numpy())
+    if failed:
+        err = ValueError(f'wridge_rows: {failed} of {segs.m} systems are not positive definite, first segment {first} '
+                         f'({int(segs.counts[first])} entries, width {k}) at l2 = {l2:g}, l2_n = {l2_n:g}: a larger l2 makes them definite')
+        err.X, err.failed, err.segment = X, failed, first
+        raise err
+    return X
+
+
+# ---------------------------------------------------------------------------
 # OT grouping on the sparse rating matrix (csrc/csr_group.hip; the contract is sparse_group.py)
 # ---------------------------------------------------------------------------
 class CsrSet:

@@ -28,6 +28,12 @@ Same flags, defaults and assertions; additions are optional:
                  --layer L0 L1 .. Lm (the reference's "setting of layers"; powers of two, 1 .. 4 fully connected layers), trained shard
                  after shard with SGD on the MSE loss, artifacts under NMF_* with the four tables as user_mat_mf / user_mat_mlp /
                  item_mat_mf / item_mat_mlp.  'mf' and 'lightgcn' do not read --layer
+  --model wmf    weighted matrix factorisation for implicit feedback by alternating least squares (ultrare_amd/wmf.py, csrc/wmf.hip,
+                 DESIGN 4.32): every rating is an observation of confidence 1 + --wmf-alpha * rating / 5 (default 40, UNTUNED), every other
+                 pair counts with confidence 1 and preference 0; --wmf-l2 is the ridge (default 0.1, UNTUNED); --epoch counts sweeps.
+                 Trained shard after shard, artifacts under WMF_*; train_loss is the objective over all pairs, the RMSE columns mean
+                 little (a preference score against rating / 5): judge the result with rank_eval.  Refuses --optimizer adam, --loss bpr,
+                 --unlearn influence, --dis-type d2d / u2u and more than one rank
   --loss         'mse' (default: the reference's MSELoss(sum) on the rating) or 'bpr': the pairwise BPR loss, one negative per triple and
                  epoch drawn on the device (ultrare_amd/bpr.py, csrc/bpr.hip).  Needs --model lightgcn (--gcn-layers 0 is
                  BPR-MF); artifacts under LightGCN_bpr_*; train_loss is the mean batch loss; judge the result with rank_eval
@@ -65,7 +71,9 @@ parser.add_argument('--parallel', type=int, default=1, help='1 (default): shards
 parser.add_argument('--group-type', type=str, default='emb-ot', help="'emb-ot' (reference), 'uniform', or 'rating-ot' (OT groups), 'rating-bkmeans', 'rating-bkmedoids', 'rating-blpa' (balanced k-means / k-medoids / label propagation groups) on the sparse rating matrix, no --group 0 run needed")
 parser.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adam'], help="'sgd' (reference) or 'adam'")
 parser.add_argument('--lr', type=float, default=None, help='learning rate (default 0.001)')
-parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn', 'nmf'], help="'mf' (reference), 'lightgcn' or 'nmf' (NeuMF; its MLP is --layer)")
+parser.add_argument('--model', type=str, default='mf', choices=['mf', 'lightgcn', 'nmf', 'wmf'], help="'mf' (reference), 'lightgcn', 'nmf' (NeuMF; its MLP is --layer) or 'wmf' (implicit-feedback ALS; --epoch counts sweeps)")
+parser.add_argument('--wmf-alpha', type=float, default=40.0, help="confidence slope of --model wmf: c = 1 + alpha * rating / 5 (default 40: untuned)")
+parser.add_argument('--wmf-l2', type=float, default=0.1, help="ridge strength of --model wmf, > 0 (default 0.1: untuned)")
 parser.add_argument('--gcn-layers', type=int, default=2, help="propagations per side of the 'lightgcn' backbone (0 .. 8)")
 parser.add_argument('--loss', type=str, default='mse', choices=['mse', 'bpr'], help="'mse' (reference) or 'bpr' (needs --model lightgcn)")
 parser.add_argument('--unlearn', type=str, default='retrain', choices=['retrain', 'influence'], help="'retrain' (reference) or 'influence' (Newton steps, no retraining; --model mf --loss mse)")
@@ -180,7 +188,7 @@ def main(argv=None):
                      k=args.k, parallel=bool(args.parallel), data_dir=args.data_dir, optimizer=args.optimizer, lr=args.lr,
                      model=args.model, gcn_layers=args.gcn_layers, loss=args.loss, unlearn=args.unlearn,
                      dis_type=args.dis_type, attr=attr_groups(args.dis_type, None if (attack is not None or adv is not None) and args.dis_type == 'nor' else args.attr_file),
-                     dis_eta=args.dis_eta)
+                     dis_eta=args.dis_eta, wmf_alpha=args.wmf_alpha, wmf_l2=args.wmf_l2)
     if attack is not None:
         # the groups against the table the attacker will read, before any training: a bad file costs no run
         from .attack import check_attack_args

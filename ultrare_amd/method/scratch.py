@@ -118,9 +118,16 @@ class Scratch(object):
                     'total_hr': [],
                     'time': []}
 
-        if self.model_type not in ('mf', 'lightgcn', 'nmf'):
-            raise NotImplementedError("model_type is 'mf' on the published path (config.py:185-199), 'lightgcn' (ultrare_amd/lightgcn.py) or 'nmf' "
-                                      "(ultrare_amd/nmf.py)")
+        if self.model_type not in ('mf', 'lightgcn', 'nmf', 'wmf'):
+            raise NotImplementedError("model_type is 'mf' on the published path (config.py:185-199), 'lightgcn' (ultrare_amd/lightgcn.py), 'nmf' "
+                                      "(ultrare_amd/nmf.py) or 'wmf' (ultrare_amd/wmf.py)")
+        if self.model_type == 'wmf':
+            # weighted MF for implicit feedback (utils.WmfSweeps): alternating least squares, `epochs` counts sweeps; no optimizer, no
+            # other loss, no per-batch term (refused by name before the generic checks below)
+            from ..wmf import DEFAULT_ALPHA, DEFAULT_L2, check_backbone, check_wmf_args
+            check_backbone(self.optimizer, getattr(param, 'loss', 'mse'), getattr(param, 'unlearn', 'retrain'), self.dis_type)
+            self.wmf_alpha, self.wmf_l2, _, _ = check_wmf_args(getattr(param, 'wmf_alpha', DEFAULT_ALPHA), getattr(param, 'wmf_l2', DEFAULT_L2), 0.0,
+                                                               self.epochs)
         if self.model_type == 'nmf':
             # the neural backbone (engine.NmfJob): SGD on the MSE loss only; `layers` is the MLP stack [L0, .., Lm]
             from ..nmf import check_layers as check_stack
@@ -207,6 +214,8 @@ class Scratch(object):
             n_train, device = job.graph.N, job.device
         elif self.model_type == 'nmf':
             return self._train_nmf(train_data, test_data, test_total, has_total, verbose, save_dir, id, given_model)
+        elif self.model_type == 'wmf':
+            return self._train_wmf(train_data, test_data, test_total, has_total, verbose, save_dir, id, given_model)
         else:
             shard, init, perms = prepare_shard(train_data, self.n_user, self.n_item, self.k, self.epochs, has_total, given_model)
             batch = as_loader(train_data).batch_size
@@ -318,6 +327,42 @@ class Scratch(object):
                     self.log[key].append(total[c])
         model = NMF.from_tables(*(t.clone() for t in job.params()), self.k, self.layers)
         job.close()
+        self.save(model, save_dir, id)
+        return model
+
+    def _train_wmf(self, train_data, test_data, test_total, has_total, verbose, save_dir, id, given_model):
+        """_train for the 'wmf' backbone: `epochs` sweeps of implicit ALS (utils.WmfSweeps) from the MF request's own draws
+        (rng.mf_init, as the 'lightgcn' backbone takes them); no other draw is made, and nothing depends on a schedule or a learning
+        rate, so a retrained shard is a function of its remaining data and the seed alone.  After every sweep the two tests of
+        scratch.py:83-97 on the models trained before (Sisa) and the current tables; train_loss is the objective over all pairs
+        (wmf.objective_ref).  The test RMSE compares a preference score with rating / 5 and means little, as under BPR: judge the
+        model with rank_eval."""
+        if not (_is_empty(given_model) or given_model == ''):
+            raise ValueError("given_model is not supported with model_type='wmf': the sweeps start from rng.mf_init")
+        U0, V0 = rng.mf_init(self.n_user, self.n_item, self.k, device=engine._device())
+        dev = engine._device()
+        U, V, d = padded_tables(MF.from_tables(U0.to(dev), V0.to(dev)))
+        job = utils.WmfSweeps(U, V, d, self.k, utils._rating_triple(train_data), self.wmf_alpha, self.wmf_l2, 0.0)
+        test_ev = as_loader(test_data).eval_set()
+        total_ev = as_loader(test_total).eval_set() if has_total else None
+        before = [padded_tables(m)[:2] for m in self._models_before()]
+        for t in range(self.epochs):
+            epoch_start = time.time()
+            job.sweep()
+            models = before + [(job.U, job.V)]
+            test = test_ev.evaluate(models, d)
+            total = total_ev.evaluate(models, d) if has_total else test
+            train_loss = job.objective()
+            epoch_time = time.strftime('%H:%M:%S', time.gmtime(time.time() - epoch_start))
+            print_epoch(verbose, t, self.epochs, train_loss, test, total, has_total, epoch_time)
+            self.log['train_loss'].append(train_loss)
+            for c, key in enumerate(('test_rmse', 'test_ndcg', 'test_hr')):
+                self.log[key].append(test[c])
+            self.log['time'].append(epoch_time)
+            if has_total:
+                for c, key in enumerate(('total_rmse', 'total_ndcg', 'total_hr')):
+                    self.log[key].append(total[c])
+        model = MF.from_tables(*job.tables())
         self.save(model, save_dir, id)
         return model
 

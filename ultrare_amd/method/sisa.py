@@ -198,9 +198,9 @@ class Sisa(Scratch):
         self.n_group = n_group
         self.group_index = group_index
         self.parallel = bool(getattr(param, 'parallel', False))
-        if self.model_type in ('lightgcn', 'nmf'):
+        if self.model_type in ('lightgcn', 'nmf', 'wmf'):
             self._gcn_one_rank()
-            if self.parallel:           # a GcnJob / NmfJob holds one shard: the shards train one after the other
+            if self.parallel:           # a GcnJob / NmfJob / WmfSweeps holds one shard: the shards train one after the other
                 import warnings
                 warnings.warn(f"model_type={self.model_type!r} trains its shards one after the other: parallel is ignored")
                 self.parallel = False
@@ -211,7 +211,7 @@ class Sisa(Scratch):
 
     def _gcn_one_rank(self):
         dist = _dist()
-        if self.model_type in ('lightgcn', 'nmf') and dist is not None and dist.get_world_size() > 1:
+        if self.model_type in ('lightgcn', 'nmf', 'wmf') and dist is not None and dist.get_world_size() > 1:
             raise ValueError(f"model_type={self.model_type!r} runs on one rank, not {dist.get_world_size()}")
 
     def _refuse_nmf(self, who):

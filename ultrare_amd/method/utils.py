@@ -12,6 +12,8 @@ the reference), backed by the HIP engine.
   fold_in      (new)             rows for new users against frozen item tables (one batched ridge solve on the device)
   als_sweeps   (new)             alternating least squares from a model's tables by the same solve
   trainer_l2   (new)             the ridge strength at which fold_in gives the trainer's own fixed point
+  wmf_sweeps   (new)             implicit-feedback ALS (weighted MF): als_sweeps with a confidence per entry and the Gram trick
+  wmf_fold_in  (new)             fold_in under that objective: the user half alone, against frozen items
   computeNDCG / computeDCG  utils.py:190-210
   ot_cluster   utils.py:628-656  OT balanced clustering (exact EMD; solver='sinkhorn': entropic OT on the device)
   kmeans       utils.py:354-418  (balanced) k-means, a comparison clusterer
@@ -378,6 +380,113 @@ def als_sweeps(model, train_data, l2, l2_n=0.0, sweeps=1):
         V = engine.ridge_rows(U, d, k, by_item, l2, l2_n)
         objectives.append(_ridge_objective_dev(U, V, k, pairs, reg_u, reg_v))
     return MF.from_tables(U[:, :k].clone().contiguous(), V[:, :k].clone().contiguous()), np.asarray(objectives, dtype=np.float64)
+
+
+class WmfSweeps:
+    """The device state of implicit ALS on one rating set (ultrare_amd/wmf.py): the two CSRs with their confidence
+    weights, the current tables and their Gram matrices.  sweep() runs the user half (every user row against V and the Gram
+    matrix of ALL of V: engine.gram, engine.wridge_rows) and then the item half against the new U; objective() is the contract's J
+    in float64 on the device from the Gram matrices at hand (a diagnostic, not a hot path).  wmf_sweeps and Scratch's 'wmf'
+    backbone drive it.  No RNG is drawn."""
+
+    def __init__(self, U, V, d, k, triple, alpha, l2, l2_n):
+        uid, iid, r = triple
+        self.d, self.k, self.l2, self.l2_n = d, k, l2, l2_n
+        dev = U.device
+        self.by_user = engine.SegmentSet(uid, iid, r, int(U.shape[0]), device=dev)
+        self.by_item = engine.SegmentSet(iid, uid, r, int(V.shape[0]), device=dev)
+        self.w_user = engine.confidence(self.by_user.val[:self.by_user.nnz], alpha)
+        self.w_item = engine.confidence(self.by_item.val[:self.by_item.nnz], alpha)
+        self.uid, self.iid, val = engine.upload_many([uid.astype(np.int32), iid.astype(np.int32), r], dev)
+        self.w_pair = engine.confidence(val, alpha)
+        self.reg_u = torch.from_numpy(l2 + l2_n * self.by_user.counts.astype(np.float64)).to(dev)
+        self.reg_v = torch.from_numpy(l2 + l2_n * self.by_item.counts.astype(np.float64)).to(dev)
+        a, b = np.triu_indices(k)
+        self.twice = torch.from_numpy(np.where(a == b, 1.0, 2.0)).to(dev)          # the packed triangle holds (a, b), a < b, once
+        self.U, self.V = U, V
+        self.GU, self.GV = engine.gram(U, d, k), engine.gram(V, d, k)
+
+    def half_user(self):
+        self.U = engine.wridge_rows(self.V, self.d, self.k, self.by_user, *self.w_user, self.GV, self.l2, self.l2_n)
+        self.GU = engine.gram(self.U, self.d, self.k)
+
+    def half_item(self):
+        self.V = engine.wridge_rows(self.U, self.d, self.k, self.by_item, *self.w_item, self.GU, self.l2, self.l2_n)
+        self.GV = engine.gram(self.V, self.d, self.k)
+
+    def sweep(self):
+        self.half_user()
+        self.half_item()
+
+    def objective(self, chunk=1 << 20):
+        k, (wg, wb) = self.k, self.w_pair
+        tot = (self.twice * self.GU * self.GV).sum()
+        for a in range(0, self.uid.numel(), chunk):
+            u, i = self.uid[a:a + chunk].long(), self.iid[a:a + chunk].long()
+            s = (self.U[u, :k].double() * self.V[i, :k].double()).sum(dim=1)
+            g, b = wg[a:a + chunk].double(), wb[a:a + chunk].double()
+            tot = tot + (g * s * s - 2.0 * b * s + b).sum()
+        tot = tot + (self.reg_u * (self.U[:, :k].double() ** 2).sum(dim=1)).sum() + (self.reg_v * (self.V[:, :k].double() ** 2).sum(dim=1)).sum()
+        return float(tot)
+
+    def tables(self):
+        """Copies of the current (U [n_user, k], V [n_item, k])."""
+        return self.U[:, :self.k].clone().contiguous(), self.V[:, :self.k].clone().contiguous()
+
+
+def wmf_sweeps(model, train_data, alpha, l2, l2_n=0.0, sweeps=1):
+    """Weighted matrix factorisation for implicit feedback by alternating least squares from `model`'s tables on the device
+    (ultrare_amd/wmf.py), the implicit twin of als_sweeps.  Every training triple is an observation of preference 1
+    and confidence 1 + alpha * rating / 5; every other (user, item) pair counts with preference 0 and confidence 1.  Each sweep
+    solves every user row against V and then every item row against the new U (WmfSweeps); a row without observations becomes
+    zero.  Returns (MF.from_tables(U, V), objectives): the float64 objective over ALL pairs (wmf.objective_ref) before the first
+    and after every half sweep, 1 + 2 * sweeps numbers computed on the device.  ValueError for bad settings before any device
+    work (wmf.check_wmf_args: l2 must be > 0) and for the 'nmf' backbone.  No RNG is drawn."""
+    from ..wmf import check_wmf_args
+    alpha, l2, l2_n, sweeps = check_wmf_args(alpha, l2, l2_n, sweeps)
+    refuse_nmf(model, 'wmf_sweeps')
+    U, V, d = padded_tables(model)
+    job = WmfSweeps(U, V, d, int(model.k), _rating_triple(train_data), alpha, l2, l2_n)
+    objectives = [job.objective()]
+    for _ in range(sweeps):
+        job.half_user()
+        objectives.append(job.objective())
+        job.half_item()
+        objectives.append(job.objective())
+    return MF.from_tables(*job.tables()), np.asarray(objectives, dtype=np.float64)
+
+
+def wmf_fold_in(models, data, alpha, l2, l2_n=0.0, item_table='mean'):
+    """fold_in under the implicit-feedback objective of wmf_sweeps: the user half alone, against frozen items.  User u's row
+    solves (V^T V + sum_j (c_j - 1) v_j v_j^T + (l2 + l2_n n_u) I) x = sum_j c_j v_j over u's observations, c_j = 1 + alpha *
+    rating / 5, with V^T V the Gram matrix of the WHOLE item table (engine.gram, engine.wridge_rows).  data, item_table and the
+    return value -- (users ascending int64, rows [n, k] float32 on the device) -- are fold_in's; the rows equal a user half sweep of
+    wmf_sweeps on those users against that table.  ValueError for bad settings before any device work."""
+    from ..wmf import check_wmf_args
+    alpha, l2, l2_n, _ = check_wmf_args(alpha, l2, l2_n, 1)
+    S = len(models)
+    refuse_nmf(models, 'wmf_fold_in')
+    if S < 1:
+        raise ValueError('wmf_fold_in needs at least one model')
+    _check_item_table(item_table, S)
+    uid, iid, r = _rating_triple(data)
+    if len(uid) and (uid.min() < 0 or iid.min() < 0):
+        raise ValueError('negative user or item id')
+    users, seg = np.unique(uid, return_inverse=True)
+    if isinstance(item_table, str):
+        tabs = [padded_tables(m) for m in models]
+        d = tabs[0][2]
+        acc = tabs[0][1].double()
+        for _, V, _ in tabs[1:]:
+            acc = acc + V.double()
+        V = (acc / S).float().contiguous()
+    else:
+        _, V, d = padded_tables(models[int(item_table)])
+    k = int(models[0].k)
+    segs = engine.SegmentSet(seg, iid, r, len(users), device=V.device)
+    wg, wb = engine.confidence(segs.val[:segs.nnz], alpha)
+    X = engine.wridge_rows(V, d, k, segs, wg, wb, engine.gram(V, d, k), l2, l2_n)
+    return users.astype(np.int64), X[:, :k].contiguous()
 
 
 def _ranking_weights(combiner, models, users, who):

@@ -27,6 +27,10 @@ to resident shards -- and stays behind engine.TrainJob.
                                                         (new)             (pred, sse partials) with fitted weight rows
     torch.ops.ultrare.ridge_rows(F, off, idx, val, k, l2, l2_n)
                                                         (new)             the ridge solution of every CSR segment against F
+    torch.ops.ultrare.gram(F, k)                        (new)             the packed upper triangle (float64) of F[:, :k]^T F[:, :k]
+    torch.ops.ultrare.wridge_rows(F, off, idx, wg, wb, G0, k, l2, l2_n)
+                                                        (new)             ridge_rows with a confidence per entry and a Gram matrix
+                                                                          added to every system (ultrare_amd/wmf.py)
     torch.ops.ultrare.csr_cost(row_off, col, val, Ct, k)
                                                         (new)             [k, n] squared distances of CSR rows to the
                                                                           centroids held transposed in Ct [n_item, ldc]
@@ -303,6 +307,31 @@ def ridge_rows(F: torch.Tensor, off: torch.Tensor, idx: torch.Tensor, val: torch
 
 @ridge_rows.register_fake
 def _(F, off, idx, val, k, l2, l2_n):
+    return F.new_empty(off.numel() - 1, F.shape[1])
+
+
+@torch.library.custom_op('ultrare::gram', mutates_args=())
+def gram(F: torch.Tensor, k: int) -> torch.Tensor:
+    _dev(F)
+    return engine.gram(F, F.shape[1], k)
+
+
+@gram.register_fake
+def _(F, k):
+    return F.new_empty(k * (k + 1) // 2, dtype=torch.float64)
+
+
+@torch.library.custom_op('ultrare::wridge_rows', mutates_args=())
+def wridge_rows(F: torch.Tensor, off: torch.Tensor, idx: torch.Tensor, wg: torch.Tensor, wb: torch.Tensor, G0: Optional[torch.Tensor], k: int,
+                l2: float, l2_n: float) -> torch.Tensor:
+    _dev(F, off, idx, wg, wb, *([G0] if G0 is not None else []))
+    wg, wb = wg.to(torch.float32).contiguous(), wb.to(torch.float32).contiguous()
+    segs = engine.SegmentSet.from_device(off.to(torch.int64), idx.to(torch.int32), wb)          # (the set's ratings are not read)
+    return engine.wridge_rows(F, F.shape[1], k, segs, wg, wb, None if G0 is None else G0.to(torch.float64).contiguous(), l2, l2_n)
+
+
+@wridge_rows.register_fake
+def _(F, off, idx, wg, wb, G0, k, l2, l2_n):
     return F.new_empty(off.numel() - 1, F.shape[1])
 
 
